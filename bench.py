@@ -1,7 +1,7 @@
 """Headline benchmark: ray-samples/s of the HIP render path on BASELINE config 3
 (800x800 view, 64 coarse + 128 importance samples, 8x256 coarse and fine MLPs, synthetic weights).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A step renders N frames (N = number of GPUs; one frame at N = 1): every frame is sharded by row tile over the
@@ -10,14 +10,20 @@ the tiles to rank 0, so per-GPU work is fixed (640 000 rays = 122.88 M ray-sampl
 Inputs (weights, tables) are resident in HBM before the timed region; the only host->device traffic in a step
 is the 64-byte poses.  Rank 0 prints ONE JSON line.
 
-For N > 1 the line also carries, measured AFTER the timed region of the headline number:
+A plain run sets up, warms up, times K steps and prints the headline line (with `roofline`, read from the HIP events of
+the timed steps).  `--dump-outputs DIR` then writes what the last timed step handed back (rgb, depth, acc of every frame)
+as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output.  Above 64 MB in all,
+the same fixed, seeded sample of pixels is taken from every array.  Everything below (`strong`, `rccl`, `in_process`,
+`configs`, `cpu_baseline` and the parity gate of the timed frame) runs only with `--full`.
+
+With --full, for N > 1 the line also carries, measured AFTER the timed region of the headline number:
 `strong`  = BASELINE config 4: ONE 800x800 frame sharded N ways (80 000 rays per rank at N = 8) + gather, ms per frame
             (max over ranks) and the per-rank kernel time, i.e. the latency case where the last round of workgroups
             dominates - weak scaling cannot show a loss there by construction;
 `in_process` = the same single frame through nwe_render_tiled from rank 0 alone (N contexts in one process,
             hipMemcpyPeerAsync into the frame): the path a GUI thread uses.  Best effort: an error is reported, not raised.
 
-At N = 1 the line also carries `configs`: the other BASELINE.json configurations the driver's one GPU can run, measured
+With --full, at N = 1 the line also carries `configs`: the other BASELINE.json configurations one GPU can run, measured
 after the headline (kernel ms from the library's HIP events, best of three launches): C1 (64x64, 32 samples, 4x128, coarse
 only), C2 (400x400, 64 coarse samples, 8x256), the YAML's 320x240 GUI frame (64+128) and C5 on one GPU (32 poses x 800x800
 in ONE launch, frames/s).  They are parity-test cases (tests/test_gpu_parity.py), not bench lines; the numbers are there so
@@ -26,7 +32,7 @@ that the driver's record holds them.
 `roofline` prices the render kernel (the only kernel of the path) against the dense fp16 MFMA peak with the
 ALGORITHMIC FLOPs of the reference formulation (2 x GEMM MACs, SURVEY.md §8d: 1 186 816 FLOP per MLP
 evaluation, 64 coarse + 192 fine evaluations per ray); its duration comes from HIP events recorded by the
-library on the launch stream around each launch.  `cpu_baseline` times the oracle (torch CPU, the reference's
+library on the launch stream around each launch.  `cpu_baseline` (--full) times the oracle (torch CPU, the reference's
 arithmetic) as BASELINE.md section 3 plans it: four reference chunks (32 768 rays) of the same frame, extrapolated linearly,
 and C1 in full, on every host core this process may use (count stated).
 """
@@ -54,6 +60,8 @@ PEAK_F16_TFLOPS = 2500.0   # dense fp16/bf16 MFMA peak, MI355X_MICROARCH.md
 TRAFFIC_PROFILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r03_pmc_traffic.json")
 CPU_CHUNK = 8192           # inference.chunk = 1024*8 (nerf/configs/office_tokyo_config.yaml:41)
 CPU_SAMPLE_RAYS = 4 * CPU_CHUNK   # >= 4 chunks of C3, extrapolated linearly (cost per ray is constant)
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+DUMP_SEED = 0
 
 
 def sweep_pose(k: int, n: int) -> np.ndarray:
@@ -119,6 +127,21 @@ def progress(msg: str) -> None:
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def dump_outputs(frame, out_dir: str, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """What the timed path handed back in its last step ({rgb [B,H,W,3], depth [B,H,W], acc [B,H,W]}) -> out_dir/<name>.npy,
+    float32.  Above `limit` bytes in all, every array keeps the same DUMP_SEED-drawn sample of pixels (sorted), as [n, C]."""
+    arrays = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in frame.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        pixels = int(np.prod(arrays["depth"].shape))
+        n = pixels * limit // total
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, n, replace=False))
+        arrays = {k: np.ascontiguousarray(a.reshape(pixels, -1)[idx]) for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def cpu_baseline(sd_c, sd_f, pose):
     """the oracle on four 8192-ray reference chunks from the middle of the frame (the reference's
     chunking: 8192 rays per chunk, 32768 points per MLP call), and the C1 frame in full; all host threads."""
@@ -152,13 +175,18 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f16x1", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` object (C1, C2, GUI frame, C5 on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's rgb/depth/acc to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: `configs` and `cpu_baseline` with the parity gate (N = 1); `strong`, `rccl`, `in_process` (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline` and the parity gate")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the `configs` object (C1, C2, GUI frame, C5 on one GPU)")
     ap.add_argument("--in-process-probe", type=int, default=0, metavar="N",
                     help="internal: render ONE frame through nwe_render_tiled on devices 0..N-1 from this process, print a JSON object, exit")
     ap.add_argument("--unfolded", action="store_true",
                     help="comparison only: evaluate _feature_linear as its own layer instead of folding it into the view layer at pack time")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch.distributed as dist
 
@@ -243,10 +271,13 @@ def main() -> None:
     value = samples_per_step * args.steps / elapsed
     k_ms = float(np.mean(kernel_ms))
 
-    # ---- after the headline measurement: the single-frame (strong scaling) case, N > 1 only ---------------------------------
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(frame, args.dump_outputs)
+
+    # ---- after the headline measurement (--full): the single-frame (strong scaling) case, N > 1 only ------------------------
     strong = None
     rccl = None
-    if world > 1:
+    if world > 1 and args.full:
         one = poses[:1]
         skm, gms = [], []
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -354,9 +385,9 @@ def main() -> None:
             line["strong"] = strong
             line["rccl"] = rccl
             line["in_process"] = in_process_probe(args, world)
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             line["configs"] = other_configs(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rays, ref, dt, start, threads, dt_c1 = cpu_baseline(sd_c, sd_f, poses[0])
             cpu_value = CPU_SAMPLE_RAYS * (NS + NI) / dt
             line["cpu_baseline"] = {"value": cpu_value, "unit": "ray-samples/s", "cores": threads, "kind": "port",

@@ -19,7 +19,7 @@ def sampler():
 th = threading.Thread(target=sampler, daemon=True)
 th.start()
 t0 = time.time()
-p = subprocess.run([sys.executable, "bench.py", "--steps", "12", "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True)
+p = subprocess.run([sys.executable, "bench.py", "--steps", "12", "--warmup", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True)
 stop = True
 th.join(timeout=5)
 print(p.stdout[-400:])

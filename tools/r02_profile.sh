@@ -7,8 +7,8 @@ set -e
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
-rocprofv3 --kernel-trace --stats -d $OUT/r02_prof -o x --output-format csv -- python3 $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/r02_bench_under_rocprof.json 2> $OUT/r02_prof.err
+BENCH="python3 $ROOT/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline"
+rocprofv3 --kernel-trace --stats -d $OUT/r02_prof -o x --output-format csv -- python3 $ROOT/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/r02_bench_under_rocprof.json 2> $OUT/r02_prof.err
 echo "kernel trace done"
 i=0
 while read -r line; do
@@ -24,5 +24,5 @@ FETCH_SIZE
 WRITE_SIZE
 TCC_HIT_sum TCC_MISS_sum
 LIST
-cd $ROOT && python3 bench.py --steps 6 --warmup 2 > $OUT/r02_bench.json 2> $OUT/r02_bench.err
+cd $ROOT && python3 bench.py --steps 6 --warmup 2 --full > $OUT/r02_bench.json 2> $OUT/r02_bench.err
 echo "plain bench done"

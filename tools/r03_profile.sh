@@ -30,5 +30,5 @@ LIST
 # the counters become profiles/r03_pmc_traffic.json ON THIS BOX first, so that the plain run below carries this run's own
 # `traffic` (bench.py takes it only from a profile of the same kernel sources); the same summary is run again at home
 cd $ROOT && rm -f $OUT/r03_bench.json && python3 tools/r03_profile_summary.py > /dev/null
-python3 bench.py --steps 6 --warmup 2 > $OUT/r03_bench.json 2> $OUT/r03_bench.err
+python3 bench.py --steps 6 --warmup 2 --full > $OUT/r03_bench.json 2> $OUT/r03_bench.err
 echo "plain bench done"
