@@ -37,7 +37,12 @@ enum {
 };
 
 /* bits OR-ed into *nwe_outputs.flags: the reference only prints
- * "[Numerical Error] <key> contains NaN or inf." (nerf_replica_inference_handler.py:273-275) */
+ * "[Numerical Error] <key> contains NaN or inf." (nerf_replica_inference_handler.py:273-275)
+ * NWE_FLAG_RGB_COARSE is not raised by a render of pinhole views on the folded MFMA path (the default for networks with view
+ * directions) that requests nothing but rgb / depth / acc / flags, sets no test hook and has n_importance > 0: such a call
+ * evaluates only the density of the coarse samples (their weights are all the fine pass reads), so there is no coarse colour
+ * to check.  Exception: networks whose skip input enters the last trunk layer (6 deep with skips (4,)) still compute the
+ * coarse colour and report it.  Every other bit means what it means in any call. */
 enum {
     NWE_FLAG_RGB = 1u << 0, NWE_FLAG_DEPTH = 1u << 1, NWE_FLAG_ACC = 1u << 2, NWE_FLAG_DISP = 1u << 3,
     NWE_FLAG_RGB_COARSE = 1u << 4, NWE_FLAG_DEPTH_COARSE = 1u << 5, NWE_FLAG_ACC_COARSE = 1u << 6,

@@ -173,11 +173,13 @@ __device__ __forceinline__ h8 pack4(uint32_t a, uint32_t b, uint32_t c, uint32_t
 // w[row] * v for every element, in fp32 on the vector ALU.  The weights of a group (dotw: this tile's row of the table in
 // LDS, laid out like a bias row) are read in the group's fma stage and used one per later stage, so that the chain of
 // dependent FMAs on `dot` never has two links in one MFMA gap.
-template <class P, bool X3, int G, int ST, bool DOT>
+// !ACT: the activations feed nothing but the dot product (drain_dot): stages from ST_PACK on do their dot FMAs only.
+template <class P, bool X3, int G, int ST, bool DOT, bool ACT = true>
 __device__ __forceinline__ void epi_stage(const Pend& t, Epi& E, float inv_scale, float lower, h8& y0h, h8& y0l, h8& y1h, h8& y1l,
                                           const float* dotw, float& dot) {
     constexpr int st = ST, e0 = G * P::GS;
     constexpr int ST_PACK = 3, ST_RES = 4, ST_PACKLO = 5, ST_PARK = X3 ? 6 : 4;
+    static_assert(ACT || DOT, "a stage without activation output only serves the dot product");
     if constexpr (DOT) {
         static_assert(P::NS - ST_PACK >= 1, "no stage left for the dot product");
         constexpr int NDS = P::NS - ST_PACK;                       // stages that carry dot FMAs: ST_PACK .. NS-1
@@ -197,6 +199,7 @@ __device__ __forceinline__ void epi_stage(const Pend& t, Epi& E, float inv_scale
                 }                                   // sinks every FMA (and keeps every activation alive) down to it
         }
     }
+    if constexpr (!ACT && st >= ST_PACK) return;
     if (st == 0) {
 #pragma unroll
         for (int e = e0; e < e0 + P::GS; ++e) {
@@ -665,18 +668,40 @@ __device__ __forceinline__ void tile_mma(WalkerT& wk, Frags& F, int lane, bool u
     wk.tile_done();
 }
 
+// The epilogue of a pending tile whose activations feed only the dot product (the last trunk tile of a density-only evaluation,
+// see mlp_eval): ReLU (lower = 0) and the tile's share of the dot product, with no MFMA around it.  P is the plan of the tile
+// that runs this epilogue otherwise; its stages go in the same order, so the FMAs into `dot` are the same ones in the same
+// order and the sum keeps its bits.  dotw: this lane half's rows of the tile's dot-table row, as tile_mma passes it.
+template <class P, bool X3>
+__device__ __forceinline__ void drain_dot(const Pend& t, float inv_scale, const float* dotw, float& dot) {
+    if constexpr (P::STAGED) {
+        Epi E;
+        h8 d0, d1, d2, d3;
+        static_for<0, P::NG * P::NS>([&](auto sc) __attribute__((always_inline)) {
+            constexpr int s = decltype(sc)::value;
+            epi_stage<P, X3, s / P::NS, s % P::NS, true, false>(t, E, inv_scale, 0.f, d0, d1, d2, d3, dotw, dot);
+        });
+    } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dot = __builtin_fmaf(dotw[8 * (e >> 2) + (e & 3)], fmaxf(pend_value(t, e, inv_scale), 0.f), dot);
+    }
+}
+
 // A full layer of NT tiles reading X (+ gamma k-steps) and writing Y.  Tile rt accumulates into P[rt&1] while the
 // epilogue of the tile before it runs: for rt = 0 that is the LAST tile of the previous layer (in P1, destined for
 // k-steps 2*NT-2, 2*NT-1 of X itself), for rt > 0 tile rt-1 of this layer (destined for Y).  On return P1 holds
 // this layer's last tile, still pending.  Chunk sizes for the DMA schedule, in pieces per wave: this layer's chunks
 // N_THIS (+2 when use_g), the following layer's N_AFTER (+2 when extra_after), and `first_nb` = what tile 0 still
 // has to issue of chunk T+1 (0 at the very start of a pass, where chunks 0 and 1 are streamed up front).  NA_LAST: what the
-// layer's last tile starts of chunk T+2 - N_AFTER unless only ONE chunk follows the layer (kFormNoViewDirs: 0).
-template <int NT, int NKP, int NKH, bool X3, bool PEND0, int N_AFTER, bool PASS_START, bool DOT = false, int NA_LAST = N_AFTER, class WalkerT>
+// layer's last tile starts of chunk T+2 - N_AFTER unless only ONE chunk follows the layer (kFormNoViewDirs: 0).  LAST_HASNEXT =
+// false: nothing follows the layer in this evaluation (N_AFTER = 0), so its last tile prefetches no fragments either.
+template <int NT, int NKP, int NKH, bool X3, bool PEND0, int N_AFTER, bool PASS_START, bool DOT = false, int NA_LAST = N_AFTER,
+          bool LAST_HASNEXT = true, class WalkerT>
 __device__ __forceinline__ void layer(WalkerT& wk, Frags& F, int lane, bool use_g, bool extra_after, const h8* Ghi, const h8* Glo,
                                       h8* Xhi, h8* Xlo, h8* Yhi, h8* Ylo, Pend& P0, Pend& P1, float inv_scale, float lower_prev,
                                       float lower, int na_last_override = -1, const float* dot_tab = nullptr, float* dot = nullptr) {
     static_assert(NT % 2 == 0 && NT >= 4, "tiles per layer must be even (accumulator ping-pong)");
+    static_assert(LAST_HASNEXT || (N_AFTER == 0 && NA_LAST == 0), "a layer that ends the evaluation streams nothing behind it");
     constexpr int N_THIS = 2 * NKH / kWaves;
     // DOT: this layer's activations also feed a one-row linear layer; tile rt's share is accumulated with its epilogue, i.e. in
     // tile rt + 1 (row rt of dot_tab); the last tile's share rides on the epilogue the caller runs in the tile after the layer.
@@ -708,7 +733,7 @@ __device__ __forceinline__ void layer(WalkerT& wk, Frags& F, int lane, bool use_
                                                                       prev, inv_scale, lower, Yhi[2 * rt - 2], Ylo[2 * rt - 2], Yhi[2 * rt - 1],
                                                                       Ylo[2 * rt - 1], -1, drow, dot);
         } else {
-            tile_mma<NKP, NKH, 0, 0, X3, true, N_AFTER, NA_LAST, true, false, DOT>(wk, F, lane, use_g, ebB, ebA, Ghi, Glo, Xhi, Xlo, nullptr, nullptr, cur,
+            tile_mma<NKP, NKH, 0, 0, X3, true, N_AFTER, NA_LAST, LAST_HASNEXT, false, DOT>(wk, F, lane, use_g, ebB, ebA, Ghi, Glo, Xhi, Xlo, nullptr, nullptr, cur,
                                                                        prev, inv_scale, lower, Yhi[2 * rt - 2], Ylo[2 * rt - 2], Yhi[2 * rt - 1],
                                                                        Ylo[2 * rt - 1], na_last_override, drow, dot);
         }
@@ -749,6 +774,16 @@ __device__ __forceinline__ void encode(float vx, float vy, float vz, int h, h8* 
     }
 }
 
+// DMA schedule of view tile RT, in pieces per wave: chunk T+1 (NB) and chunk T+2 (NA).  Plan0: the epilogue plan of view tile 0,
+// which in FOLD finishes the last trunk tile (drain_dot replays it where no view layer follows).
+template <int W, int D, bool X3>
+struct ViewDma {
+    using S = Shape<W, D>;
+    static constexpr int nb(int rt) { return rt + 1 < S::NTV ? S::N_V : S::N_RGB; }
+    static constexpr int na(int rt) { return rt + 2 < S::NTV ? S::N_V : (rt + 2 == S::NTV ? S::N_RGB : 0); }
+    using Plan0 = EpiPlan<X3, S::KH, S::KH + S::KD, true, DmaPlan<nb(0), na(0), S::KH + S::KD>::mask()>;
+};
+
 // View-layer tiles RT..NTV-1 (compile-time recursion: the DMA schedule and the ring phase depend on RT).  Each tile has
 // KH + KD k-steps, which shifts the fragment ring by (KH+KD) mod (PD+1) per tile.
 // SIGMA_TILE (the unfolded formulation): tile 0 follows the alpha tile, which has no activation output to finish; tile RT
@@ -764,8 +799,8 @@ __device__ __forceinline__ void view_tiles(WalkerT& wk, Frags& F, int lane, h8* 
     Pend& cur = par ? P1 : P0;
     Pend& prev = par ? P0 : P1;
     constexpr int PH = (RT * (S::KH + S::KD)) % (PD + 1);
-    constexpr int NB = RT + 1 < S::NTV ? S::N_V : S::N_RGB;                            // chunk T+1
-    constexpr int NA = RT + 2 < S::NTV ? S::N_V : (RT + 2 == S::NTV ? S::N_RGB : 0);   // chunk T+2
+    constexpr int NB = ViewDma<W, D, X3>::nb(RT);   // chunk T+1
+    constexpr int NA = ViewDma<W, D, X3>::na(RT);   // chunk T+2
     if constexpr (RT == 0 && SIGMA_TILE) {
         h8 d0, d1, d2, d3;
         tile_mma<0, S::KH, S::KD, PH, X3, false, NB, NA, true>(wk, F, lane, false, false, false, nullptr, nullptr, Ahi, Alo, GDhi, GDlo, cur,
@@ -783,6 +818,17 @@ __device__ __forceinline__ void view_tiles(WalkerT& wk, Frags& F, int lane, h8* 
     if constexpr (RT + 1 < S::NTV) view_tiles<RT + 1, W, D, X3, SIGMA_TILE>(wk, F, lane, Ahi, Alo, GDhi, GDlo, Bhi, Blo, P0, P1, inv_scale);
 }
 
+#ifndef NWE_COARSE_DENSITY_ONLY
+#define NWE_COARSE_DENSITY_ONLY 1   // density-only coarse evaluations in lean frames (mlp_eval); 0 = every evaluation runs the view layer and rgb head
+#endif
+// Whether mlp_eval has the density-only path for a shape: every folded shape except those whose gamma(x) skip input enters the
+// last trunk layer (6-deep with skips (4,)).  There the second copy of that layer carries the gamma(x) k-steps too, and the
+// three-pass LEAN kernels spill (36 / 64 B of scratch per lane at 6x256); those shapes keep computing the coarse colour.
+template <int D, int SKIP>
+constexpr bool density_only_built(int form) {
+    return NWE_COARSE_DENSITY_ONLY != 0 && form == kFormFolded && !(SKIP >= 0 && SKIP / 2 == D / 2 - 1);
+}
+
 // One MLP evaluation for the wave's 32 points.  nerf/models/nerf_model.py:45-83.
 // Trunk layers run as pairs A->B, B->A so that the two activation register sets keep fixed names inside a rolled loop;
 // every tile's epilogue is deferred into the next tile (see Pend).
@@ -795,10 +841,12 @@ __device__ __forceinline__ void view_tiles(WalkerT& wk, Frags& F, int lane, h8* 
 // kFormNoViewDirs (use_view_dirs=False, nerf_model.py:42-43,78-79): the trunk as in FOLD (D/2 - 1 pairs and the single last
 // layer A -> B, without the dot product), then ONE tile of _output_linear on B = h whose rows 0..3 are rgb_raw, sigma_raw
 // (copies in rows 4..7 for the upper lane half; the reference ignores the fifth channel too: model_utils.py:62,71).
+// density_only (wave-uniform; honoured where density_only_built): sigma is all the caller reads, so the evaluation ends with
+// the trunk (see below) and returns o_r = o_g = o_b = 0.
 // On entry chunks 0 and 1 of the stream are visible / in flight and F holds the first PD k-steps of chunk 0.
 template <int W, int D, int SKIP, bool X3, int FORM, class WalkerT>
 __device__ __forceinline__ void mlp_eval(WalkerT& wk, Frags& F, int lane, float inv_scale, h8* Ghi, h8* Glo, const char* gd_lds,
-                                         const float* dot_tab, float& o_r, float& o_g, float& o_b, float& o_s) {
+                                         const float* dot_tab, bool density_only, float& o_r, float& o_g, float& o_b, float& o_s) {
     using S = Shape<W, D>;
     static_assert(D % 2 == 0, "trunk depth must be even");
     static_assert(SKIP < 0 || SKIP % 2 == 0, "skip layer index must be even");
@@ -843,12 +891,45 @@ __device__ __forceinline__ void mlp_eval(WalkerT& wk, Frags& F, int lane, float 
         }
     }
     float sig = 0.f;   // FOLD: this lane half's share of _alpha_linear . h
+    // both lane halves hold half of the features: the other half's share comes over the 32-lane swap; the row behind the
+    // weights holds the bias in element 0
+    auto sigma_of = [&]() __attribute__((always_inline)) { return __fadd_rn(__fadd_rn(sig, __shfl_xor(sig, 32, 64)), dot_tab[S::NT * 32]); };
     if constexpr (FOLD) {
         // FOLD: the last trunk layer stands alone (A -> B); behind it comes the view layer at once (its chunks are N_V pieces).
         // _alpha_linear (nerf_model.py:63) is one output row on this layer's activations h: sigma = w . h + b is accumulated
         // in fp32 on the vector ALU with the tiles' epilogues (row rt of dot_tab holds w[32 rt .. 32 rt + 31]) instead of a
         // 32-row MFMA tile of which one row would be used (48 of 3168 MFMAs, 16 KB of the weight stream per evaluation).
         constexpr bool G_LAST = SKIP_PAIR == NPAIR - 1;
+        if constexpr (density_only_built<D, SKIP>(FORM)) {
+            if (density_only) {
+                // Density only (the coarse pass of a lean frame with importance sampling: its colour is never read, only its weights,
+                // which depend on sigma alone): the last trunk layer a second time, with nothing streamed behind it - its last two
+                // tiles start no DMA of chunks T+1 / T+2 and the last one prefetches no fragments - and the view layer and rgb head
+                // (240 of 3120 MFMAs and 160 of 2080 KiB of weight tiles at 8x256) are skipped.  The last trunk tile's epilogue
+                // (pending in P1), which view tile 0 runs otherwise, is reduced to what sigma needs: ReLU and row NT-1 of the dot
+                // product, in view tile 0's order.  Every FMA into `sig` is the one of the full evaluation in the same order, so
+                // sigma has the same bits.
+                // End of the evaluation: no DMA is in flight (the last piece, of this layer's last chunk, was waited for at the
+                // barrier of tile NT-2), and across the last tile's barrier each wave has at most the two reads of that chunk's TAIL
+                // SLOT outstanding, consumed by its own last MFMAs (Walker timeline) - every read of a chunk buffer had completed
+                // before any wave passed that barrier.  The next evaluation's first pieces (issued at once, before any barrier) write
+                // chunk buffers 0 and 1 only; the first piece that writes a tail slot is issued behind that evaluation's first
+                // barriers, which no wave reaches before its last MFMA here.  So nothing lands where a read can still be pending.
+                using TrunkA = EpiPlan<X3, S::KH, S::KH, false, DmaPlan<S::N_H, S::N_V, S::KH>::mask()>;   // tile NT-2, full / here
+                using TrunkA0 = EpiPlan<X3, S::KH, S::KH, false, DmaPlan<S::N_H, 0, S::KH>::mask()>;
+                using TrunkB = EpiPlan<X3, S::KH, S::KH, false, DmaPlan<S::N_V, S::N_V, S::KH>::mask()>;   // tile NT-1, full / here
+                using TrunkB0 = EpiPlan<X3, S::KH, S::KH, false, DmaPlan<0, 0, S::KH>::mask()>;
+                static_assert(TrunkA::NG == TrunkA0::NG && TrunkB::NG == TrunkB0::NG,
+                              "the last trunk tiles must run the epilogues they carry in the full evaluation's order (dot FMAs)");
+                static_assert(!G_LAST, "density_only_built: the last trunk layer takes no gamma(x) k-steps here");
+                layer<S::NT, 0, S::KH, X3, true, 0, false, true, 0, false>(wk, F, lane, false, false, nullptr, nullptr, Ahi, Alo, Bhi, Blo, P0, P1,
+                                                                           inv_scale, 0.f, 0.f, -1, dot_tab, &sig);
+                drain_dot<typename ViewDma<W, D, X3>::Plan0, X3>(P1, inv_scale, dot_tab + (S::NT - 1) * 32 + 4 * (lane >> 5), sig);
+                o_s = sigma_of();
+                o_r = o_g = o_b = 0.f;
+                return;
+            }
+        }
         layer<S::NT, G_LAST ? S::KG : 0, S::KH, X3, true, S::N_V, false, true>(wk, F, lane, G_LAST, false, Ghi, Glo, Ahi, Alo, Bhi, Blo, P0, P1,
                                                                                inv_scale, 0.f, 0.f, -1, dot_tab, &sig);
     }
@@ -884,9 +965,7 @@ __device__ __forceinline__ void mlp_eval(WalkerT& wk, Frags& F, int lane, float 
         // Its first tile runs the epilogue of the last trunk tile (P1, NT even): ReLU into the last two k-steps of B itself and
         // the last share of the alpha dot product.  Tile RT accumulates in P[RT & 1], so the last one (NTV even) is in P1.
         view_tiles<0, W, D, X3, false>(wk, F, lane, Bhi, Blo, GDhi, GDlo, Ahi, Alo, P0, P1, inv_scale, dot_tab, &sig);
-        // both lane halves hold half of the features: the other half's share comes over the 32-lane swap; the row behind the
-        // weights holds the bias in element 0
-        const float sigma = __fadd_rn(__fadd_rn(sig, __shfl_xor(sig, 32, 64)), dot_tab[S::NT * 32]);
+        const float sigma = sigma_of();
         // rgb head (nerf_model.py:74) in P0 while the last view tile (P1) is finished into A; rows 0..2 and their copies 4..6
         // for the upper lane half.  Nothing is streamed behind it: the caller starts the next pass.
         tile_mma<0, S::KV, 0, 0, X3, true, 0, 0, false, true>(wk, F, lane, false, false, false, nullptr, nullptr, Ahi, Alo, nullptr, nullptr, P0,
@@ -1046,6 +1125,9 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
         const float* bias = s_bias + (pass == 0 ? 0 : SM::BIAS_BYTES / 4);
         const float* dot_tab = bias + NCH * 32;
         const int Stot = pass == 0 ? ns : ns + ni;
+        // a lean frame with importance sampling reads nothing of the coarse pass but its weights, which depend on sigma alone
+        // (mlp_eval: density_only); with ni == 0 the coarse colour is the frame's colour
+        const bool density_only = LEAN && density_only_built<D, SKIP>(FORM) && pass == 0 && ni > 0;
         const float* noise = pass == 0 ? a.noise_c : a.noise_f;
         const float* raw_in = pass == 0 ? a.raw_in_c : a.raw_in_f;   // test hook: network outputs from the caller (uniform)
         if (pass == 0 && a.w_in) {                                   // test hook: coarse weights from the caller, no coarse pass
@@ -1149,7 +1231,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                 wk.st_t0 = t2;
                 st_sync += t2 - t1;
 #endif
-                mlp_eval<W, D, SKIP, X3, FORM>(wk, F, lane, net.inv_scale, Ghi, Glo, gd_lds, dot_tab, rr, rg, rb, rs);
+                mlp_eval<W, D, SKIP, X3, FORM>(wk, F, lane, net.inv_scale, Ghi, Glo, gd_lds, dot_tab, density_only, rr, rg, rb, rs);
 #ifdef NWE_STAMPS
                 st_mlp += __builtin_amdgcn_s_memtime() - t2;
 #endif
@@ -1238,7 +1320,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                 wk.st_t0 = t2;
                 st_sync += t2 - t1;
     #endif
-                mlp_eval<W, D, SKIP, X3, FORM>(wk, F, lane, net.inv_scale, Ghi, Glo, gd_lds, dot_tab, rr, rg, rb, rs);
+                mlp_eval<W, D, SKIP, X3, FORM>(wk, F, lane, net.inv_scale, Ghi, Glo, gd_lds, dot_tab, density_only, rr, rg, rb, rs);
     #ifdef NWE_STAMPS
                 st_mlp += __builtin_amdgcn_s_memtime() - t2;
     #endif
@@ -1264,7 +1346,8 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
             }
         }
         if (live) {
-            flags |= store_ray(a.out, ridx, comp, pass == 1, a.white_bkgd != 0);
+            // density-only coarse pass: there is no coarse colour whose flag could be raised (include/nwe.h)
+            flags |= store_ray(a.out, ridx, comp, pass == 1, a.white_bkgd != 0) & (density_only ? ~(uint32_t)NWE_FLAG_RGB_COARSE : ~0u);
             if (ni == 0) flags |= store_ray(a.out, ridx, comp, true, a.white_bkgd != 0);
         }
     }
