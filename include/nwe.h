@@ -42,7 +42,11 @@ enum {
  * directions) that requests nothing but rgb / depth / acc / flags, sets no test hook and has n_importance > 0: such a call
  * evaluates only the density of the coarse samples (their weights are all the fine pass reads), so there is no coarse colour
  * to check.  Exception: networks whose skip input enters the last trunk layer (6 deep with skips (4,)) still compute the
- * coarse colour and report it.  Every other bit means what it means in any call. */
+ * coarse colour and report it.  Every other bit means what it means in any call.
+ * fp16 range (NWE_PREC_F16X3 / F16X1): hidden activations are split into fp16 hi + lo, so an activation of 65520 or more (hi =
+ * inf) cannot be represented.  The MFMA kernels keep the resulting NaN through their ReLUs and the compositing's relu(sigma), so
+ * such a call raises NWE_FLAG_RAW (when raw outputs are requested) and the rgb / depth / acc bits instead of returning finite,
+ * wrong values.  NWE_PREC_F32 has no such limit. */
 enum {
     NWE_FLAG_RGB = 1u << 0, NWE_FLAG_DEPTH = 1u << 1, NWE_FLAG_ACC = 1u << 2, NWE_FLAG_DISP = 1u << 3,
     NWE_FLAG_RGB_COARSE = 1u << 4, NWE_FLAG_DEPTH_COARSE = 1u << 5, NWE_FLAG_ACC_COARSE = 1u << 6,

@@ -152,7 +152,8 @@ struct Composite {
                                                    bool last, float dnorm, float noise = 0.f) {
         float dist = last ? 1e10f : __fsub_rn(z_next, z);                    // :51-56
         dist = __fmul_rn(dist, dnorm);                                       // :60
-        const float sig = fmaxf(__fadd_rn(raw_s, noise), 0.f);               // relu(raw + noise), :49,:71 (noise = 0. in inference)
+        // relu(raw + noise), :49,:71 (noise = 0. in inference); a NaN stays NaN as in torch's relu (fmaxf would make it 0)
+        const float sig = __builtin_elementwise_maximum(__fadd_rn(raw_s, noise), 0.f);
         const float alpha = __fsub_rn(1.f, expf(-__fmul_rn(sig, dist)));     // :49
         const float cr = __fdiv_rn(1.f, __fadd_rn(1.f, expf(-raw_r)));       // sigmoid, :62
         const float cg = __fdiv_rn(1.f, __fadd_rn(1.f, expf(-raw_g)));

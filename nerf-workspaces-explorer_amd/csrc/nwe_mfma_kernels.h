@@ -85,6 +85,12 @@ struct Pend {
     float4 bias[4];   // register 4g+i holds row 8g + 4h + i -> bias[g].{x,y,z,w}
 };
 
+// ReLU (lower = 0) or pass-through (lower = -inf) of an activation that KEEPS a NaN: v_maximum3_f32, one instruction like the
+// v_max_f32 of fmaxf, which returns the other operand for a NaN.  An activation >= 65520 has hi = fp16(v) = inf and a NaN
+// residual product in the next layer's accumulators; with fmaxf that NaN became a finite, wrong 0.  Kept, it reaches the raw
+// outputs and the NWE_FLAG_* bits (include/nwe.h, "fp16 range").
+__device__ __forceinline__ float act(float v, float lower) { return __builtin_elementwise_maximum(v, lower); }
+
 __device__ __forceinline__ float pend_value(const Pend& t, int r, float inv_scale) {
     const float4 b = t.bias[r >> 2];
     const float bb = (r & 3) == 0 ? b.x : ((r & 3) == 1 ? b.y : ((r & 3) == 2 ? b.z : b.w));
@@ -99,7 +105,7 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 template <bool X3, bool DOT = false>
 __device__ __forceinline__ void finish_elem(const Pend& t, int e, float inv_scale, float lower, float& keep, h8& hi0, h8& lo0,
                                             h8& hi1, h8& lo1, const float* dotw = nullptr, float* dot = nullptr) {
-    const float v = fmaxf(pend_value(t, e, inv_scale), lower);
+    const float v = act(pend_value(t, e, inv_scale), lower);
     if (DOT) *dot = __builtin_fmaf(dotw[8 * (e >> 2) + (e & 3)], v, *dot);   // dotw already points at this lane half's rows
     if ((e & 1) == 0) { keep = v; return; }
     const float v0 = keep, v1 = v;
@@ -219,7 +225,7 @@ __device__ __forceinline__ void epi_stage(const Pend& t, Epi& E, float inv_scale
         }
     } else if (st == 2) {
 #pragma unroll
-        for (int e = e0; e < e0 + P::GS; ++e) E.v[e] = fmaxf(E.v[e], lower);
+        for (int e = e0; e < e0 + P::GS; ++e) E.v[e] = act(E.v[e], lower);
     } else if (st == ST_PACK) {
 #pragma unroll
         for (int p = e0 / 2; p < (e0 + P::GS) / 2; ++p) {
@@ -683,7 +689,7 @@ __device__ __forceinline__ void drain_dot(const Pend& t, float inv_scale, const 
         });
     } else {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) dot = __builtin_fmaf(dotw[8 * (e >> 2) + (e & 3)], fmaxf(pend_value(t, e, inv_scale), 0.f), dot);
+        for (int e = 0; e < 16; ++e) dot = __builtin_fmaf(dotw[8 * (e >> 2) + (e & 3)], act(pend_value(t, e, inv_scale), 0.f), dot);
     }
 }
 

@@ -72,7 +72,8 @@ def ref_volumetric_rendering(ray_batch, net_c, net_f, n_samples, n_importance, n
     rays_o, rays_d, viewdirs = ray_batch[:, 0:3], ray_batch[:, 3:6], ray_batch[:, -3:]
     bounds = torch.reshape(ray_batch[..., 6:8], [-1, 1, 2])
     near, far = bounds[..., 0], bounds[..., 1]
-    t_vals = torch.linspace(0., 1., steps=n_samples)
+    # fp64 rays: the fp32 table is widened before 1 - t (nerf_oracle.py's fp64 mode: every operation after the inputs in fp64)
+    t_vals = torch.linspace(0., 1., steps=n_samples).to(ray_batch.dtype)
     z_vals = near * (1. - t_vals) + far * (t_vals)
     z_vals = z_vals.expand([ray_batch.shape[0], n_samples])
     pts = rays_o[..., None, :] + rays_d[..., None, :] * z_vals[..., :, None]
@@ -412,6 +413,48 @@ def main() -> None:
         var["ep_" + k] = ref[k].numpy()
     var["ep_sigma_last_fine"] = ref["raw_fine"][:, -1, 3].numpy()
     np.savez_compressed(os.path.join(GOLD, "variants.npz"), **var)
+
+    # (11) the fp64 ground truth --------------------------------------------------------------------------
+    # The reference's blocks on fp64 inputs (NeRFModel.double(); Embedding, raw2outputs and sample_pdf by type promotion of
+    # their fp32 constants and tables) against the oracle's explicit fp64 mode (nerf_oracle.py, dtype=torch.float64): inputs
+    # keep their fp32 values, everything after them runs in fp64.  tests/test_gpu_accuracy.py measures every kernel mode
+    # against this mode.
+    print("[11] fp64 ground truth")
+    f64 = {}
+    D64 = torch.float64
+    same(O.embed(pts.double(), 10, 10), e3.embed(pts.double()), "fp64 embed xyz")
+    same(O.embed(dirs.double(), 4, 1), e2.embed(dirs.double()), "fp64 embed dir")
+    for tag, (D, W, seed) in {"4x128": (4, 128, 1000), "8x256": (8, 256, 1001)}.items():
+        sd = synthetic.make_state_dict(seed, D, W)
+        x = torch.from_numpy(mlp_out[f"x_{tag}"]).double()
+        ref = load_ref_model(D, W, sd).double()(x)
+        same(O.mlp_forward(O.cast_state({k: torch.from_numpy(v) for k, v in sd.items()}, D64), x), ref, f"fp64 mlp {tag}")
+        f64[f"mlp_y_{tag}"] = ref.numpy()
+    g4 = np.load(os.path.join(GOLD, "raw2outputs.npz"))
+    raw4, z4, d4 = (torch.from_numpy(g4[k]).double() for k in ("raw", "z", "d"))
+    ref = ref_raw2outputs(raw4, z4, d4, 0, False, endpoint_feat=False, cuda_enabled=False)
+    for nm, a_, b_ in zip(("rgb", "disp", "acc", "weights", "depth"), O.raw2outputs(raw4, z4, d4), ref[:5]):
+        same(a_, b_, f"fp64 raw2outputs {nm}")
+        f64[f"r2o_{nm}"] = b_.numpy()
+    ref = ref_sample_pdf(zmid.double(), w.double(), Ni, det=True)
+    same(O.sample_pdf(zmid.double(), w.double(), Ni), ref, "fp64 sample_pdf")
+    f64["pdf_samples"] = ref.numpy()
+    # 256 rays of the C3 hor30 subset with the bench networks (64 + 128)
+    full = ref_create_rays(1, POSES["hor30"], 800, 800, fx, fy, cx, cy, 0.1, 10.0, True)[0]
+    idx11 = ((torch.arange(4096) * 156 + 77) % (800 * 800))[::16]
+    rays11 = full[idx11].contiguous()
+    ref = ref_volumetric_rendering(rays11.double(), net_c.double(), net_f.double(), 64, 128, 1024 * 32)
+    mine = O.render_rays(rays11, tc, tf, O.RenderConfig(), dtype=D64)
+    for k in ref:
+        assert ref[k].dtype == D64, (k, ref[k].dtype)
+        same(mine[k], ref[k], f"fp64 C3-subset hor30 {k}")
+    f64["e2e_idx"] = idx11.numpy()
+    for k in ("rgb_fine", "depth_fine", "acc_fine", "disp_fine", "z_std", "rgb_coarse", "depth_coarse", "acc_coarse"):
+        f64["e2e_" + k] = ref[k].numpy()
+    f64["e2e_z_samples_first32"] = ref["z_samples"][:32].numpy()
+    f64["e2e_raw_fine_first8"] = ref["raw_fine"][:8].numpy()
+    net_c.float(), net_f.float()
+    np.savez_compressed(os.path.join(GOLD, "f64.npz"), **f64)
     print("goldens written to", GOLD)
 
 

@@ -16,6 +16,13 @@ not installed: that one function is "parity unpinned" (SURVEY.md §8c).
 
 All arithmetic is fp32 torch ops in the same order as the reference so that
 the results are bit-identical to the reference on the same torch build.
+
+fp64 ground truth: ``render_rays`` / ``volumetric_rendering`` / ``run_network`` take ``dtype=torch.float64``.  The inputs
+keep their fp32 values (the [N,11] rays, the network weights and the ``linspace`` tables of t and u, which the kernel
+reproduces bit for bit) and are widened exactly; every operation after that runs in fp64, in the reference's order.  The
+reference's own blocks run the same way on fp64 inputs by type promotion; ``oracle/make_goldens.py`` checks that the two
+agree bit for bit and ``tests/golden/f64.npz`` pins it.
+
 Citations are ``file:line`` relative to the reference root.
 """
 from __future__ import annotations
@@ -75,7 +82,7 @@ def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, n_samples: int, u: Opt
     if u is None:
         u = torch.linspace(0., 1., steps=n_samples)                 # rays.py:95
         u = u.expand(list(cdf.shape[:-1]) + [n_samples])
-    u = u.contiguous()                                              # rays.py:101
+    u = u.to(cdf.dtype).contiguous()                                # rays.py:101 (fp64 mode: the fp32 table, widened)
     inds = torch.searchsorted(cdf, u, right=True)                   # rays.py:103
     below = torch.clamp(inds - 1, min=0)                            # rays.py:104
     above = torch.clamp(inds, max=cdf.shape[-1] - 1)                # rays.py:105
@@ -133,7 +140,7 @@ def embed(x: torch.Tensor, num_freqs: int, scalar_factor: float) -> torch.Tensor
     nerf/models/embedding.py:24-48.  3-wide groups, identity first.
     """
     v = x / scalar_factor                                           # embedding.py:48 (true division)
-    bands = 2. ** torch.linspace(0., num_freqs - 1, steps=num_freqs)  # embedding.py:32
+    bands = (2. ** torch.linspace(0., num_freqs - 1, steps=num_freqs)).to(v.dtype)  # embedding.py:32 (powers of two: exact)
     parts = [v]
     for f in bands:
         parts.append(torch.sin(v * f))
@@ -187,10 +194,21 @@ def mlp_forward(state: Dict[str, torch.Tensor], x: torch.Tensor, show_endpoint: 
     return torch.cat([out, g], -1) if show_endpoint else out                                 # :78-81
 
 
+def cast_state(state: Dict[str, torch.Tensor], dtype: torch.dtype) -> Dict[str, torch.Tensor]:
+    """The weights widened (or kept) to `dtype`; fp32 -> fp64 is exact."""
+    return {k: v.to(dtype) for k, v in state.items()}
+
+
 def run_network(pts: torch.Tensor, viewdirs: Optional[torch.Tensor], state: Dict[str, torch.Tensor],
-                freqs_xyz: int, freqs_dir: int, netchunk: int, show_endpoint: bool = False) -> torch.Tensor:
+                freqs_xyz: int, freqs_dir: int, netchunk: int, show_endpoint: bool = False,
+                dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """[N,S,3] points + [N,3] view dirs (None: 8-column rays of use_view_dirs=False) -> raw [N,S,C].
-    nerf/models/model_utils.py:13-30 and utils/batch_utils.py:28-39 (the point-chunk loop)."""
+    nerf/models/model_utils.py:13-30 and utils/batch_utils.py:28-39 (the point-chunk loop).
+    dtype (default: that of `pts`): points, directions and weights are cast to it first, then everything runs in it."""
+    dtype = dtype or pts.dtype
+    if pts.dtype != dtype or next(iter(state.values())).dtype != dtype:
+        pts, state = pts.to(dtype), cast_state(state, dtype)
+        viewdirs = None if viewdirs is None else viewdirs.to(dtype)
     flat = pts.reshape(-1, 3)
     enc = embed(flat, freqs_xyz, 10)                                 # handler.py:93 (scalar_factor=10)
     if viewdirs is not None:                                         # model_utils.py:22
@@ -213,11 +231,11 @@ def raw2outputs(raw: torch.Tensor, z_vals: torch.Tensor, rays_d: torch.Tensor, w
     `torch.randn(raw[..., 3].shape) * raw_noise_std` (:64-66), None = raw_noise_std 0 (:69, noise = 0.).
     """
     dists = z_vals[..., 1:] - z_vals[..., :-1]                                       # :51
-    dists = torch.cat([dists, torch.Tensor([1e10]).expand(dists[..., :1].shape)], -1)  # :56
+    dists = torch.cat([dists, torch.tensor([1e10], dtype=dists.dtype).expand(dists[..., :1].shape)], -1)  # :56 (1e10 is exact in fp32)
     dists = dists * torch.norm(rays_d[..., None, :], dim=-1)                         # :60
     rgb = torch.sigmoid(raw[..., :3])                                                # :62
     alpha = 1. - torch.exp(-F.relu(raw[..., 3] + (0. if noise is None else noise)) * dists)   # :49,:71
-    trans = torch.cumprod(torch.cat([torch.ones((alpha.shape[0], 1)), 1. - alpha + 1e-10], -1), -1)[:, :-1]  # :79-80
+    trans = torch.cumprod(torch.cat([torch.ones((alpha.shape[0], 1), dtype=alpha.dtype), 1. - alpha + 1e-10], -1), -1)[:, :-1]  # :79-80
     weights = alpha * trans
     rgb_map = torch.sum(weights[..., None] * rgb, -2)                                # :84
     depth_map = torch.sum(weights * z_vals, -1)                                      # :93
@@ -248,7 +266,8 @@ class RenderConfig:
 
 def volumetric_rendering(ray_batch: torch.Tensor, coarse: Dict[str, torch.Tensor],
                          fine: Optional[Dict[str, torch.Tensor]], cfg: RenderConfig,
-                         train: Optional[Dict[str, Optional[torch.Tensor]]] = None) -> Dict[str, torch.Tensor]:
+                         train: Optional[Dict[str, Optional[torch.Tensor]]] = None,
+                         dtype: Optional[torch.dtype] = None) -> Dict[str, torch.Tensor]:
     """One ray chunk [N,11] -> the output dict of handler.py:203-277.
 
     With n_importance == 0 the reference raises UnboundLocalError (handler.py:263); here the coarse
@@ -259,13 +278,20 @@ def volumetric_rendering(ray_batch: torch.Tensor, coarse: Dict[str, torch.Tensor
     (randn * raw_noise_std, model_utils.py:64-66), "u" [N,Ni] (rays.py:98).  That handler cannot be imported here
     (hard-coded .cuda(), tensorboard); the jitter lines are restated from the file, raw2outputs' noise branch and
     sample_pdf's det=False branch are pinned against the reference by tests/golden/train_mode.npz.
+
+    dtype (default: that of `ray_batch`): rays, weights and `train` tensors are cast to it, the t / u tables are the fp32
+    linspace values cast to it; float64 gives the fp64 ground truth of the module docstring.
     """
-    train = train or {}
+    dtype = dtype or ray_batch.dtype
+    ray_batch = ray_batch.to(dtype)
+    coarse = cast_state(coarse, dtype)
+    fine = None if fine is None else cast_state(fine, dtype)
+    train = {k: (None if v is None else v.to(dtype)) for k, v in (train or {}).items()}
     rays_o, rays_d = ray_batch[:, 0:3], ray_batch[:, 3:6]                                 # :210
     viewdirs = ray_batch[:, -3:] if ray_batch.shape[-1] > 8 else None                     # :211 (8 columns: use_view_dirs=False)
     bounds = ray_batch[..., 6:8].reshape(-1, 1, 2)
     near, far = bounds[..., 0], bounds[..., 1]                                            # :213-214
-    t_vals = torch.linspace(0., 1., steps=cfg.n_samples)                                  # :216
+    t_vals = torch.linspace(0., 1., steps=cfg.n_samples).to(dtype)                        # :216
     z_vals = near * (1. - t_vals) + far * t_vals                                          # :218
     z_vals = z_vals.expand([ray_batch.shape[0], cfg.n_samples])
     if train.get("t_rand") is not None:                                                   # training_handler.py:553-562
@@ -309,14 +335,16 @@ def fine_pass_given_depths(ray_batch: torch.Tensor, z_all: torch.Tensor, fine: D
 
 def render_rays(flat_rays: torch.Tensor, coarse, fine, cfg: RenderConfig,
                 keep: Optional[Sequence[str]] = None,
-                train: Optional[Dict[str, Optional[torch.Tensor]]] = None) -> Dict[str, torch.Tensor]:
+                train: Optional[Dict[str, Optional[torch.Tensor]]] = None,
+                dtype: Optional[torch.dtype] = None) -> Dict[str, torch.Tensor]:
     """All rays of a frame in `cfg.chunk`-ray chunks, concatenated per key.
-    utils/batch_utils.py:7-25 + handler.py:187-201.  `keep` limits the keys retained (memory)."""
+    utils/batch_utils.py:7-25 + handler.py:187-201.  `keep` limits the keys retained (memory).
+    dtype=torch.float64: the fp64 ground truth (volumetric_rendering)."""
     parts: Dict[str, list] = {}
     with torch.no_grad():
         for i in range(0, flat_rays.shape[0], cfg.chunk):
             tr = None if train is None else {k: (None if v is None else v[i:i + cfg.chunk]) for k, v in train.items()}
-            res = volumetric_rendering(flat_rays[i:i + cfg.chunk], coarse, fine, cfg, tr)
+            res = volumetric_rendering(flat_rays[i:i + cfg.chunk], coarse, fine, cfg, tr, dtype)
             for k, v in res.items():
                 if keep is None or k in keep:
                     parts.setdefault(k, []).append(v)

@@ -211,3 +211,43 @@ def test_model_variants(golden_dir):
     for k in ("rgb_fine", "depth_fine", "acc_fine", "feat_map_fine", "z_fine"):
         _close(out[k].numpy(), g["ep_" + k])
     assert out["feat_map_fine"].shape == (256, 128)
+
+
+F64_TOL = 1e-10     # relative: bit-exact on the torch build f64.npz was made with; another CPU kernel selection may move last bits
+
+
+def test_fp64_ground_truth(golden_dir):
+    """The oracle's fp64 mode (dtype=torch.float64) against the reference's own blocks run in fp64 (tests/golden/f64.npz):
+    the MLP, compositing and sampler vectors, and 256 rays of the C3 hor30 subset with the bench networks end to end."""
+    g = _load(golden_dir, "f64.npz")
+    D64 = torch.float64
+    m = _load(golden_dir, "mlp.npz")
+    for tag, (D, W, seed) in {"4x128": (4, 128, 1000), "8x256": (8, 256, 1001)}.items():
+        sd = O.cast_state({k: torch.from_numpy(v) for k, v in nwe_amd.synthetic.make_state_dict(seed, D, W).items()}, D64)
+        y = O.mlp_forward(sd, torch.from_numpy(m[f"x_{tag}"]).double()).numpy()
+        assert y.dtype == np.float64
+        _close(y, g[f"mlp_y_{tag}"], F64_TOL)
+        assert np.abs(y - m[f"y_{tag}"]).max() > 0          # the fp32 golden is a different (rounded) answer
+    r = _load(golden_dir, "raw2outputs.npz")
+    out = O.raw2outputs(*(torch.from_numpy(r[k]).double() for k in ("raw", "z", "d")))
+    for nm, v in zip(("rgb", "disp", "acc", "weights", "depth"), out):
+        assert v.dtype == D64
+        _close(v.numpy(), g[f"r2o_{nm}"], F64_TOL)
+    p = _load(golden_dir, "sample_pdf.npz")
+    _close(O.sample_pdf(torch.from_numpy(p["bins"]).double(), torch.from_numpy(p["weights"]).double(), 128).numpy(), g["pdf_samples"], F64_TOL)
+    c = _load(golden_dir, "e2e_c3_subset.npz")
+    fx, fy, cx, cy = O.intrinsics(800, 800)
+    full = O.create_rays(torch.from_numpy(c["pose_hor30"])[None], 800, 800, fx, fy, cx, cy, 0.1, 10.0)[0]
+    idx = torch.from_numpy(g["e2e_idx"])
+    assert np.array_equal(g["e2e_idx"], c["idx_hor30"][::16])
+    t = lambda sd: {k: torch.from_numpy(v) for k, v in sd.items()}
+    res = O.render_rays(full[idx].contiguous(), t(nwe_amd.synthetic.make_state_dict(1000, 8, 256)),
+                        t(nwe_amd.synthetic.make_state_dict(1001, 8, 256)), O.RenderConfig(), dtype=D64)
+    for k in ("rgb_fine", "depth_fine", "acc_fine", "disp_fine", "z_std", "rgb_coarse", "depth_coarse", "acc_coarse"):
+        assert res[k].dtype == D64
+        _close(res[k].numpy(), g["e2e_" + k], F64_TOL)
+    _close(res["z_samples"][:32].numpy(), g["e2e_z_samples_first32"], F64_TOL)
+    _close(res["raw_fine"][:8].numpy(), g["e2e_raw_fine_first8"], F64_TOL)
+    # the fp32 reference on the same rays is a rounded version of it, not equal to it
+    ref32 = c["rgb_fine_hor30"][::16]
+    assert 0 < np.abs(ref32 - g["e2e_rgb_fine"]).max() < 1e-2
