@@ -127,7 +127,11 @@ int nwe_set_network_no_view_dirs(nwe_ctx *ctx, int which, int depth, int width, 
 /* Sampling tables computed by the host with torch.linspace (its bits are not i/(n-1)):
  *   t_vals[n_samples] = linspace(0,1,Ns) and one_minus_t[n_samples] = 1 - t_vals  (handler.py:216-218)
  *   u[n_importance]   = linspace(0,1,Ni)                                        (nerf/rays/rays.py:95)
- * n_importance may be 0 (coarse only; u may then be NULL). */
+ * n_importance may be 0 (coarse only; u may then be NULL).
+ * nwe_render is asynchronous, so this call and nwe_set_network[_no_view_dirs] first wait for every launch of this context
+ * that is still in flight, on whatever stream, before they touch the device tables and weights those launches read: the
+ * caller need not synchronise before reconfiguring.  (nwe_set_white_background and the other host-side switches are copied
+ * at launch and never reach a launch already queued.) */
 int nwe_set_sampling(nwe_ctx *ctx, const float *t_vals, const float *one_minus_t, int n_samples,
                      const float *u, int n_importance);
 
@@ -184,8 +188,11 @@ int nwe_to8b(nwe_ctx *ctx, const float *rgb_dev, uint8_t *out_dev, int64_t n, vo
 int64_t nwe_flops_per_eval(const nwe_ctx *ctx, int which);
 
 /* Time of the most recent RENDER launch on this context (nwe_render / nwe_render_rays / this context's tile of
- * nwe_render_tiled; nwe_create_rays does not count), from HIP events recorded on its stream around the kernel; blocks
- * until that launch has finished.  Returns < 0 if nothing was launched.  Like every entry point it leaves the calling
+ * nwe_render_tiled), from HIP events recorded on its stream around the kernel; blocks until that launch has finished.
+ * nwe_create_rays does not count, however often it is called (it has events of its own), and neither does a call that was
+ * refused, zero rays, or a launch refused after its argument checks ("coarse and fine networks must have the same
+ * shape"): this call and nwe_last_launch_parts then still describe the last launch that was made.  Returns < 0 if nothing
+ * was launched.  Like every entry point it leaves the calling
  * thread's current HIP device as it found it. */
 float nwe_last_kernel_ms(nwe_ctx *ctx);
 
@@ -209,7 +216,11 @@ float nwe_packed_scale(const nwe_ctx *ctx, int which);
 
 /* Test hook: the NEXT nwe_render_rays call takes the fine-pass sample depths from z_dev (DEVICE [n_rays, S],
  * sorted per ray) instead of its own importance sampling; cleared after that call.  Lets a test feed the
- * reference's own depths and compare the fine pass alone. */
+ * reference's own depths and compare the fine pass alone.
+ * This holds for every one-shot hook below and for nwe_set_train_tables: "that call" is the next nwe_render_rays whatever
+ * becomes of it.  A refused call consumes the hooks too (unsupported precision or shape, bad arguments, a wrong
+ * struct_bytes), and so does a call with zero rays: no hook survives into a call whose caller did not set it.  nwe_render
+ * and nwe_render_tiled neither use nor clear the hooks; NULL pointers disarm them. */
 int nwe_debug_set_fine_depths(nwe_ctx *ctx, const float *z_dev);
 
 /* Test hooks in the same style (the NEXT nwe_render_rays call, cleared after it); both kernels honour them:

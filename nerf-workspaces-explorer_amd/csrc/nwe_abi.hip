@@ -54,7 +54,10 @@ struct nwe_ctx {
     };
     static constexpr int kSlots = 4;
     Slot slots[kSlots];
-    int next_slot = 0, last_slot = -1;   // last_slot: the most recent RENDER launch (nwe_last_kernel_ms), not nwe_create_rays
+    Slot rays_slot;                      // nwe_create_rays: a pose table and events of its own, outside the timing ring
+    // next_slot: the slot the next render takes.  last_slot: the most recent render launch that was RECORDED
+    // (nwe_last_kernel_ms); both move only when launch() has succeeded, so a refused launch leaves the timing calls alone.
+    int next_slot = 0, last_slot = -1;
     const float* dbg_z_fine = nullptr;
     const float *dbg_raw_c = nullptr, *dbg_raw_f = nullptr, *dbg_w = nullptr;   // nwe_debug_set_raw / _coarse_weights, one call
     int fold = 1;             // nwe_debug_set_fold: read by nwe_set_network
@@ -313,20 +316,46 @@ __global__ void create_rays_kernel(RenderArgs a, float* __restrict__ out) {
     o[6] = r.near; o[7] = r.far; o[8] = r.vx; o[9] = r.vy; o[10] = r.vz;
 }
 
-// The slot of the next launch: waits for the launch that used it kSlots launches ago (normally long finished).
-int acquire_slot(nwe_ctx* c, nwe_ctx::Slot** out, bool render = true) {
-    nwe_ctx::Slot& s = c->slots[c->next_slot];
+// Makes a slot ready for a new launch: waits for the launch that used it last (for a render slot that was kSlots launches
+// ago, normally long finished).  From here on the slot's events describe no launch until a new one has been recorded.
+int prepare_slot(nwe_ctx* c, nwe_ctx::Slot& s) {
     if (!s.ev0) {
         HIPCHK(c, hipEventCreate(&s.ev0));
         HIPCHK(c, hipEventCreate(&s.ev1));
         HIPCHK(c, hipEventCreate(&s.ev_mid));
     }
     if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
-    if (render) c->last_slot = c->next_slot;
-    c->next_slot = (c->next_slot + 1) % nwe_ctx::kSlots;
-    *out = &s;
+    s.used = false;
+    s.has_mid = false;
     return NWE_OK;
 }
+
+// The slot of the next render launch.  The ring moves on in launch(), once the launch has been recorded.
+int acquire_slot(nwe_ctx* c, nwe_ctx::Slot** out) {
+    *out = &c->slots[c->next_slot];
+    return prepare_slot(c, **out);
+}
+
+// nwe_set_sampling and nwe_set_network change device memory that a queued launch reads (the sampling tables are copied
+// into LDS by every workgroup as it starts, the weights are streamed throughout): wait for this context's own launches,
+// on whatever streams they are.  Costs nothing when nothing is in flight.
+int wait_for_launches(nwe_ctx* c) {
+    for (nwe_ctx::Slot& s : c->slots)
+        if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
+    if (c->rays_slot.used) HIPCHK(c, hipEventSynchronize(c->rays_slot.ev1));
+    return NWE_OK;
+}
+
+// The one-shot hooks of nwe_render_rays (nwe_debug_set_fine_depths / _raw / _coarse_weights, nwe_set_train_tables) are
+// consumed by the call whatever becomes of it: a refused call must not leave them armed for a later one.
+struct HookReset {
+    nwe_ctx* c;
+    ~HookReset() {
+        if (!c) return;
+        c->dbg_z_fine = c->dbg_raw_c = c->dbg_raw_f = c->dbg_w = nullptr;
+        c->trn_t = c->trn_nc = c->trn_nf = c->trn_u = nullptr;
+    }
+};
 
 // Poses into the slot's own table.  hipMemcpyAsync from pageable host memory is staged by the runtime before it returns,
 // so the caller's array is free on return; from pinned memory the copy is truly asynchronous and include/nwe.h asks the
@@ -393,6 +422,8 @@ int launch(nwe_ctx* ctx, nwe_ctx::Slot& slot, RenderArgs& a, int precision, void
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(slot.ev1, stream));
     slot.used = true;
+    ctx->last_slot = (int)(&slot - ctx->slots);
+    ctx->next_slot = (ctx->last_slot + 1) % nwe_ctx::kSlots;
     return NWE_OK;
 }
 
@@ -431,13 +462,15 @@ void nwe_destroy(nwe_ctx* c) {
         if (c->tile_done) (void)hipEventDestroy(c->tile_done);
         if (c->frame_ready) (void)hipEventDestroy(c->frame_ready);
         if (c->tile_stream) (void)hipStreamDestroy(c->tile_stream);
-        for (nwe_ctx::Slot& sl : c->slots) {
+        auto drop = [](nwe_ctx::Slot& sl) {
             if (sl.used) (void)hipEventSynchronize(sl.ev1);
             if (sl.d_poses) (void)hipFree(sl.d_poses);
             if (sl.ev0) (void)hipEventDestroy(sl.ev0);
             if (sl.ev1) (void)hipEventDestroy(sl.ev1);
             if (sl.ev_mid) (void)hipEventDestroy(sl.ev_mid);
-        }
+        };
+        for (nwe_ctx::Slot& sl : c->slots) drop(sl);
+        drop(c->rays_slot);
     }
     delete c;
 }
@@ -465,6 +498,7 @@ static int set_network_impl(nwe_ctx* c, int which, int depth, int width, int in_
     if (!c->host_only) {
         DeviceGuard guard;
         HIPCHK(c, hipSetDevice(c->device));
+        { const int rc = wait_for_launches(c); if (rc) return rc; }   // a queued launch still streams the old weights
         if (n.d_blob) { (void)hipFree(n.d_blob); n.d_blob = nullptr; }
         if (n.d_stream) { (void)hipFree(n.d_stream); n.d_stream = nullptr; }
         if (n.d_bias) { (void)hipFree(n.d_bias); n.d_bias = nullptr; }
@@ -523,6 +557,7 @@ int nwe_set_sampling(nwe_ctx* c, const float* t_vals, const float* one_minus_t, 
         c->d_omt = c->d_t + kMaxSamples;
         c->d_u = c->d_omt + kMaxSamples;
     }
+    { const int rc = wait_for_launches(c); if (rc) return rc; }   // later workgroups of a queued launch still read the old tables
     HIPCHK(c, hipMemcpy(c->d_t, t_vals, n_samples * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_omt, one_minus_t, n_samples * sizeof(float), hipMemcpyHostToDevice));
     if (n_importance > 0) HIPCHK(c, hipMemcpy(c->d_u, u, n_importance * sizeof(float), hipMemcpyHostToDevice));
@@ -674,8 +709,8 @@ int nwe_create_rays(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, flo
         return fail(c, NWE_ERR_INVALID, "bad pose / image / row range");
     DeviceGuard guard;
     HIPCHK(c, hipSetDevice(c->device));
-    nwe_ctx::Slot* slot = nullptr;
-    int rc = acquire_slot(c, &slot, false);
+    nwe_ctx::Slot* slot = &c->rays_slot;   // not a slot of the ring: nwe_last_kernel_ms / _launch_parts keep describing the last render
+    int rc = prepare_slot(c, *slot);
     if (rc) return rc;
     rc = upload_poses(c, *slot, c2w, n_poses, (hipStream_t)stream);
     if (rc) return rc;
@@ -694,14 +729,11 @@ int nwe_create_rays(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, flo
 }
 
 int nwe_render_rays(nwe_ctx* c, const float* rays_dev, int64_t n_rays, int precision, const nwe_outputs* out, void* stream) {
+    HookReset hooks{c};   // every return below, refusals included, consumes the one-shot hooks
     int rc = check_ready(c, out, precision);
     if (rc) return rc;
     if (n_rays < 0 || n_rays > INT32_MAX || (!rays_dev && n_rays > 0)) return fail(c, NWE_ERR_INVALID, "bad rays (null, or more than 2^31 - 1)");
-    if (n_rays == 0) {
-        c->dbg_z_fine = c->dbg_raw_c = c->dbg_raw_f = c->dbg_w = nullptr;
-        c->trn_t = c->trn_nc = c->trn_nf = c->trn_u = nullptr;
-        return NWE_OK;
-    }
+    if (n_rays == 0) return NWE_OK;
     DeviceGuard guard;
     HIPCHK(c, hipSetDevice(c->device));
     nwe_ctx::Slot* slot = nullptr;
@@ -711,9 +743,7 @@ int nwe_render_rays(nwe_ctx* c, const float* rays_dev, int64_t n_rays, int preci
     a.rays = rays_dev; a.n_rays = n_rays; a.W = 1; a.rows = 1;
     a.ray_cols = c->net[0].in_dir == 0 ? 8 : 11;                       // rays.py:22-30: no view-direction columns without view dirs
     a.z_fine_in = c->dbg_z_fine; a.raw_in_c = c->dbg_raw_c; a.raw_in_f = c->dbg_raw_f; a.w_in = c->dbg_w;
-    c->dbg_z_fine = c->dbg_raw_c = c->dbg_raw_f = c->dbg_w = nullptr;
     a.t_rand = c->trn_t; a.noise_c = c->trn_nc; a.noise_f = c->trn_nf; a.u_rand = c->trn_u;
-    c->trn_t = c->trn_nc = c->trn_nf = c->trn_u = nullptr;
     a.out = *out;
     return launch(c, *slot, a, precision, stream);
 }

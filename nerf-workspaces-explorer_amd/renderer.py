@@ -202,39 +202,43 @@ class Renderer:
         if rays.dim() != 2 or rays.shape[1] != self.ray_columns or rays.dtype != torch.float32:
             raise ValueError(f"rays must be float32 [R,{self.ray_columns}] for these networks")
         rays = rays.to(self.device).contiguous()
-        if debug_fine_depths is not None:
-            debug_fine_depths = debug_fine_depths.to(self.device, torch.float32).contiguous()
-            if tuple(debug_fine_depths.shape) != (rays.shape[0], self.n_samples + self.n_importance):
-                raise ValueError("debug_fine_depths must be [R, n_samples + n_importance]")
-            self._lib.nwe_debug_set_fine_depths(self._ctx, debug_fine_depths.data_ptr())
+        # Every hook argument is validated before any hook is armed: a ValueError leaves the context as it was.
         keep = []
         S = self.n_samples + self.n_importance
+        if debug_fine_depths is not None:
+            debug_fine_depths = debug_fine_depths.to(self.device, torch.float32).contiguous()
+            if tuple(debug_fine_depths.shape) != (rays.shape[0], S):
+                raise ValueError("debug_fine_depths must be [R, n_samples + n_importance]")
+        raw_ptrs = None
         if debug_raw is not None:
-            ptrs = []
+            raw_ptrs = []
             for t, n in zip(debug_raw, (self.n_samples, S)):
                 if t is None:
-                    ptrs.append(None)
+                    raw_ptrs.append(None)
                     continue
                 t = t.to(self.device, torch.float32).contiguous()
                 if tuple(t.shape) != (rays.shape[0], n, 4):
                     raise ValueError(f"debug_raw entries must be [R, {n}, 4]")
                 keep.append(t)
-                ptrs.append(t.data_ptr())
-            self._lib.nwe_debug_set_raw(self._ctx, *ptrs)
+                raw_ptrs.append(t.data_ptr())
+        weights = None
         if debug_coarse_weights is not None:
-            t = debug_coarse_weights.to(self.device, torch.float32).contiguous()
-            if tuple(t.shape) != (rays.shape[0], self.n_samples):
+            weights = debug_coarse_weights.to(self.device, torch.float32).contiguous()
+            if tuple(weights.shape) != (rays.shape[0], self.n_samples):
                 raise ValueError("debug_coarse_weights must be [R, n_samples]")
-            keep.append(t)
-            self._lib.nwe_debug_set_coarse_weights(self._ctx, t.data_ptr())
+            keep.append(weights)
+        train_ptrs = None
         if train:
             R, ns, ni = rays.shape[0], self.n_samples, self.n_importance
             shapes = {"t_rand": (R, ns), "noise_coarse": (R, ns), "noise_fine": (R, ns + ni), "u": (R, ni)}
-            ptrs = []
+            unknown = set(train) - set(shapes)
+            if unknown:
+                raise ValueError(f"unknown train keys {sorted(unknown)}")
+            train_ptrs = []
             for key in ("t_rand", "noise_coarse", "noise_fine", "u"):
                 t = train.get(key)
                 if t is None:
-                    ptrs.append(None)
+                    train_ptrs.append(None)
                     continue
                 t = t.to(self.device, torch.float32)
                 if tuple(t.shape) != shapes[key]:
@@ -243,15 +247,24 @@ class Renderer:
                     t = torch.sort(t, dim=-1).values
                 t = t.contiguous()
                 keep.append(t)
-                ptrs.append(t.data_ptr())
-            unknown = set(train) - set(shapes)
-            if unknown:
-                raise ValueError(f"unknown train keys {sorted(unknown)}")
-            self._lib.nwe_set_train_tables(self._ctx, *ptrs)
+                train_ptrs.append(t.data_ptr())
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"unknown precision {precision!r}")
         with torch.cuda.device(self.device):
             o, res = self._alloc(rays.shape[0], outputs)
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            if debug_fine_depths is not None:
+                self._lib.nwe_debug_set_fine_depths(self._ctx, debug_fine_depths.data_ptr())
+            if raw_ptrs is not None:
+                self._lib.nwe_debug_set_raw(self._ctx, *raw_ptrs)
+            if weights is not None:
+                self._lib.nwe_debug_set_coarse_weights(self._ctx, weights.data_ptr())
+            if train_ptrs is not None:
+                self._lib.nwe_set_train_tables(self._ctx, *train_ptrs)
             rc = self._lib.nwe_render_rays(self._ctx, rays.data_ptr(), rays.shape[0], _lib.PRECISIONS[precision], C.byref(o), stream)
+        if rc != _lib.NWE_OK:
+            # a refused call consumes the hooks (include/nwe.h); disarmed here as well, while `keep` still holds the buffers
+            self.disarm_hooks()
         self._check(rc, "nwe_render_rays")
         res["_keepalive_rays"] = rays
         if keep:
@@ -259,6 +272,13 @@ class Renderer:
         if debug_fine_depths is not None:
             res["_keepalive_depths"] = debug_fine_depths
         return res
+
+    def disarm_hooks(self) -> None:
+        """Clears the one-shot hooks of ``render_rays`` (debug depths / raw / coarse weights, train tables)."""
+        self._lib.nwe_debug_set_fine_depths(self._ctx, None)
+        self._lib.nwe_debug_set_raw(self._ctx, None, None)
+        self._lib.nwe_debug_set_coarse_weights(self._ctx, None)
+        self._lib.nwe_set_train_tables(self._ctx, None, None, None, None)
 
     def debug_set_fold(self, on: bool) -> None:
         """Test hook: networks uploaded after this call are packed with (default) / without _feature_linear folded into the

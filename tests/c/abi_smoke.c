@@ -51,6 +51,16 @@ int main(void) {
     CHECK(nwe_render_rays(ctx, NULL, 0, NWE_PREC_F16X3, &out, NULL) == NWE_ERR_STATE);  /* host-only context cannot render */
     out.struct_bytes = sizeof out - sizeof(void *);
     CHECK(nwe_render_rays(ctx, NULL, 0, NWE_PREC_F16X3, &out, NULL) == NWE_ERR_INVALID); /* an older header's layout */
+    /* the one-shot hooks are consumed by every nwe_render_rays, refused ones included; a NULL context has none to consume */
+    {
+        static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
+        CHECK(nwe_debug_set_fine_depths(ctx, dummy) == NWE_OK && nwe_debug_set_raw(ctx, dummy, dummy) == NWE_OK);
+        CHECK(nwe_debug_set_coarse_weights(ctx, dummy) == NWE_OK && nwe_set_train_tables(ctx, dummy, dummy, dummy, dummy) == NWE_OK);
+        out.struct_bytes = sizeof out;
+        CHECK(nwe_render_rays(ctx, dummy, 1, NWE_PREC_F16X3, &out, NULL) == NWE_ERR_STATE);
+        CHECK(nwe_render_rays(NULL, dummy, 1, NWE_PREC_F16X3, &out, NULL) == NWE_ERR_INVALID);
+        CHECK(nwe_create_rays(ctx, dummy, 1, 1, 1, 1.f, 1.f, 0.f, 0.f, 0.1f, 10.f, 0, 1, NULL, NULL) == NWE_ERR_STATE);
+    }
     CHECK(nwe_render_tiled(NULL, 0, NULL, 0, 0, 0, 1, 1, 0, 0, 0.1f, 10.f, 0, NULL, NULL, NULL, NULL, NULL) == NWE_ERR_INVALID);
     CHECK(nwe_debug_last_plan(ctx) == -1 && nwe_last_kernel_ms(ctx) < 0.f);
     CHECK(strlen(nwe_last_warning(ctx)) == 0 && nwe_debug_peer_access(ctx, ctx) == -1);   /* host-only contexts have no device */

@@ -261,3 +261,15 @@ def test_m0_checker_rules():
     assert check_m0.analyse(body, addrs) == (1, 4)
     with pytest.raises(AssertionError):
         check_m0.analyse(W + [P(), P(1024), M, P(3072)], [0, 4, 8, 16, 24, 32])
+
+
+def test_sequence_walk_covers_every_operation_twice():
+    """tests/test_gpu_sequences.py walks one context through a seeded list of steps; generated here without rendering: the list
+    is long enough, deterministic, and holds every operation class, every (precision, lean | full) pair and every refusal at
+    least twice, so the walk cannot thin out unnoticed."""
+    from tests import test_gpu_sequences as S
+    steps, cover = S.make_walk()
+    assert len(steps) >= 60 and steps == S.make_walk()[0]
+    assert not S.walk_coverage_gaps(cover), S.walk_coverage_gaps(cover)
+    assert {s[3] for s in steps if s[0] in ("render", "render_rays")} == {0, 1}
+    assert all(h * w % 128 for h, w in S.FRAMES) and min(h * w for h, w in S.FRAMES) < 32
