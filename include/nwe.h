@@ -46,7 +46,23 @@ enum {
  * fp16 range (NWE_PREC_F16X3 / F16X1): hidden activations are split into fp16 hi + lo, so an activation of 65520 or more (hi =
  * inf) cannot be represented.  The MFMA kernels keep the resulting NaN through their ReLUs and the compositing's relu(sigma), so
  * such a call raises NWE_FLAG_RAW (when raw outputs are requested) and the rgb / depth / acc bits instead of returning finite,
- * wrong values.  NWE_PREC_F32 has no such limit. */
+ * wrong values.  NWE_PREC_F32 has no such limit.
+ * Non-finite and degenerate inputs are defined as in the reference, whose PyTorch code runs on anything: every output's NaN /
+ * inf pattern is the reference's and the bits below report it (tests/input_domain.py lists the cases).  In particular
+ *   - a NaN weight or bias stays NaN through every ReLU of every precision, NWE_PREC_F32 included (torch's relu keeps it);
+ *   - z_std of a ray with NaN or inf importance samples is NaN, as torch.std's, and raises NWE_FLAG_ZSTD; sample_cond /
+ *     sample_amp / sample_switch keep a NaN the way torch's min / max do; with finite coarse depths NaN samples are the last
+ *     entries of z_fine, behind every depth, as torch.sort leaves them (with NaN or inf coarse depths - far = inf, NaN bounds -
+ *     every entry is non-finite as in the reference, in an order that is not specified);
+ *   - coordinate range of the positional encoding (NWE_PREC_F16X3 / F16X1): gamma(x) is guaranteed for |x / 10| * 32 < 1.6e6,
+ *     i.e. point coordinates below 5e5 (nwe_selftest report[7]).  Beyond that, and for inf or NaN, the encoding is NaN - never
+ *     a finite wrong value - and so are the raw outputs and rgb / depth / acc of the ray, with their bits; the identity inputs
+ *     x / 10 are split into fp16 hi + lo and end at 65520 in the same way.  NWE_PREC_F32 (sinf / cosf) is defined for every
+ *     finite coordinate.
+ * near <= far: nwe_render, nwe_create_rays and nwe_render_tiled refuse far < near with NWE_ERR_INVALID (near == far, inf and
+ * NaN bounds are rendered as the reference renders them).  For nwe_render_rays near <= far on every ray is a PRECONDITION: the
+ * fine pass merges the coarse depths with the importance samples as two ascending lists where the reference sorts their
+ * union, so with far < near its sample order - and every fine output - differs from the reference's. */
 enum {
     NWE_FLAG_RGB = 1u << 0, NWE_FLAG_DEPTH = 1u << 1, NWE_FLAG_ACC = 1u << 2, NWE_FLAG_DISP = 1u << 3,
     NWE_FLAG_RGB_COARSE = 1u << 4, NWE_FLAG_DEPTH_COARSE = 1u << 5, NWE_FLAG_ACC_COARSE = 1u << 6,
@@ -176,6 +192,7 @@ int nwe_create_rays(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, f
 
 /* Render precomputed rays: DEVICE [n_rays,11] fp32 = [o(3) d(3) near far viewdir(3)] (rays.py:26-30); [n_rays,8] without the
  * view directions when the context's networks were set with nwe_set_network_no_view_dirs.
+ * Precondition: near <= far on every ray (see "near <= far" above).
  * Replaces: NeRFReplicaInferenceHandler._render_rays(flat_rays) (handler.py:187-201). */
 int nwe_render_rays(nwe_ctx *ctx, const float *rays_dev, int64_t n_rays, int precision, const nwe_outputs *out,
                     void *stream);
@@ -273,7 +290,9 @@ int nwe_debug_set_stamps(nwe_ctx *ctx, unsigned long long *per_wave_dev);
 
 /* Device self-test of the hardware assumptions the MFMA kernel relies on (fragment layouts of
  * v_mfma_f32_32x32x16_f16, fp16 subnormal operands, LDS-DMA lane order).  report[0..7] receives
- * mismatch counts / measured values; returns NWE_OK when every assumption holds. */
+ * mismatch counts / measured values (report[4] / report[7]: the positional encoding's error against fp64 over scene-sized
+ * arguments / over its whole documented range, in 1e-9; report[7] = -1 if an argument beyond the range gave a finite value);
+ * returns NWE_OK when every assumption holds. */
 int nwe_selftest(nwe_ctx *ctx, int32_t *report8);
 
 #ifdef __cplusplus

@@ -271,7 +271,7 @@ struct FineSampler {
     __device__ __forceinline__ float sample(const Ray& r, int j, int& p, SampleSurvey* sv) const {
         const int ncdf = ns - 1;
         const float u = u_rand ? u_rand[(int64_t)cd.row * ni + j] : u_tab[j];
-        while (p < ncdf && wc[p * stride] <= u) ++p;                         // searchsorted(right=True), :103
+        while (p < ncdf && !(wc[p * stride] > u)) ++p;                       // searchsorted(right=True), :103: torch steps over a NaN entry
         const int below = max(p - 1, 0), above = min(p, ncdf - 1);           // :104-105
         const float cb = wc[below * stride], ca = wc[above * stride];
         const float bb = zmid(r, below), ba = zmid(r, above);
@@ -281,16 +281,17 @@ struct FineSampler {
         const float width = __fsub_rn(ba, bb);
         if (sv) {
             if (above != below) {
-                sv->min_denom = fminf(sv->min_denom, raw_denom);
-                sv->min_switch = fminf(sv->min_switch, fabsf(raw_denom - 1e-5f));
-                sv->max_amp = fmaxf(sv->max_amp, width / denom);
+                // torch's min / max keep a NaN (fminf / fmaxf would drop it)
+                sv->min_denom = __builtin_elementwise_minimum(sv->min_denom, raw_denom);
+                sv->min_switch = __builtin_elementwise_minimum(sv->min_switch, fabsf(raw_denom - 1e-5f));
+                sv->max_amp = __builtin_elementwise_maximum(sv->max_amp, width / denom);
             } else if (ncdf >= 2) {
                 // u at or above the last cdf entry (u = 1.0 against a cdf that ends at 1 - 1 ulp, :103-105): the sample sits on
                 // the last bin edge.  Whether it does is itself a rounding matter - with the last entry one ulp higher the
                 // sample is interpolated in the last bin - so that bin's step counts for the amplification.
                 float dl = __fsub_rn(wc[(ncdf - 1) * stride], wc[(ncdf - 2) * stride]);
                 if (dl < 1e-5f) dl = 1.f;
-                sv->max_amp = fmaxf(sv->max_amp, __fsub_rn(zmid(r, ncdf - 1), zmid(r, ncdf - 2)) / dl);
+                sv->max_amp = __builtin_elementwise_maximum(sv->max_amp, __fsub_rn(zmid(r, ncdf - 1), zmid(r, ncdf - 2)) / dl);
             }
         }
         const float t = __fdiv_rn(__fsub_rn(u, cb), denom);                  // :118
@@ -307,13 +308,14 @@ struct FineSampler {
             s1 += (double)z; s2 += (double)z * (double)z;
         }
         const double m = s1 / ni, v = s2 / ni - m * m;
-        sv.z_std = (float)sqrt(v > 0.0 ? v : 0.0);
+        sv.z_std = (float)sqrt(v < 0.0 ? 0.0 : v);   // a NaN variance (NaN or inf samples) stays NaN, as in torch.std
         return sv;
     }
     __device__ __forceinline__ float next(const Ray& r) {
         const float a = ci < ns ? zc(r, ci) : INFINITY;
         const float f = fj < ni ? cur_f : INFINITY;
-        if (!(fj < ni) || a <= f) { ++ci; return a; }
+        // torch.sort puts NaN samples behind every depth: a NaN sample waits while coarse depths are left, then is emitted itself
+        if (!(fj < ni) || a <= f || (f != f && ci < ns)) { ++ci; return a; }
         ++fj;
         if (fj < ni) cur_f = sample(r, fj, ptr, nullptr);
         return f;
@@ -322,7 +324,7 @@ struct FineSampler {
 
 // sin and cos of a * 2^b for b = 0..NB-1, a = v * first (first a power of two, so a is exact): the NB octaves of one
 // positional-encoding coordinate (nerf/models/embedding.py:36 evaluates sin/cos of the fp32 product x * 2^b, which is exact).
-// One fp64 evaluation at the lowest octave - two-constant Cody-Waite reduction by pi/2 (exact for |a| < 1.6e6), the
+// One fp64 evaluation at the lowest octave - two-constant Cody-Waite reduction by pi/2 (exact for |a| < 1.6e6; NaN beyond), the
 // classic degree-13/12 minimax kernels on [-pi/4, pi/4] (error < 2^-57) - then double-angle steps in fp64, whose error
 // doubles per octave and stays below 1e-13 after nine of them; every result is rounded to fp32 once.  This replaces
 // 2*NB libm calls per coordinate (each with its own range reduction) and is at least as close to the reference's libm
@@ -348,11 +350,16 @@ __device__ __forceinline__ void octave_sincos(float v, float first, float* sn, f
     pc = __builtin_fma(pc, z, -1.38888888888741095749e-03);
     pc = __builtin_fma(pc, z, 4.16666666666666019037e-02);
     const double cos_r = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
-    const int q = (int)n & 3;                     // a = r + n*pi/2
+    // Beyond |a| < 1.6e6 the routine is not guaranteed (and n may not fit an int): such an argument gives NaN in every octave,
+    // which reaches the outputs and their NWE_FLAG_* bits, never a finite wrong value.  inf and NaN arrive here as NaN
+    // already (r = inf - inf).
+    const bool in_range = __builtin_fabs(a) < 1.6e6;
+    const int q = (int)(in_range ? n : 0.0) & 3;  // a = r + n*pi/2
     double s = (q & 1) ? cos_r : sin_r;
     double c = (q & 1) ? sin_r : cos_r;
     if (q & 2) s = -s;
     if ((q + 1) & 2) c = -c;
+    if (!in_range) s = c = __builtin_nan("");
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         sn[b] = (float)s;

@@ -52,7 +52,10 @@ __device__ __forceinline__ void dense16(const float* __restrict__ blob, const La
 #pragma unroll
         for (int q = 0; q < kRP / 4; ++q) {
             float4 v = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
-            if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            if (relu) {   // a NaN stays NaN as in torch's relu (fmaxf would make it 0), like act() of the MFMA kernels
+                v.x = __builtin_elementwise_maximum(v.x, 0.f); v.y = __builtin_elementwise_maximum(v.y, 0.f);
+                v.z = __builtin_elementwise_maximum(v.z, 0.f); v.w = __builtin_elementwise_maximum(v.w, 0.f);
+            }
             o[q] = v;
         }
     }

@@ -7,6 +7,9 @@
 //   report[3]  mismatches of the LDS-DMA (global_load_lds_dwordx4) lane order: LDS[base + 16*lane]
 //   report[4]  max |octave_sincos - fp64 libm| over the positional-encoding arguments (up to 1.1e3 rad), in units of 1e-9
 //   report[5]  max relative error of expf over [-20, 20], in units of 1e-9 (informational)
+//   report[7]  the same as report[4] over the whole argument range the routine is documented for: lowest-octave arguments up to
+//              1.6e6 rad (coordinates |v| <= 5e4 in the upper lane half, top octave 2.56e7 rad), in units of 1e-9; -1 if an
+//              argument beyond the range (or inf / NaN) gave anything but NaN in every octave
 //   report[6]  mismatches of the scalar-base + immediate-offset LDS-DMA form the render kernel uses: the instruction
 //              offset must advance BOTH the global source and the LDS destination
 #include <cmath>
@@ -88,11 +91,20 @@ __global__ void selftest_kernel(float* d1 /*32x32*/, float* d2 /*32x32*/, float*
 
 int run_selftest(int32_t* rep, hipStream_t stream) {
     for (int k = 0; k < 8; ++k) rep[k] = 0;
-    const int n = 4096;
+    const int n = 8192;   // 4096 scene-sized arguments (report[4]), then the wide sweep and the arguments beyond the range (report[7])
     std::vector<float> args(n);
+    const int n_small = 4096, n_wide = 8096;   // then 96 arguments beyond the documented range
+    const float beyond[8] = {5.0001e4f, -5.0001e4f, 1e5f, -3e6f, 1e11f, 3e37f, INFINITY, NAN};
     for (int k = 0; k < n; ++k) {   // gamma(x) coordinates |v| <= 2.2; the kernel evaluates octaves 0..4 (k even) or 5..9 (k odd)
-        const double v = -2.2 + 4.4 * ((k * 2654435761u) % 100003) / 100003.0;
-        args[k] = (float)v;
+        const double f = ((k * 2654435761u) % 100003) / 100003.0;
+        double v = -2.2 + 4.4 * f;
+        if (k >= n_small) {          // |v| up to 5e4 (1.6e6 rad at the lowest octave of the upper half), log-uniform, both signs
+            v = std::pow(10.0, -1.0 + 5.69897 * f) * ((k & 2) ? -1.0 : 1.0);
+            if (std::fabs(v) > 4.9999e4) v = 4.9999e4;
+        }
+        args[k] = k >= n_wide ? beyond[k & 7] : (float)v;
+        // odd k multiply by 32: an argument beyond the range there only; even k of the finite ones stay in range up to 1.6e6
+        if (k >= n_wide && !(k & 1) && std::fabs(args[k]) < 1.6e6f) args[k] = 2e6f;
     }
     std::vector<uint32_t> pat(512);
     for (int k = 0; k < 512; ++k) pat[k] = 0x9e3779b9u * (k + 1);
@@ -132,18 +144,25 @@ int run_selftest(int32_t* rep, hipStream_t stream) {
     rep[2] = hsub == 0.015625f ? 1 : (hsub == 0.f ? 0 : -1);
     for (int k = 0; k < 512; ++k) if (hl[k] != pat[k]) rep[3]++;
     for (int k = 0; k < 512; ++k) if (hl2[k] != pat[k]) rep[6]++;
-    double worst = 0.0, worst_e = 0.0;
+    double worst = 0.0, worst_wide = 0.0, worst_e = 0.0;
+    bool beyond_ok = true;
     for (int k = 0; k < n; ++k) {
         for (int b = 0; b < 5; ++b) {
+            if (k >= n_wide) {       // beyond the documented range: NaN, never a finite value
+                if (!std::isnan(hsc[10 * k + 2 * b]) || !std::isnan(hsc[10 * k + 2 * b + 1])) beyond_ok = false;
+                continue;
+            }
             const double a = (double)(args[k] * (float)(1 << (b + ((k & 1) ? 5 : 0))));   // the fp32 product the reference forms
-            worst = std::fmax(worst, std::fabs((double)hsc[10 * k + 2 * b] - std::sin(a)));
-            worst = std::fmax(worst, std::fabs((double)hsc[10 * k + 2 * b + 1] - std::cos(a)));
+            double& w = k < n_small ? worst : worst_wide;
+            const double es = std::fabs((double)hsc[10 * k + 2 * b] - std::sin(a)), ec = std::fabs((double)hsc[10 * k + 2 * b + 1] - std::cos(a));
+            w = std::fmax(w, (es == es && ec == ec) ? std::fmax(es, ec) : 1.0);   // a NaN inside the range counts as an error of 1
         }
         const double x = (double)(-20.f + 40.f * (float)k / (float)n);
         worst_e = std::fmax(worst_e, std::fabs((double)hex[k] - std::exp(x)) / std::exp(x));
     }
     rep[4] = (int32_t)(worst * 1e9);
     rep[5] = (int32_t)(worst_e * 1e9);
+    rep[7] = beyond_ok ? (int32_t)(worst_wide * 1e9) : -1;
     return (rep[0] == 0 && rep[1] == 0 && rep[3] == 0 && rep[6] == 0) ? 0 : 1;
 }
 

@@ -87,13 +87,25 @@ class Report:
 
 
 def raw_at_depths(rays: torch.Tensor, z: torch.Tensor, state: Dict[str, torch.Tensor], dtype: torch.dtype,
-                  cfg: Optional[O.RenderConfig] = None) -> torch.Tensor:
+                  cfg: Optional[O.RenderConfig] = None, fp32_points: bool = False) -> torch.Tensor:
     """The network of the reference at the points o + d * z of the given fp32 rays [R, 8|11] and depths [R, S] (the points
-    are formed in `dtype`, as the oracle's render loop forms them, handler.py:223,246) -> raw [R, S, 4]."""
+    are formed in `dtype`, as the oracle's render loop forms them, handler.py:223,246) -> raw [R, S, 4].
+    `fp32_points`: the points o + d * z and their division by 10 (embedding.py:48) are formed in fp32 exactly as the reference
+    forms them, and encoding and MLP run in `dtype` on those fp32 values (the view directions are fp32 values already).  With
+    dtype = float64 this is the ground truth for coordinates so large that the rounding of the point dominates everything else:
+    there |fp32 - fp64| of the plain fp64 path measures the point rounding and nothing of the arithmetic under test."""
     cfg = cfg or O.RenderConfig()
-    rays, z = rays.to(dtype), z.to(dtype)
-    pts = rays[:, None, 0:3] + rays[:, None, 3:6] * z[..., None]
     viewdirs = rays[:, -3:] if rays.shape[1] > 8 else None
+    if fp32_points:
+        rays32, z32 = rays.to(torch.float32), z.to(torch.float32)
+        pts = rays32[:, None, 0:3] + rays32[:, None, 3:6] * z32[..., None]            # handler.py:223, fp32
+        # run_network divides by 10 in `dtype`: hand it 10 x (the fp32 quotient), which that division undoes exactly in fp64
+        # (v * 10 is exact in fp64 for an fp32 v, and (v * 10) / 10 rounds back to v: |v * 10 / 10 - v| < ulp64(v) / 2)
+        v = (pts / 10.0).to(dtype)
+        pts = v * 10.0 if dtype == torch.float64 else pts
+    else:
+        rays, z = rays.to(dtype), z.to(dtype)
+        pts = rays[:, None, 0:3] + rays[:, None, 3:6] * z[..., None]
     with torch.no_grad():
         raw = O.run_network(pts, viewdirs, state, cfg.freqs_xyz, cfg.freqs_dir, cfg.net_chunk, dtype=dtype)
     return raw[..., :4]

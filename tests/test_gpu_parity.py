@@ -13,6 +13,7 @@ import torch
 
 import nwe_amd
 from oracle import nerf_oracle as O
+from tests import input_domain
 
 pytestmark = pytest.mark.gpu
 
@@ -61,6 +62,9 @@ def test_selftest_hardware_assumptions(r_c1):
     assert rc == 0
     assert rep[4] < 100, f"octave_sincos error {rep[4]}e-9: the positional encoding must be fp32-rounding accurate in every band"
     assert rep[5] < 500, f"expf relative error {rep[5]}e-9"
+    # the whole documented range (|x / 10| <= 5e4, lowest-octave arguments up to 1.6e6 rad): the reference's own sinf error
+    # there plus one fp32 ulp (tests/test_input_domain_oracle.py derives the bound of tests/input_domain.py); beyond it NaN in every octave (-1 if not)
+    assert 0 <= rep[7] < input_domain.SINCOS_WIDE_BOUND, f"octave_sincos over its documented range: {rep[7]}e-9 (-1: a finite value beyond it)"
 
 
 def test_create_rays_bit_exact(r_c1, golden_dir):
