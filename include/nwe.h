@@ -125,7 +125,13 @@ const char *nwe_last_error(const nwe_ctx *ctx);
  *   skip_layer     i such that gamma(x) is concatenated in front of h AFTER layer i's ReLU
  *                  (nerf_model.py:58-59; 4 for D=8), or -1
  *   w, b           depth+4 pointers each, ordered: _pts_linears[0..depth-1], _views_linears[0],
- *                  _feature_linear, _alpha_linear, _rgb_linear */
+ *                  _feature_linear, _alpha_linear, _rgb_linear
+ * Domain: depth 1..16, even width 2..256, in_xyz = 3 + 6 k <= 93, in_dir = 3 + 6 k <= 63 (NWE_ERR_UNSUPPORTED outside; a
+ * refused call leaves the network set before it in place); a skip_layer that feeds no layer (outside 0..depth-2) is no skip.
+ * The coarse and the fine network SHARE THEIR ENCODINGS, as in the reference, where one Embedding per input serves both
+ * (handler.py:93-103): with n_importance > 0 a render of two networks that differ in in_xyz or in_dir is refused with
+ * NWE_ERR_STATE (the kernels encode a ray's view direction once, for both passes).  Under NWE_PREC_F32 the two may differ in
+ * depth, width and skip (net_depth_fine / net_width_fine, handler.py:42-45,106-119); the MFMA precisions need one shape. */
 int nwe_set_network(nwe_ctx *ctx, int which, int depth, int width, int in_xyz, int in_dir, int skip_layer,
                     const float *const *w, const float *const *b);
 
@@ -143,7 +149,8 @@ int nwe_set_network_no_view_dirs(nwe_ctx *ctx, int which, int depth, int width, 
 /* Sampling tables computed by the host with torch.linspace (its bits are not i/(n-1)):
  *   t_vals[n_samples] = linspace(0,1,Ns) and one_minus_t[n_samples] = 1 - t_vals  (handler.py:216-218)
  *   u[n_importance]   = linspace(0,1,Ni)                                        (nerf/rays/rays.py:95)
- * n_importance may be 0 (coarse only; u may then be NULL).
+ * n_importance may be 0 (coarse only; u may then be NULL).  n_samples 2..128 and n_importance 0..256 (NWE_ERR_UNSUPPORTED
+ * outside); importance samples need n_samples >= 3, since sample_pdf takes weights[..., 1:-1] (NWE_ERR_INVALID).
  * nwe_render is asynchronous, so this call and nwe_set_network[_no_view_dirs] first wait for every launch of this context
  * that is still in flight, on whatever stream, before they touch the device tables and weights those launches read: the
  * caller need not synchronise before reconfiguring.  (nwe_set_white_background and the other host-side switches are copied

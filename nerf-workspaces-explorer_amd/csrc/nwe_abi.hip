@@ -383,6 +383,12 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision) {
         return fail(ctx, NWE_ERR_INVALID, "unknown precision");
     if (ctx->ni > 0 && (ctx->net[0].in_dir == 0) != (ctx->net[1].in_dir == 0))
         return fail(ctx, NWE_ERR_STATE, "coarse and fine networks must both have, or both lack, view directions");
+    // one Embedding serves both networks in the reference (handler.py:93-103) and one gamma(d) per ray both passes here
+    if (ctx->ni > 0 && (ctx->net[0].in_xyz != ctx->net[1].in_xyz || ctx->net[0].in_dir != ctx->net[1].in_dir))
+        return fail(ctx, NWE_ERR_STATE,
+                    "coarse and fine networks must share their encodings: in_xyz " + std::to_string(ctx->net[0].in_xyz) + " / " +
+                        std::to_string(ctx->net[1].in_xyz) + ", in_dir " + std::to_string(ctx->net[0].in_dir) + " / " +
+                        std::to_string(ctx->net[1].in_dir) + " (coarse / fine)");
     if (out->feat_map) {
         if (ctx->ni <= 0 || ctx->net[1].in_dir == 0)
             return fail(ctx, NWE_ERR_INVALID, "feat_map is the fine pass's view-layer output: it needs n_importance > 0 and networks with view directions");

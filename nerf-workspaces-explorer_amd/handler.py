@@ -134,7 +134,8 @@ class NeRFReplicaInferenceHandler:
                 mfma = False                  # the fused MFMA kernel runs both passes with one instantiation
             self._precision = "f16x3" if mfma else "f32"
             if not mfma:
-                print(f"[nwe] network shape {self._renderer.shapes.get(_lib.NET_COARSE)} has no MFMA instantiation: rendering with the "
+                shapes = " / ".join(str(self._renderer.shapes.get(w)) for w in nets)
+                print(f"[nwe] network shape {shapes} has no MFMA instantiation: rendering with the "
                       "fp32 vector-ALU kernel (same results, ~25x slower)")
 
     def _need_renderer(self) -> Renderer:
