@@ -106,7 +106,7 @@ struct DeviceGuard {
     } while (0)
 
 // ---------------------------------------------------------------------------------------------
-// packing for the MFMA kernel.  Must mirror nwe_mfma_kernels.h (encode(), split_tile(), tile_mma()).
+// packing for the MFMA kernel.  Must mirror nwe_mfma_eval.h (encode(), tile_mma()).
 // ---------------------------------------------------------------------------------------------
 
 // Column of gamma(v) (embedding.py:24-48 order: identity(3), then per band sin(3), cos(3)) that lane half h

@@ -35,7 +35,7 @@ struct NetMfma {
     int form;               // Form: which formulation of the network the stream holds
 };
 
-// The three formulations the MFMA kernel is instantiated for (template argument FORM of nwe_mfma_kernels.h).
+// The three formulations the MFMA kernel is instantiated for (template argument FORM of nwe_mfma_kernels.h; the shapes: nwe_mfma_shapes.h).
 enum Form {
     kFormReference = 0,     // every layer of nerf_model.py:45-76 as a tile of the stream (selectable for comparison)
     kFormFolded = 1,        // the product path: _feature_linear multiplied into the view layer at pack time, _alpha_linear a dot product

@@ -1,5 +1,5 @@
-// Dispatch of the MFMA render kernel (templates: nwe_mfma_kernels.h).  The instantiations are compiled in separate
-// translation units (nwe_mfma_inst_*.hip) so that they build in parallel.
+// Launch planning and dispatch of the MFMA render kernel (templates: nwe_mfma_kernels.h).  The instantiations are compiled in
+// separate translation units (nwe_mfma_inst_*.hip, one group of nwe_mfma_shapes.h each) so that they build in parallel.
 #include "nwe_mfma_kernels.h"
 
 namespace nwe {
@@ -8,68 +8,68 @@ namespace nwe {
 template __global__ void render_mfma_kernel<256, 8, 4, true, false, NWE_ONE_KERNEL, true>(RenderArgs, NetMfma, NetMfma);
 }  // namespace nwe
 #else
-// Instantiated shapes: width 128 or 256, even depth 4 / 6 / 8 with the reference's skip connection (after layer 4 where
-// that layer exists and feeds another trunk layer, nerf_model.py:13,58-59; none for depth 4), 63/27-wide encodings.
-// The reference formulation (kFormReference) exists for the two BASELINE shapes only.
+NWE_SHAPES(NWE_EXTERN_SHAPE_LAUNCHER)
+#define NWE_SHAPE_IS(W_, D_, SKIP_, FORM_) (W == W_ && D == D_ && skip == SKIP_ && form == FORM_)
+
 bool mfma_supported(int D, int W, int in_xyz, int in_dir, int skip, int form) {
-    if (in_xyz != 63 || in_dir != (form == kFormNoViewDirs ? 0 : 27) || (W != 128 && W != 256)) return false;
-    const bool shape = (D == 8 && skip == 4) || (D == 6 && skip == 4) || (D == 4 && skip == -1);
-    if (!shape) return false;
-    return form != kFormReference || (D == 8 && W == 256) || (D == 4 && W == 128);
+    if (in_xyz != 63 || in_dir != (form == kFormNoViewDirs ? 0 : 27)) return false;
+#define NWE_OR_SHAPE(W_, D_, SKIP_, FORM_) || NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)
+    return false NWE_SHAPES(NWE_OR_SHAPE);
+#undef NWE_OR_SHAPE
 }
 
 int mfma_max_samples() { return kSplitMaxSamples; }
 
-#define NWE_EXTERN_SHAPE(W_, D_, SKIP_, FORM_) \
-    extern template bool launch_t<W_, D_, SKIP_, FORM_>(const RenderArgs&, const NetMfma&, const NetMfma&, bool, int, hipStream_t, LaunchInfo*)
-NWE_EXTERN_SHAPE(256, 8, 4, kFormFolded);
-#ifndef NWE_ONLY_HEADLINE
-NWE_EXTERN_SHAPE(256, 8, 4, kFormReference);
-NWE_EXTERN_SHAPE(256, 8, 4, kFormNoViewDirs);
-NWE_EXTERN_SHAPE(256, 6, 4, kFormFolded);
-NWE_EXTERN_SHAPE(256, 4, -1, kFormFolded);
-NWE_EXTERN_SHAPE(128, 8, 4, kFormFolded);
-NWE_EXTERN_SHAPE(128, 6, 4, kFormFolded);
-NWE_EXTERN_SHAPE(128, 4, -1, kFormFolded);
-NWE_EXTERN_SHAPE(128, 4, -1, kFormReference);
-NWE_EXTERN_SHAPE(128, 4, -1, kFormNoViewDirs);
-NWE_EXTERN_SHAPE(256, 6, 4, kFormNoViewDirs);
-NWE_EXTERN_SHAPE(256, 4, -1, kFormNoViewDirs);
-NWE_EXTERN_SHAPE(128, 8, 4, kFormNoViewDirs);
-NWE_EXTERN_SHAPE(128, 6, 4, kFormNoViewDirs);
-#endif
-#undef NWE_EXTERN_SHAPE
+// The plan of a call: 0 = all packets, 1 = all sample-split, 2 = hybrid; *full = the rays of the hybrid plan's first launch.
+static int plan_launch(const RenderArgs& a, int decomposition, int64_t* full_out) {
+    // One workgroup per CU at a time, so a launch costs (rounds of workgroups) x (sample iterations per workgroup).  Three
+    // plans, same arithmetic: all packets; all sample-split (finer units, ~6 % overhead: redundant sequential part and
+    // exchange); or the full rounds as packets and the ragged last round sample-split in a second launch behind it.
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (cus <= 0) cus = 256;
+    const int64_t rays_wg = kWaves * kRaysPerWave;
+    const double its = (double)(a.n_samples + (a.n_importance > 0 ? a.n_samples + a.n_importance : 0));
+    const double its_split = 1.06 * (double)((a.n_samples + 3) / 4 + (a.n_importance > 0 ? (a.n_samples + a.n_importance + 3) / 4 : 0));
+    const auto rounds = [&](int64_t rays, int64_t per_wg) { return (double)(((rays + per_wg - 1) / per_wg + cus - 1) / cus); };
+    const int64_t full = (a.n_rays / rays_wg / cus) * cus * rays_wg;            // rays in complete rounds of packet workgroups
+    const double t_packet = rounds(a.n_rays, rays_wg) * its;
+    const double t_split = rounds(a.n_rays, kRaysPerWave) * its_split;
+    const double t_hybrid = full > 0 && full < a.n_rays ? (double)(full / rays_wg / cus) * its + rounds(a.n_rays - full, kRaysPerWave) * its_split : 1e300;
+    // two launches when the model promises at least 0.8 %: the 800x800 frame (19 full rounds + 136 workgroups) is 1.0 % by the
+    // model and measures -0.4 % (368.4 vs 370.0 ms, alternating, tools/plan_ab.py); a second launch costs a few microseconds
+    const double t_single = t_packet <= t_split ? t_packet : t_split;
+    int plan = t_hybrid < 0.992 * t_single ? 2 : (t_packet <= t_split ? 0 : 1);
+    if (decomposition >= 0) plan = decomposition;   // nwe_debug_set_decomposition: tests force one
+    if (a.n_samples > kPacketMaxSamples) plan = 1;  // only the single-packet workgroup has LDS for that many coarse weights
+    *full_out = full;
+    return plan;
+}
 
 bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& nf, bool three_pass, int decomposition, hipStream_t stream,
                         LaunchInfo* info) {
     if (a.n_importance > 0 && (nf.D != nc.D || nf.W != nc.W || nf.skip != nc.skip || nf.form != nc.form)) return false;
     if (a.n_samples > kSplitMaxSamples) return false;
-    const int D = nc.D, W = nc.W, skip = nc.skip;
-    if (nc.form == kFormFolded) {
-        if (D == 8 && W == 256 && skip == 4) return launch_t<256, 8, 4, kFormFolded>(a, nc, nf, three_pass, decomposition, stream, info);
-#ifndef NWE_ONLY_HEADLINE
-        if (D == 4 && W == 128 && skip == -1) return launch_t<128, 4, -1, kFormFolded>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 8 && W == 128 && skip == 4) return launch_t<128, 8, 4, kFormFolded>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 4 && W == 256 && skip == -1) return launch_t<256, 4, -1, kFormFolded>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 6 && W == 256 && skip == 4) return launch_t<256, 6, 4, kFormFolded>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 6 && W == 128 && skip == 4) return launch_t<128, 6, 4, kFormFolded>(a, nc, nf, three_pass, decomposition, stream, info);
-#endif
-        return false;
+    const int D = nc.D, W = nc.W, skip = nc.skip, form = nc.form;
+    decltype(&launch_one<256, 8, 4, kFormFolded>) launch = nullptr;
+    int n_chunks = -1;
+#define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_) \
+    if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) { launch = launch_one<W_, D_, SKIP_, FORM_>; n_chunks = Shape<W_, D_>::n_chunks(FORM_); }
+    NWE_SHAPES(NWE_PICK_SHAPE)
+#undef NWE_PICK_SHAPE
+    if (!launch) return false;
+    if (nc.n_chunks != n_chunks || (a.n_importance > 0 && nf.n_chunks != n_chunks)) return false;   // the kernel copies n_chunks bias rows
+    int64_t full = 0;
+    const int plan = plan_launch(a, decomposition, &full);
+    if (info) { info->plan = plan; info->rays_first = plan == 2 ? full : a.n_rays; info->mid_recorded = false; }
+    if (plan == 2) {
+        launch(a, nc, nf, three_pass, false, 0, full, stream);
+        if (info && info->mid) info->mid_recorded = hipEventRecord(info->mid, stream) == hipSuccess;   // the two launches timed apart
+        launch(a, nc, nf, three_pass, true, full, a.n_rays - full, stream);
+    } else {
+        launch(a, nc, nf, three_pass, plan == 1, 0, a.n_rays, stream);
     }
-#ifndef NWE_ONLY_HEADLINE
-    if (nc.form == kFormNoViewDirs) {
-        if (D == 8 && W == 256 && skip == 4) return launch_t<256, 8, 4, kFormNoViewDirs>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 4 && W == 128 && skip == -1) return launch_t<128, 4, -1, kFormNoViewDirs>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 6 && W == 256 && skip == 4) return launch_t<256, 6, 4, kFormNoViewDirs>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 4 && W == 256 && skip == -1) return launch_t<256, 4, -1, kFormNoViewDirs>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 8 && W == 128 && skip == 4) return launch_t<128, 8, 4, kFormNoViewDirs>(a, nc, nf, three_pass, decomposition, stream, info);
-        if (D == 6 && W == 128 && skip == 4) return launch_t<128, 6, 4, kFormNoViewDirs>(a, nc, nf, three_pass, decomposition, stream, info);
-        return false;
-    }
-    if (D == 8 && W == 256 && skip == 4) return launch_t<256, 8, 4, kFormReference>(a, nc, nf, three_pass, decomposition, stream, info);
-    if (D == 4 && W == 128 && skip == -1) return launch_t<128, 4, -1, kFormReference>(a, nc, nf, three_pass, decomposition, stream, info);
-#endif
-    return false;
+    return true;
 }
 
 }  // namespace nwe

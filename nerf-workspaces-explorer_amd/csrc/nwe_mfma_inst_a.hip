@@ -1,6 +1,6 @@
-// Instantiations of the MFMA render kernel, part a (see nwe_kernel_mfma.hip).
+// Instantiations of the MFMA render kernel, group A of nwe_mfma_shapes.h.
 #include "nwe_mfma_kernels.h"
 
 namespace nwe {
-template bool launch_t<256, 8, 4, kFormFolded>(const RenderArgs&, const NetMfma&, const NetMfma&, bool, int, hipStream_t, LaunchInfo*);
+NWE_SHAPES_A(NWE_SHAPE_LAUNCHER)
 }  // namespace nwe

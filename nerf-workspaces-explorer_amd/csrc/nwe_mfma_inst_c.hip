@@ -1,7 +1,6 @@
-// Instantiations of the MFMA render kernel, part c (see nwe_kernel_mfma.hip).
+// Instantiations of the MFMA render kernel, group C of nwe_mfma_shapes.h.
 #include "nwe_mfma_kernels.h"
 
 namespace nwe {
-template bool launch_t<256, 6, 4, kFormFolded>(const RenderArgs&, const NetMfma&, const NetMfma&, bool, int, hipStream_t, LaunchInfo*);
-template bool launch_t<128, 4, -1, kFormReference>(const RenderArgs&, const NetMfma&, const NetMfma&, bool, int, hipStream_t, LaunchInfo*);
+NWE_SHAPES_C(NWE_SHAPE_LAUNCHER)
 }  // namespace nwe

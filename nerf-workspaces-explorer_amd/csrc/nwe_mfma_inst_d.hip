@@ -1,8 +1,6 @@
-// Instantiations of the MFMA render kernel, part d (see nwe_kernel_mfma.hip).
+// Instantiations of the MFMA render kernel, group D of nwe_mfma_shapes.h.
 #include "nwe_mfma_kernels.h"
 
 namespace nwe {
-template bool launch_t<128, 8, 4, kFormFolded>(const RenderArgs&, const NetMfma&, const NetMfma&, bool, int, hipStream_t, LaunchInfo*);
-template bool launch_t<128, 6, 4, kFormFolded>(const RenderArgs&, const NetMfma&, const NetMfma&, bool, int, hipStream_t, LaunchInfo*);
-template bool launch_t<128, 4, -1, kFormFolded>(const RenderArgs&, const NetMfma&, const NetMfma&, bool, int, hipStream_t, LaunchInfo*);
+NWE_SHAPES_D(NWE_SHAPE_LAUNCHER)
 }  // namespace nwe

@@ -28,7 +28,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 F64 = torch.float64
 F32 = torch.float32
 
-# every (D, W, form) launch_render_mfma dispatches (nwe_kernel_mfma.hip)
+# every (D, W, form) launch_render_mfma dispatches (nwe_mfma_shapes.h)
 FOLDED = [(8, 256), (4, 128), (8, 128), (4, 256), (6, 256), (6, 128)]
 REFERENCE = [(8, 256), (4, 128)]
 NO_VIEW_DIRS = [(8, 256), (4, 128), (6, 256), (4, 256), (8, 128), (6, 128)]

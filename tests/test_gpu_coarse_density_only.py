@@ -1,4 +1,4 @@
-"""Density-only coarse evaluations (csrc/nwe_mfma_kernels.h: mlp_eval, density_only).
+"""Density-only coarse evaluations (csrc/nwe_mfma_eval.h: mlp_eval, density_only).
 
 A lean frame (rgb / depth / acc only) with importance sampling reads nothing of the coarse pass but its weights, which depend
 on sigma alone, so its LEAN kernel ends every coarse evaluation with the trunk and skips the view layer and the rgb head.  Any

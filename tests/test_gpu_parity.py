@@ -578,7 +578,7 @@ def test_frame_hand_off_and_preview():
 
 @pytest.mark.gpu
 def test_work_decompositions_are_bit_identical():
-    """The MFMA kernel has two work decompositions (nwe_mfma_kernels.h: four ray packets per workgroup, or one packet
+    """The MFMA kernel has two work decompositions (nwe_mfma_render.h: four ray packets per workgroup, or one packet
     whose samples are dealt to the four waves); the launcher picks by frame size.  Same arithmetic in the same order:
     every output must agree bit for bit, including ragged ray counts and sample counts that are no multiple of four."""
     cases = [(8, 256, 64, 128, 37, 53), (8, 256, 30, 17, 20, 33), (4, 128, 32, 0, 64, 64), (4, 128, 21, 10, 9, 11)]
@@ -752,8 +752,8 @@ def test_contexts_and_streams_are_independent(r_c1, r_c3):
 def test_hybrid_launch_plan(r_c3):
     """A frame with full rounds of 128-ray workgroups plus a ragged rest (300x200 = 60000 rays on 256 CUs: one round of
     32768 rays as packets, 27232 rays sample-split in a second launch): all three plans give the same bits, and the
-    launcher's automatic choice is the one its cost model (rounds of workgroups x sample iterations, csrc/nwe_mfma_kernels.h:
-    launch_t) prescribes - checked as a plan, not as a timing; the times are printed."""
+    launcher's automatic choice is the one its cost model (rounds of workgroups x sample iterations, csrc/nwe_kernel_mfma.hip:
+    plan_launch) prescribes - checked as a plan, not as a timing; the times are printed."""
     fx, fy, cx, cy = O.intrinsics(200, 300)
     pose = O.camera_pose((0.0, -0.5, -0.77, 0.0, -90.0, 0.0), (0, 0, 0, -30.0, 0.0, 0.0))[0].numpy()
     kw = dict(fx=fx, fy=fy, cx=cx, cy=cy, near=0.1, far=10.0, outputs=("rgb", "depth", "acc", "z_std", "rgb_coarse"))
@@ -771,7 +771,7 @@ def test_hybrid_launch_plan(r_c3):
     print("kernel ms by plan (packets, split, hybrid, auto):", [round(ms[m], 2) for m in (0, 1, 2, -1)])
 
     def model(n_rays, cus=256, ns=64, ni=128):
-        """launch_t's cost model: rounds of workgroups x sample iterations; two launches for a modelled gain of >= 0.8 %."""
+        """plan_launch's cost model: rounds of workgroups x sample iterations; two launches for a modelled gain of >= 0.8 %."""
         rounds = lambda rays, per: -(-(-(-rays // per)) // cus)
         its, its_split = ns + ns + ni, 1.06 * ((ns + 3) // 4 + (ns + ni + 3) // 4)
         full = n_rays // 128 // cus * cus * 128
