@@ -62,7 +62,16 @@ enum {
  * near <= far: nwe_render, nwe_create_rays and nwe_render_tiled refuse far < near with NWE_ERR_INVALID (near == far, inf and
  * NaN bounds are rendered as the reference renders them).  For nwe_render_rays near <= far on every ray is a PRECONDITION: the
  * fine pass merges the coarse depths with the importance samples as two ascending lists where the reference sorts their
- * union, so with far < near its sample order - and every fine output - differs from the reference's. */
+ * union, so with far < near its sample order - and every fine output - differs from the reference's.
+ * Camera domain of nwe_render, nwe_create_rays and nwe_render_tiled: fx, fy, cx and cy are four independent floats.  Any
+ * finite non-zero fx and fy (negative focal lengths mirror the image along their axis), any finite cx and cy (on a pixel,
+ * between pixels, outside the image) and any finite upper 3x4 part of c2w (a rotation or any other linear map, any
+ * translation) give rays that are the reference's bit for bit, zero signs included: x = (w - cx) / fx and y = (h - cy) / fy
+ * are true fp32 divisions, d = R (x, y, 1) is summed left to right without FMA onto torch's +0 accumulator (three products
+ * that are all -0 give +0, not -0).  Row 3 of c2w is ignored, whatever it holds.
+ * fx == 0 or fy == 0 (either sign of zero) is refused by all three with NWE_ERR_INVALID before anything is queued: the
+ * outputs stay untouched and nwe_last_kernel_ms / nwe_last_launch_parts keep describing the previous launch.
+ * (tests/camera_domain.py lists the cases.) */
 enum {
     NWE_FLAG_RGB = 1u << 0, NWE_FLAG_DEPTH = 1u << 1, NWE_FLAG_ACC = 1u << 2, NWE_FLAG_DISP = 1u << 3,
     NWE_FLAG_RGB_COARSE = 1u << 4, NWE_FLAG_DEPTH_COARSE = 1u << 5, NWE_FLAG_ACC_COARSE = 1u << 6,

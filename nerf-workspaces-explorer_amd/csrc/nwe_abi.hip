@@ -603,6 +603,7 @@ int nwe_render_tiled(nwe_ctx* const* ctxs, int n_ctx, const float* c2w, int n_po
     for (int i = 0; i < n_ctx; ++i)
         if (!ctxs[i] || ctxs[i]->host_only) return fail(c0, NWE_ERR_INVALID, "nwe_render_tiled: null or host-only context");
     if (!c2w || n_poses < 1 || H < 1 || W < 1) return fail(c0, NWE_ERR_INVALID, "bad pose / image");
+    if (!(fx != 0.f) || !(fy != 0.f)) return fail(c0, NWE_ERR_INVALID, "fx and fy must be non-zero");
     if (far < near) return fail(c0, NWE_ERR_INVALID, "far < near: the sorted merge of the fine pass needs ascending depths");
     hipStream_t stream0 = (hipStream_t)stream_;
     DeviceGuard guard;
@@ -715,6 +716,7 @@ int nwe_create_rays(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, flo
     if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
     if (!c2w || !rays_out_dev || n_poses < 1 || H < 1 || W < 1 || row_begin < 0 || row_end > H || row_begin > row_end)
         return fail(c, NWE_ERR_INVALID, "bad pose / image / row range");
+    if (!(fx != 0.f) || !(fy != 0.f)) return fail(c, NWE_ERR_INVALID, "fx and fy must be non-zero");
     if (far < near) return fail(c, NWE_ERR_INVALID, "far < near: nwe_render_rays needs near <= far on every ray");
     DeviceGuard guard;
     HIPCHK(c, hipSetDevice(c->device));

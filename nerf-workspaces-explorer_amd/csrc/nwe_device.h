@@ -92,10 +92,12 @@ __device__ __forceinline__ Ray make_ray(const RenderArgs& a, const RaySeed& s) {
         if (VIEW && a.ray_cols > 8) { r.vx = p[8]; r.vy = p[9]; r.vz = p[10]; }
     } else {
         const float* m = a.poses + s.pose * 16;
-        // rays.py:67: 3x3 @ 3x1 as torch's CPU bmm does it: products summed left to right, no FMA
-        r.dx = __fadd_rn(__fadd_rn(__fmul_rn(m[0], s.x), __fmul_rn(m[1], s.y)), m[2]);
-        r.dy = __fadd_rn(__fadd_rn(__fmul_rn(m[4], s.x), __fmul_rn(m[5], s.y)), m[6]);
-        r.dz = __fadd_rn(__fadd_rn(__fmul_rn(m[8], s.x), __fmul_rn(m[9], s.y)), m[10]);
+        // rays.py:67: 3x3 @ 3x1 as torch's CPU bmm does it: products summed left to right, no FMA, onto an accumulator that
+        // starts at +0.  The start shows where all three products are -0 (axis-aligned poses with zero entries): their sum
+        // is -0, the reference's +0; x + 0.f changes no other value and is added last here (tests/camera_domain.py).
+        r.dx = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[0], s.x), __fmul_rn(m[1], s.y)), m[2]), 0.f);
+        r.dy = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[4], s.x), __fmul_rn(m[5], s.y)), m[6]), 0.f);
+        r.dz = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[8], s.x), __fmul_rn(m[9], s.y)), m[10]), 0.f);
         r.ox = m[3]; r.oy = m[7]; r.oz = m[11];          // rays.py:68
         r.near = a.near; r.far = a.far;                  // rays.py:26
         if (VIEW) {

@@ -455,6 +455,28 @@ def main() -> None:
     f64["e2e_raw_fine_first8"] = ref["raw_fine"][:8].numpy()
     net_c.float(), net_f.float()
     np.savez_compressed(os.path.join(GOLD, "f64.npz"), **f64)
+
+    # (12) the camera domain ----------------------------------------------------------------------------------
+    # nerf/rays/rays.py's create_rays on every case of tests/camera_domain.py, whole frames, with and without view directions.
+    # The 8-column rays are the first 8 of the 11 (rays.py:27-30), so one array per case is recorded; the hybrid case is sized
+    # from the CU count at test time and is compared against the oracle alone.
+    print("[12] camera domain")
+    from tests import camera_domain as CD                                                              # noqa: E402
+    cams = {}
+    for c in CD.CASES:
+        pose = torch.from_numpy(c.poses)
+        ref11 = ref_create_rays(c.n_poses, pose, c.H, c.W, c.fx, c.fy, c.cx, c.cy, c.near, c.far, True)
+        ref8 = ref_create_rays(c.n_poses, pose, c.H, c.W, c.fx, c.fy, c.cx, c.cy, c.near, c.far, False)
+        assert ref11.shape == (c.n_poses, c.H * c.W, 11) and ref8.shape == (c.n_poses, c.H * c.W, 8) and c.n_rays <= CD.MAX_GOLDEN_RAYS
+        assert CD.same_bits(ref11[..., :8], ref8), c.name
+        assert CD.same_bits(O.create_rays(pose, c.H, c.W, c.fx, c.fy, c.cx, c.cy, c.near, c.far, True), ref11), c.name
+        same(O.create_rays(pose, c.H, c.W, c.fx, c.fy, c.cx, c.cy, c.near, c.far, True), ref11, f"camera {c.name}")
+        same(O.create_rays(pose, c.H, c.W, c.fx, c.fy, c.cx, c.cy, c.near, c.far, False), ref8, f"camera {c.name}, 8 columns")
+        cams[f"rays_{c.name}"] = ref11.numpy()
+        cams[f"pose_{c.name}"] = c.poses
+        cams[f"camera_{c.name}"] = np.array([c.H, c.W, c.fx, c.fy, c.cx, c.cy, c.near, c.far], dtype=np.float64)
+    cams["eight_columns_are_the_first_eight"] = np.array(True)
+    np.savez_compressed(os.path.join(GOLD, "cameras.npz"), **cams)
     print("goldens written to", GOLD)
 
 
