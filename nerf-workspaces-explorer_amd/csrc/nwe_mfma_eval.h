@@ -283,7 +283,7 @@ __device__ __forceinline__ void layer(WalkerT& wk, Frags& F, int lane, bool use_
     }
 }
 
-// gamma(x) and gamma(d) slot maps (must match the packer, nwe_abi.hip: gamma_col()):
+// gamma(x) and gamma(d) slot maps (must match the packer, nwe_pack.cpp: gamma_col()):
 //   lane half h computes bands [NB*h, NB*h + NB) for the three coordinates; slot q = 2*pair + {0: sin, 1: cos},
 //   pair = band_local*3 + coord; after the 6*NB sin/cos slots: identity slots (h=0: x, y; h=1: z, pad).
 template <int NB, int NK, bool X3>
@@ -371,7 +371,7 @@ constexpr bool density_only_built(int form) {
 // every tile's epilogue is deferred into the next tile (see Pend).
 //
 // FOLD (the product path): _feature_linear has no activation (nerf_model.py:64) and feeds only the view layer (:66-70), so
-// the packer multiplies it into the view layer's weights (nwe_abi.hip: pack_mfma): trunk layers 1..D-1 = D/2 - 1 pairs and
+// the packer multiplies it into the view layer's weights (nwe_pack.cpp: pack_mfma): trunk layers 1..D-1 = D/2 - 1 pairs and
 // one single layer A->B, then _alpha_linear and the folded view layer both read B = h, the rgb head reads the view layer's
 // output in A.  !FOLD evaluates the feature layer as the reference formulates it (D/2 pairs, the last pair's second layer
 // is the feature layer without ReLU; alpha reads B, the view layer A); kept selectable for comparison.

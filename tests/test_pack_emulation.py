@@ -1,6 +1,6 @@
 """The MFMA weight stream produced by the C ABI, replayed on the CPU with the documented MFMA lane maps
 (tests/mfma_emulator.py) and compared with the oracle's MLP.  Catches any mismatch between the packer
-(nwe_abi.hip) and the kernel's consumption order without a GPU."""
+(nwe_pack.cpp) and the kernel's consumption order without a GPU."""
 import numpy as np
 import pytest
 import torch
