@@ -277,6 +277,37 @@ int nwe_debug_set_fold(nwe_ctx *ctx, int on);
  * (coarse and fine) is rgb + (1 - acc).  Off by default, as in all four office configs. */
 int nwe_set_white_background(nwe_ctx *ctx, int on);
 
+/* Early ray termination, opt-in: min_transmittance = eps, 0 <= eps < 1; 0 (the default) is off and changes nothing.  NaN,
+ * a negative value or eps >= 1 is NWE_ERR_INVALID and the previous value stays.  Host-side like nwe_set_white_background:
+ * copied at launch, works on a host-only context; nwe_get_early_termination returns the value (-1 for a NULL context).
+ * The rule is per ray: the outputs of a ray do not depend on which rays share its workgroup.  In the TERMINATED PASS - the
+ * pass that produces the frame's outputs: the fine pass when n_importance > 0, the only pass otherwise - sample i of a ray
+ * contributes nothing (w_i = 0) when its transmittance T_i is below eps.  T_i is the reference's trans[:, i]
+ * (nerf/models/model_utils.py:79-80), the fp32 value alpha_i is multiplied by; it runs on unmasked.  In reference terms the
+ * result is raw2outputs with weights * (trans >= eps).  Everything else is as without it: the 1e10 last interval,
+ * white_background (rgb + 1 - acc with the masked acc), the flags.  A NaN T_i is not below eps, so a ray with NaN keeps the
+ * reference's NaN pattern.  The coarse pass of a frame with importance sampling is never touched: its weights feed
+ * sample_pdf, which amplifies the smallest change.
+ * Error bound, by construction: on the supported domain (near <= far, so alpha in [0, 1]) T never increases, so a masked ray
+ * stays masked and the dropped weights sum to less than eps: |d rgb| < eps per channel, |d acc| < eps, |d depth| < eps * z_last.
+ * The skip is a pure optimisation under that rule: a workgroup stops evaluating the pass once every ray it owns is masked
+ * (up to one iteration late, nwe_mfma_render.h); a ray masked before its group is done has its later samples evaluated and
+ * ignored.  Results are bit-identical across the work decompositions, the hybrid plan, row tiles, pose batches and the
+ * tiles of nwe_render_tiled, as without it.
+ * Honoured by calls that request nothing but rgb / depth / acc / flags of pinhole views - nwe_render and nwe_render_tiled - in
+ * all three precisions.  With eps > 0 every other call is refused with NWE_ERR_UNSUPPORTED and a message that names the
+ * setting, behind every refusal the call has without it: any further output (per-sample and coarse outputs have no meaning
+ * past a stop), all of nwe_render_rays with or without hooks or training tables, and under the MFMA precisions a network
+ * packed unfolded (nwe_debug_set_fold(0)) or a shape whose terminating kernel was not built (NWE_PREC_F32 renders both). */
+int nwe_set_early_termination(nwe_ctx *ctx, float min_transmittance);
+float nwe_get_early_termination(const nwe_ctx *ctx);
+
+/* Ray evaluations of the most recent render launch of this context (the launch nwe_last_kernel_ms describes, under the same
+ * rules about refused calls; blocks like it): out[0] = executed, counted as the rays of each workgroup times the samples
+ * that workgroup walked, out[1] = the full count n_rays * (n_samples [+ n_samples + n_importance]).  A launch without early
+ * termination reports out[0] == out[1].  Shows the skip without a clock. */
+int nwe_last_ray_evaluations(nwe_ctx *ctx, int64_t *out2);
+
 /* Training-mode forward (nerf/training/nerf_replica_training_handler.py:553-580; forward only): the NEXT
  * nwe_render_rays call uses random numbers drawn by the caller exactly where the reference calls torch.rand /
  * torch.randn, one row per ray of that call (DEVICE pointers, each may be NULL = the inference behaviour); cleared

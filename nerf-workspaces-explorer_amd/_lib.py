@@ -21,7 +21,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_create_rays", "nwe_render_rays", "nwe_to8b", "nwe_flops_per_eval", "nwe_last_kernel_ms", "nwe_packed_bytes",
            "nwe_packed_copy", "nwe_packed_bias_count", "nwe_packed_bias_copy", "nwe_packed_scale",
            "nwe_debug_set_fine_depths", "nwe_debug_set_raw", "nwe_debug_set_coarse_weights", "nwe_debug_set_fold", "nwe_set_train_tables", "nwe_set_white_background", "nwe_debug_set_decomposition", "nwe_debug_last_plan", "nwe_debug_set_stamps", "nwe_selftest",
-           "nwe_last_warning", "nwe_debug_peer_access", "nwe_set_network_no_view_dirs", "nwe_last_launch_parts")
+           "nwe_last_warning", "nwe_debug_peer_access", "nwe_set_network_no_view_dirs", "nwe_last_launch_parts",
+           "nwe_set_early_termination", "nwe_get_early_termination", "nwe_last_ray_evaluations")
 
 
 class Outputs(C.Structure):
@@ -79,6 +80,9 @@ def load() -> C.CDLL:
         "nwe_selftest": (I, [P, C.POINTER(C.c_int32)]),
         "nwe_last_warning": (C.c_char_p, [P]),
         "nwe_debug_peer_access": (I, [P, P]),
+        "nwe_set_early_termination": (I, [P, F]),
+        "nwe_get_early_termination": (F, [P]),
+        "nwe_last_ray_evaluations": (I, [P, C.POINTER(I64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

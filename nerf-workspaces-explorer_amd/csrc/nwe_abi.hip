@@ -60,6 +60,10 @@ struct Slot {
     Event ev0, ev1, ev_mid;   // ev_mid: between the two launches of the hybrid plan
     bool used = false, has_mid = false;
     int64_t rays_first = 0, rays_total = 0;
+    // nwe_last_ray_evaluations: the full count of the launch and, if it terminated rays early, the word its waves added to
+    DevBuf<unsigned long long> evals;
+    bool term = false;
+    int64_t evals_full = 0;
 };
 
 thread_local std::string g_create_error;
@@ -92,6 +96,7 @@ struct nwe_ctx {
     int peer_access = -2;               // this context's device -> contexts[0]'s device: 1 direct, 0 staged, -1 query/enable failed, -2 not asked yet
     std::string warn;                   // nwe_last_warning: what did not fail the call but the caller should know
     int white_bkgd = 0;
+    float min_trans = 0.f;    // nwe_set_early_termination: 0 = off
     int decomposition = -1;   // nwe_debug_set_decomposition
     int last_plan = -1;       // nwe_debug_last_plan
     unsigned long long* stamps = nullptr;   // nwe_debug_set_stamps
@@ -222,7 +227,8 @@ RenderArgs camera_args(const Camera& m, const float* poses_dev) {
     return a;
 }
 
-int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision) {
+// pinhole: nwe_render / a tile of nwe_render_tiled (false: nwe_render_rays).  The refusals of early termination come last.
+int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole) {
     if (!ctx || !out) return fail(ctx, NWE_ERR_INVALID, "null context or outputs");
     if (out->struct_bytes != sizeof(nwe_outputs))
         return fail(ctx, NWE_ERR_INVALID, "nwe_outputs.struct_bytes != sizeof(nwe_outputs): the caller was built against another version of include/nwe.h");
@@ -253,6 +259,26 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision) {
         if (ctx->ns > mfma_max_samples())
             return fail(ctx, NWE_ERR_UNSUPPORTED, "the MFMA kernel supports n_samples <= 128; use NWE_PREC_F32");
     }
+    if (ctx->min_trans > 0.f) {
+        // what a terminated call cannot give has no meaning past a stop: refused by name rather than changed in silence
+        const std::string on = "early termination is on (nwe_set_early_termination, min_transmittance = " + std::to_string(ctx->min_trans) + "): ";
+        const char* off = "; set min_transmittance to 0 for this call";
+        if (!pinhole) return fail(ctx, NWE_ERR_UNSUPPORTED, on + "nwe_render_rays, its hooks and its training tables are not terminated" + off);
+        nwe_outputs rest = *out;
+        rest.struct_bytes = 0; rest.rgb = rest.depth = rest.acc = nullptr; rest.flags = nullptr;
+        const nwe_outputs none = {};
+        if (std::memcmp(&rest, &none, sizeof(none)) != 0)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, on + "only rgb / depth / acc / flags can be requested" + off);
+        if (precision != NWE_PREC_F32) {
+            for (int i = 0; i < (ctx->ni > 0 ? 2 : 1); ++i) {
+                const NetState& n = ctx->net[i];
+                if (mfma_term_supported(n.D, n.W, n.skip, n.form)) continue;
+                return fail(ctx, NWE_ERR_UNSUPPORTED,
+                            on + (n.form == kFormReference ? "a network packed unfolded (nwe_debug_set_fold(0)) has no terminating MFMA kernel"
+                                                           : "no terminating MFMA kernel was built for this network shape") + "; use NWE_PREC_F32" + off);
+            }
+        }
+    }
     return NWE_OK;
 }
 
@@ -265,8 +291,16 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
     a.stamps = ctx->stamps;   // only read by -DNWE_STAMPS builds of the kernel (nwe_debug_set_stamps)
     if (a.n_rays <= 0) return NWE_OK;
     const NetState &nc = ctx->net[0], &nf = ctx->net[ctx->ni > 0 ? 1 : 0];
+    a.min_trans = ctx->min_trans;
+    if (a.min_trans > 0.f) {   // the launch's waves add their ray evaluations to the slot's own word (its last reader: prepare_slot)
+        HIPCHK(ctx, slot.evals.reserve(1));
+        HIPCHK(ctx, hipMemsetAsync(slot.evals.get(), 0, sizeof(unsigned long long), stream));
+        a.evals = slot.evals.get();
+    }
     const int rc = record_launch(ctx, slot, stream, [&]() -> int {
         slot.has_mid = false; slot.rays_first = slot.rays_total = a.n_rays;
+        slot.term = a.min_trans > 0.f;
+        slot.evals_full = a.n_rays * (int64_t)(a.n_samples + (a.n_importance > 0 ? a.n_samples + a.n_importance : 0));
         if (precision == NWE_PREC_F32) {
             launch_render_f32(a, nc.f32, nf.f32, stream);
             return NWE_OK;
@@ -287,7 +321,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
 
 // nwe_render, and one tile of nwe_render_tiled.  Refuses in this order: check_ready, camera, device.
 int render_rows(nwe_ctx* c, const Camera& m, int precision, const nwe_outputs* out, hipStream_t stream) {
-    TRY(check_ready(c, out, precision));
+    TRY(check_ready(c, out, precision, true));
     TRY(check_camera(c, m));
     ON_DEVICE(c);
     Slot& slot = c->slots[c->next_slot];
@@ -585,7 +619,7 @@ int nwe_create_rays(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, flo
 
 int nwe_render_rays(nwe_ctx* c, const float* rays_dev, int64_t n_rays, int precision, const nwe_outputs* out, void* stream) {
     HookReset hooks{c};   // every return below, refusals included, consumes the one-shot hooks
-    TRY(check_ready(c, out, precision));
+    TRY(check_ready(c, out, precision, false));
     if (n_rays < 0 || n_rays > INT32_MAX || (!rays_dev && n_rays > 0)) return fail(c, NWE_ERR_INVALID, "bad rays (null, or more than 2^31 - 1)");
     if (n_rays == 0) return NWE_OK;
     ON_DEVICE(c);
@@ -638,6 +672,22 @@ int nwe_last_launch_parts(nwe_ctx* c, float* ms2, int64_t* rays2) {
     return NWE_OK;
 }
 
+int nwe_last_ray_evaluations(nwe_ctx* c, int64_t* out2) {
+    if (!c || !out2) return NWE_ERR_INVALID;
+    out2[0] = out2[1] = 0;
+    const Slot* s = last_render(c);
+    if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
+    ON_DEVICE(c);
+    HIPCHK(c, hipEventSynchronize(s->ev1));
+    out2[0] = out2[1] = s->evals_full;
+    if (s->term) {
+        unsigned long long ran = 0;
+        HIPCHK(c, hipMemcpy(&ran, s->evals.get(), sizeof(ran), hipMemcpyDeviceToHost));
+        out2[0] = (int64_t)ran;
+    }
+    return NWE_OK;
+}
+
 int64_t nwe_flops_per_eval(const nwe_ctx* c, int which) { const NetState* n = set_net(c, which); return n ? n->flops : 0; }
 int64_t nwe_packed_bytes(const nwe_ctx* c, int which) { const NetState* n = set_net(c, which); return n ? (int64_t)n->p.stream.size() : 0; }
 int64_t nwe_packed_bias_count(const nwe_ctx* c, int which) { const NetState* n = set_net(c, which); return n ? (int64_t)n->p.bias_tab.size() : 0; }
@@ -653,6 +703,13 @@ int nwe_debug_set_fold(nwe_ctx* c, int on) { return set_on(c, [&] { c->fold = on
 int nwe_debug_set_decomposition(nwe_ctx* c, int mode) { return set_on(mode < -1 || mode > 2 ? nullptr : c, [&] { c->decomposition = mode; }); }
 int nwe_debug_set_stamps(nwe_ctx* c, unsigned long long* per_wave_dev) { return set_on(c, [&] { c->stamps = per_wave_dev; }); }
 int nwe_set_white_background(nwe_ctx* c, int on) { return set_on(c, [&] { c->white_bkgd = on ? 1 : 0; }); }
+int nwe_set_early_termination(nwe_ctx* c, float min_transmittance) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!(min_transmittance >= 0.f && min_transmittance < 1.f)) return fail(c, NWE_ERR_INVALID, "min_transmittance must be in [0, 1) (0 = off)");
+    c->min_trans = min_transmittance > 0.f ? min_transmittance : 0.f;
+    return NWE_OK;
+}
+float nwe_get_early_termination(const nwe_ctx* c) { return c ? c->min_trans : -1.f; }
 int nwe_set_train_tables(nwe_ctx* c, const float* t_rand_dev, const float* noise_coarse_dev, const float* noise_fine_dev, const float* u_sorted_dev) {
     return set_on(c, [&] { c->trn_t = t_rand_dev; c->trn_nc = noise_coarse_dev; c->trn_nf = noise_fine_dev; c->trn_u = u_sorted_dev; });
 }

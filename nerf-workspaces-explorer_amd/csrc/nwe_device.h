@@ -46,6 +46,10 @@ struct RenderArgs {
     int n_samples, n_importance;
     unsigned long long* stamps;  // diagnostic builds (-DNWE_STAMPS): per-wave cycle sums, else unused
     nwe_outputs out;
+    // early ray termination (nwe_set_early_termination): read by the terminating instantiations only, which a launch takes
+    // exactly if min_trans > 0.  Behind `out`, so that no other kernel's argument offsets move.
+    float min_trans;             // eps: in the pass that produces the outputs a sample whose transmittance is below it weighs 0
+    unsigned long long* evals;   // ray evaluations executed, summed over the launch's waves (nwe_last_ray_evaluations)
 };
 
 struct Ray {
@@ -172,6 +176,28 @@ struct Composite {
         b = __fadd_rn(b, __fmul_rn(w, ca.z));
         depth = __fadd_rn(depth, __fmul_rn(w, z));                           // :93
         acc = __fadd_rn(acc, w);                                             // :95
+        return w;
+    }
+    // Early ray termination: the same step, but a sample whose transmittance T_i - the (float)t_run that multiplies alpha - is
+    // below eps weighs nothing and leaves the sums as they are (selects, not products: what a masked sample holds, NaN
+    // included, never reaches them, so evaluating it and skipping it give the same bits).  T itself runs on unmasked, as the
+    // reference's `trans`.  eps = 0 is accumulate() bit for bit; a NaN T is not below eps.
+    // T never increases on the supported domain (near <= far, so dist >= 0, sigma >= 0 and alpha = 1 - exp(-sigma dist) in
+    // [0, 1]): the fp32 factor 1 - alpha + 1e-10 is at most 1 (1 + 1e-10 rounds to 1, and below 1 the 1e-10 is under half an
+    // ulp), a double times a factor <= 1 rounds to no more than itself, and the conversion to float is monotone.  So a ray that
+    // is below eps once stays below: `below()` after sample i says that every later sample is masked.
+    __device__ __forceinline__ bool below(float eps) const { return (float)t_run < eps; }
+    __device__ __forceinline__ float accumulate_above(float4 ca, float z, float eps) {
+        const float alpha = ca.w;
+        const float trans = (float)t_run;
+        const bool masked = trans < eps;
+        const float w = masked ? 0.f : __fmul_rn(alpha, trans);
+        t_run *= (double)__fadd_rn(__fsub_rn(1.f, alpha), 1e-10f);
+        r = masked ? r : __fadd_rn(r, __fmul_rn(w, ca.x));
+        g = masked ? g : __fadd_rn(g, __fmul_rn(w, ca.y));
+        b = masked ? b : __fadd_rn(b, __fmul_rn(w, ca.z));
+        depth = masked ? depth : __fadd_rn(depth, __fmul_rn(w, z));
+        acc = masked ? acc : __fadd_rn(acc, w);
         return w;
     }
     // raw = network output for this sample, z = its depth, z_next = next depth (ignored when last).

@@ -8,6 +8,7 @@
 
 namespace nwe {
 
+// a.min_trans > 0 (early ray termination, with a.evals set) takes the terminating instantiation of either kernel
 void launch_render_f32(const RenderArgs& a, const NetF32& nc, const NetF32& nf, hipStream_t stream);
 
 // true if a kernel instantiation exists for this shape (in_dir == 0 exactly for kFormNoViewDirs)
@@ -25,6 +26,9 @@ struct LaunchInfo {
 };
 bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& nf, bool three_pass, int decomposition, hipStream_t stream,
                         LaunchInfo* info);
+
+// true if the shape's terminating kernels (early ray termination) were built: every supported shape but kFormReference
+bool mfma_term_supported(int D, int W, int skip, int form);
 
 int mfma_max_samples();      // n_samples the MFMA kernel's per-wave LDS buffers are sized for
 

@@ -79,6 +79,11 @@ __device__ __forceinline__ void encode16(float* dst, const float* src3 /*[3][16]
     }
 }
 
+// TERM: early ray termination (include/nwe.h, nwe_set_early_termination; the rule and its argument: render_mfma_kernel,
+// nwe_mfma_render.h).  The 16 owners vote at the top of every sample iteration of the pass that produces the outputs, on a
+// barrier of its own that all 256 threads pass, and the workgroup leaves the loop with no lag: min(S, M) iterations for the
+// largest stop index M of its rays.  One atomic per workgroup counts the ray evaluations.
+template <bool TERM>
 __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc, NetF32 nf) {
     __shared__ __attribute__((aligned(16))) float s_gx[96 * kRP];
     __shared__ __attribute__((aligned(16))) float s_gd[64 * kRP];
@@ -131,6 +136,8 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
 #pragma unroll
         for (int p = 0; p < kRP; ++p) facc[p] = 0.f;
         const float* s_feat = s_ha;
+        const bool stops = TERM && (pass == 1 || ni == 0);   // the pass that produces the outputs
+        const float eps = stops ? a.min_trans : 0.f;
         float z_cur = 0.f, z_next = 0.f;
         if (owner) {
             comp.reset();
@@ -144,7 +151,12 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
                 z_cur = a.z_fine_in ? a.z_fine_in[(live ? ridx : a.n_rays - 1) * S] : fs.next(ray);
             }
         }
-        for (int s = 0; s < S; ++s) {
+        int s = 0;
+        for (; s < S; ++s) {
+            if constexpr (TERM) {
+                // uniform: every thread gets the same answer from the one barrier (a thread that owns no ray agrees)
+                if (stops && __syncthreads_and(!live || comp.below(eps))) break;
+            }
             if (owner) {
                 if (s + 1 < S) {
                     if (pass == 0) z_next = fs.cd.z(ray, s + 1);
@@ -189,7 +201,8 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
                 const float rr = s_raw[0 * kRP + tid], rg = s_raw[1 * kRP + tid], rb = s_raw[2 * kRP + tid],
                             rs = s_raw[3 * kRP + tid];
                 const float* nz = pass == 0 ? a.noise_c : a.noise_f;
-                const float w = comp.step(rr, rg, rb, rs, z_cur, z_next, s + 1 == S, ray.dnorm, nz ? nz[rrow * S + s] : 0.f);
+                const float4 shaded = Composite::shade(rr, rg, rb, rs, z_cur, z_next, s + 1 == S, ray.dnorm, nz ? nz[rrow * S + s] : 0.f);
+                const float w = TERM ? comp.accumulate_above(shaded, z_cur, eps) : comp.accumulate(shaded, z_cur);
                 if (pass == 0) s_w[s * kRP + tid] = w;
                 if (want_feat) s_wcur[tid] = w;
                 if (live) {
@@ -216,6 +229,12 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
             // s_pt / s_raw are rewritten only after the next barrier pair; the owners' reads above are
             // ordered before their own writes at the top of the next iteration.
         }
+        if constexpr (TERM) {
+            if (stops && tid == 0) {
+                const int64_t mine = a.n_rays - base < kRP ? a.n_rays - base : kRP;
+                atomicAdd(a.evals, (unsigned long long)mine * (unsigned long long)((ni > 0 ? ns : 0) + s));
+            }
+        }
         if (want_feat && tid < net.W / 2) {
             for (int p = 0; p < kRP; ++p)
                 if (base + p < a.n_rays) a.out.feat_map[(base + p) * (net.W / 2) + tid] = facc[p];
@@ -230,7 +249,8 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
 
 void launch_render_f32(const RenderArgs& a, const NetF32& nc, const NetF32& nf, hipStream_t stream) {
     const int64_t blocks = (a.n_rays + kRP - 1) / kRP;
-    hipLaunchKernelGGL(render_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, nc, nf);
+    if (a.min_trans > 0.f && a.evals) hipLaunchKernelGGL(render_f32_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, a, nc, nf);
+    else hipLaunchKernelGGL(render_f32_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, a, nc, nf);
 }
 
 }  // namespace nwe

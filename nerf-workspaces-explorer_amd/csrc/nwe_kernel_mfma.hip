@@ -9,6 +9,12 @@ template __global__ void render_mfma_kernel<256, 8, 4, true, false, NWE_ONE_KERN
 }  // namespace nwe
 #else
 NWE_SHAPES(NWE_EXTERN_SHAPE_LAUNCHER)
+#ifndef NWE_ONLY_HEADLINE   // diagnostic builds hold no terminating kernels
+NWE_SHAPES(NWE_EXTERN_SHAPE_TERM_LAUNCHER)
+#define NWE_TERM_BUILT(FORM_) term_built(FORM_)
+#else
+#define NWE_TERM_BUILT(FORM_) false
+#endif
 #define NWE_SHAPE_IS(W_, D_, SKIP_, FORM_) (W == W_ && D == D_ && skip == SKIP_ && form == FORM_)
 
 bool mfma_supported(int D, int W, int in_xyz, int in_dir, int skip, int form) {
@@ -16,6 +22,12 @@ bool mfma_supported(int D, int W, int in_xyz, int in_dir, int skip, int form) {
 #define NWE_OR_SHAPE(W_, D_, SKIP_, FORM_) || NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)
     return false NWE_SHAPES(NWE_OR_SHAPE);
 #undef NWE_OR_SHAPE
+}
+
+bool mfma_term_supported(int D, int W, int skip, int form) {
+#define NWE_OR_TERM_SHAPE(W_, D_, SKIP_, FORM_) || (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_) && NWE_TERM_BUILT(FORM_))
+    return false NWE_SHAPES(NWE_OR_TERM_SHAPE);
+#undef NWE_OR_TERM_SHAPE
 }
 
 int mfma_max_samples() { return kSplitMaxSamples; }
@@ -53,8 +65,20 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
     const int D = nc.D, W = nc.W, skip = nc.skip, form = nc.form;
     decltype(&launch_one<256, 8, 4, kFormFolded>) launch = nullptr;
     int n_chunks = -1;
+    // early termination (a.min_trans > 0): the shape's terminating kernels, which exist for lean calls only (nwe_abi.hip refuses
+    // the rest by name before it gets here)
+    const bool term = a.min_trans > 0.f;
+    if (term && (!is_lean(a) || !a.evals || !mfma_term_supported(D, W, skip, form))) return false;
+#ifndef NWE_ONLY_HEADLINE
+#define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_)                                                          \
+    if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {                                                         \
+        launch = term ? launch_one_term<W_, D_, SKIP_, FORM_> : launch_one<W_, D_, SKIP_, FORM_>;     \
+        n_chunks = Shape<W_, D_>::n_chunks(FORM_);                                                    \
+    }
+#else
 #define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_) \
     if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) { launch = launch_one<W_, D_, SKIP_, FORM_>; n_chunks = Shape<W_, D_>::n_chunks(FORM_); }
+#endif
     NWE_SHAPES(NWE_PICK_SHAPE)
 #undef NWE_PICK_SHAPE
     if (!launch) return false;

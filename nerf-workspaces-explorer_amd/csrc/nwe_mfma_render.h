@@ -89,8 +89,34 @@ __device__ __forceinline__ void read_raw(const float* raw_in, int64_t at, float&
         NWE_STAMP(st_mlp += __builtin_amdgcn_s_memtime() - t2;)                                                                    \
     }
 
-template <int W, int D, int SKIP, bool X3, bool SPLIT, int FORM, bool LEAN>
+// TERM: early ray termination (include/nwe.h, nwe_set_early_termination), for the LEAN kernels of the folded and the
+// no-view-dirs formulations.  In the pass that produces the outputs (the fine pass, or the only one) a sample whose
+// transmittance is below a.min_trans weighs nothing (Composite::accumulate_above) - a per-ray rule, whatever the rays around
+// it do - and the workgroup leaves the sample loop once every ray it owns is below: the rest of their samples weigh nothing
+// either (T never increases, nwe_device.h), so the exit changes no bit of any output.  The masked state costs no register: it
+// is (float)comp.t_run < eps.
+// The exit is workgroup-uniform by construction and is taken at the top of a sample iteration only, in front of
+// NWE_PRIME_STREAM, where no LDS-DMA piece is in flight (the tile that ends an evaluation streams nothing behind it) and no
+// barrier is half passed; it adds no barrier:
+//   packets:      at the top of iteration s every wave writes "all my rays are below after sample s - 1" to vote word
+//                 [s & 1][wave] and reads the four words [(s - 1) & 1][*], written at the top of iteration s - 1 and published
+//                 by that iteration's barriers (the first waits for the writer's LDS counter, Walker::sync<false>), which
+//                 every wave has passed.  All four waves read the same four words, so all leave in the same iteration.  Word
+//                 [s & 1][w] is next written at the top of iteration s + 2 (s + 1: the other parity), and the writer
+//                 gets there only through the barriers of iteration s + 1, which the slowest wave reaches behind its read.
+//   sample split: the four waves composite the same 32 rays from the same LDS data, so each wave's own vote is the same
+//                 value; no exchange.  The two barriers that close the pass are reached by every wave, with the last drain
+//                 between them.
+// Lag: ONE iteration in both plans.  With M = the largest stop index of the workgroup's rays (the first sample whose T is below
+// eps; samples 0 .. M - 1 count), the packets plan runs min(S, M + 1) iterations of one sample, the sample-split plan
+// min(ceil(S / 4), ceil(M / 4) + 1) iterations of four: the votes are taken in front of the compositing that the same
+// iteration's first barrier releases.
+// The ray evaluations executed go to *a.evals, one atomic per wave: rays of its own x samples its workgroup walked.
+constexpr int kVoteBytes = 2 * kWaves * 4;
+
+template <int W, int D, int SKIP, bool X3, bool SPLIT, int FORM, bool LEAN, bool TERM = false>
 __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMfma nc, NetMfma nf) {
+    static_assert(!TERM || (LEAN && FORM != kFormReference), "early termination: lean kernels of the product formulations only");
     RenderArgs a = a_in;
     if constexpr (LEAN) {
         a.out.raw_coarse = a.out.raw_fine = a.out.z_fine = a.out.weights_coarse = nullptr;
@@ -101,7 +127,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
     }
     using S = Shape<W, D>;
     using SM = Smem<W, D, SPLIT>;
-    __shared__ __attribute__((aligned(16))) char smem[SM::TOTAL];
+    __shared__ __attribute__((aligned(16))) char smem[SM::TOTAL + (TERM && !SPLIT ? kVoteBytes : 0)];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -126,6 +152,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
     const int64_t ridx64 = a.ray_first + packet * kRaysPerWave + (lane & 31);
     const bool lane_live = ridx64 < a.n_rays && half == 0;    // this lane stores per-sample outputs of its ray
     const bool live = lane_live && (!SPLIT || wave == 0);      // ... and the per-ray results (every wave holds them in SPLIT mode)
+    const bool gone = ridx64 >= a.n_rays;                      // TERM: a lane past the call's rays computes along and has no say
     // One 32-bit row index per lane (the ABI keeps n_rays below 2^31): the ray's own index, or the call's last ray for the
     // lanes of a ragged last packet, which compute along and store nothing.  64-bit only where an offset is formed.
     const int row = (int)(ridx64 < a.n_rays ? ridx64 : a.n_rays - 1);
@@ -191,6 +218,8 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
             continue;
         }
         comp.reset();
+        const bool stops = TERM && (pass == 1 || ni == 0);          // the pass that produces the outputs
+        const float eps = stops ? a.min_trans : 0.f;                // 0: nothing is ever below
         if constexpr (SPLIT) {
             // depths are produced strictly in order: zq[0..3] = this iteration's four samples, zq[4] = the first of the next
             int produced = 0;
@@ -224,7 +253,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                 for (int k = 0; k < 4; ++k) {
                     const int si = 4 * it + k;
                     if (si < Stot) {
-                        const float w = comp.accumulate(x[k * kRaysPerWave], zp[k]);
+                        const float w = TERM ? comp.accumulate_above(x[k * kRaysPerWave], zp[k], eps) : comp.accumulate(x[k * kRaysPerWave], zp[k]);
                         if (pass == 0) {
                             if (wc_writer) fs.wc[si * kRaysPerWave] = w;
                             if (live && a.out.weights_coarse) a.out.weights_coarse[ridx * ns + si] = w;
@@ -232,7 +261,12 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                     }
                 }
             };
+            [[maybe_unused]] int it_end = n_it;   // TERM: the iterations that ran
             for (int it = 0; it < n_it; ++it) {
+                if constexpr (TERM) {
+                    // comp holds the samples of iterations 0 .. it - 2: iteration it - 1 is composited behind this one's barrier
+                    if (stops && it > 0 && __all(gone || comp.below(eps))) { it_end = it; break; }
+                }
                 NWE_STAMP(const unsigned long long t0 = __builtin_amdgcn_s_memtime();)
                 if (!raw_in) NWE_PRIME_STREAM();
                 const Ray ray = fresh_ray();
@@ -273,8 +307,15 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                 NWE_STAMP(st_comp += __builtin_amdgcn_s_memtime() - t3;)
             }
             __syncthreads();
-            drain(n_it - 1);
+            drain(TERM ? it_end - 1 : n_it - 1);   // TERM: the last iteration that ran (it_end >= 1)
             __syncthreads();   // the exchange buffers are free again for the next pass
+            if constexpr (TERM) {
+                if (stops) {
+                    const unsigned long long mine = __popcll(__ballot(lane_live));
+                    const int walked = (ni > 0 ? ns : 0) + (4 * it_end < Stot ? 4 * it_end : Stot);
+                    if (wave == 0 && lane == 0) atomicAdd(a.evals, mine * (unsigned long long)walked);
+                }
+            }
         } else {
             float z_cur, z_next = 0.f;
             {
@@ -289,7 +330,19 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                     z_cur = a.z_fine_in ? a.z_fine_in[rclamp * Stot] : fs.next(ray);
                 }
             }
+            [[maybe_unused]] int s_end = Stot;   // TERM: the iterations that ran
             for (int s = 0; s < Stot; ++s) {
+                if constexpr (TERM) {
+                    if (stops) {
+                        int* vote = reinterpret_cast<int*>(smem + SM::TOTAL);
+                        const int mine = __all(gone || comp.below(eps));
+                        if (lane == 0) vote[(s & 1) * kWaves + wave] = mine;
+                        if (s > 0) {
+                            const int* v = vote + ((s - 1) & 1) * kWaves;
+                            if (__builtin_amdgcn_readfirstlane(v[0] & v[1] & v[2] & v[3])) { s_end = s; break; }
+                        }
+                    }
+                }
                 NWE_STAMP(const unsigned long long t0 = __builtin_amdgcn_s_memtime();)
                 if (!raw_in) NWE_PRIME_STREAM();
                 const Ray ray = fresh_ray();
@@ -304,7 +357,8 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                     NWE_EVAL_POINT(z_cur, );
                 }
                 NWE_STAMP(const unsigned long long t3 = __builtin_amdgcn_s_memtime();)
-                const float w = comp.step(rr, rg, rb, rs, z_cur, z_next, s + 1 == Stot, ray.dnorm, noise ? noise[rclamp * Stot + s] : 0.f);
+                const float4 shaded = Composite::shade(rr, rg, rb, rs, z_cur, z_next, s + 1 == Stot, ray.dnorm, noise ? noise[rclamp * Stot + s] : 0.f);
+                const float w = TERM ? comp.accumulate_above(shaded, z_cur, eps) : comp.accumulate(shaded, z_cur);
                 if (pass == 0) fs.wc[s * kRaysPerWave] = w;
                 if (lane_live) {
                     if (pass == 0 && a.out.weights_coarse) a.out.weights_coarse[ridx * ns + s] = w;
@@ -314,6 +368,12 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                 }
                 z_cur = z_next;
                 NWE_STAMP(st_comp += __builtin_amdgcn_s_memtime() - t3;)
+            }
+            if constexpr (TERM) {
+                if (stops) {
+                    const unsigned long long mine = __popcll(__ballot(lane_live));
+                    if (lane == 0 && mine) atomicAdd(a.evals, mine * (unsigned long long)((ni > 0 ? ns : 0) + s_end));
+                }
             }
         }
         if (live) {
@@ -350,6 +410,28 @@ void launch_one(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_p
         NWE_KERNEL(false, true, true), NWE_KERNEL(false, true, false), NWE_KERNEL(false, false, true), NWE_KERNEL(false, false, false)};
 #undef NWE_KERNEL
     hipLaunchKernelGGL(kernels[(three_pass ? 0 : 4) + (split ? 0 : 2) + (is_lean(a) ? 0 : 1)], dim3(blocks), dim3(256), 0, stream, a, nc, nf);
+}
+
+// Whether a shape has the terminating kernels (TERM): the product formulations do, kFormReference is a comparison path.
+constexpr bool term_built(int form) { return form != kFormReference; }
+
+// The same launch with early termination: the shape's four terminating kernels (three-pass / single-pass, packets / sample
+// split; lean only - the caller has checked is_lean(a), a.min_trans > 0 and a.evals).  Instantiated per shape in files of their
+// own (nwe_mfma_inst_term_*.hip); nothing for a shape that is not term_built.
+template <int W, int D, int SKIP, int FORM>
+void launch_one_term(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_pass, bool split, int64_t ray_first, int64_t rays,
+                     hipStream_t stream) {
+    if constexpr (term_built(FORM)) {
+        if (rays <= 0) return;
+        a.ray_first = ray_first;
+        const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
+        const unsigned blocks = (unsigned)((rays + per_wg - 1) / per_wg);
+#define NWE_KERNEL(X3_, SPLIT_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, true, true>
+        void (*const kernels[4])(RenderArgs, NetMfma, NetMfma) = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true),
+                                                                  NWE_KERNEL(false, false)};
+#undef NWE_KERNEL
+        hipLaunchKernelGGL(kernels[(three_pass ? 0 : 2) + (split ? 0 : 1)], dim3(blocks), dim3(256), 0, stream, a, nc, nf);
+    }
 }
 
 }  // namespace nwe

@@ -24,3 +24,8 @@
 #define NWE_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_) \
     template void launch_one<W_, D_, SKIP_, FORM_>(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);
 #define NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_)
+// The launcher of the shape's four terminating kernels (early ray termination; lean, three-pass / single-pass, packets / sample
+// split), in instantiation files of their own (nwe_mfma_inst_term_*.hip, the same groups).  Empty for kFormReference.
+#define NWE_SHAPE_TERM_LAUNCHER(W_, D_, SKIP_, FORM_) \
+    template void launch_one_term<W_, D_, SKIP_, FORM_>(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);
+#define NWE_EXTERN_SHAPE_TERM_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_TERM_LAUNCHER(W_, D_, SKIP_, FORM_)

@@ -49,8 +49,11 @@ def pinhole_intrinsics(H: int, W: int, hfov_deg: float = 90.0) -> Tuple[float, f
 class NeRFReplicaInferenceHandler:
 
     def __init__(self, office_name: str, ckpt_path: str, device: int = 0, precision: str = "auto",
-                 devices: Optional[Sequence[int]] = None) -> None:
-        """``devices`` (or the environment variable NWE_DEVICES, e.g. "0,1,2,3", for a caller that constructs the handler
+                 devices: Optional[Sequence[int]] = None, early_termination: float = 0.0) -> None:
+        """``early_termination`` (or the environment variable NWE_EARLY_TERMINATION, for the same two-argument callers):
+        the minimum transmittance of Renderer.set_early_termination, applied in initialize_models(); 0 = off.  While it is on,
+        frames (render, render_batch, render_coordinates) are terminated and ``_render_rays`` raises what the ABI says.
+        ``devices`` (or the environment variable NWE_DEVICES, e.g. "0,1,2,3", for a caller that constructs the handler
         with the reference's two arguments, application/workspace.py:28-29): render every frame as row tiles on these
         devices from this one process (renderer.TiledRenderer); a device may be listed more than once."""
         self._office_name = office_name
@@ -59,6 +62,11 @@ class NeRFReplicaInferenceHandler:
         if devices is None and os.environ.get("NWE_DEVICES"):
             devices = [int(d) for d in os.environ["NWE_DEVICES"].split(",") if d.strip() != ""]
         self._devices = list(devices) if devices else None
+        if not early_termination and os.environ.get("NWE_EARLY_TERMINATION"):
+            early_termination = float(os.environ["NWE_EARLY_TERMINATION"])
+        if not 0.0 <= early_termination < 1.0:      # NaN fails too
+            raise ValueError("early_termination (min_transmittance) must be in [0, 1)")
+        self._early_termination = float(early_termination)
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -127,6 +135,7 @@ class NeRFReplicaInferenceHandler:
             self._renderer.set_network(_lib.NET_FINE, fine)
         self._renderer.set_sampling(self._n_samples, self._n_importance)
         self._renderer.set_white_background(self._white_bkgd)                     # handler.py:57,231,253
+        self._renderer.set_early_termination(self._early_termination)
         if self._auto_precision:
             nets = (_lib.NET_COARSE,) + ((_lib.NET_FINE,) if fine is not None else ())
             mfma = all(self._renderer.mfma_supported(w) for w in nets)
@@ -236,6 +245,11 @@ class NeRFReplicaInferenceHandler:
     @property
     def renderer(self) -> Renderer:
         return self._need_renderer()
+
+    @property
+    def early_termination(self) -> float:
+        """The minimum transmittance initialize_models() applies (0 = off)."""
+        return self._early_termination
 
     @property
     def image_size(self) -> Tuple[int, int]:

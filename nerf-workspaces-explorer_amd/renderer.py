@@ -298,6 +298,23 @@ class Renderer:
         """rendering.white_background (model_utils.py:97-98): rgb += 1 - acc on every rgb output."""
         self._check(self._lib.nwe_set_white_background(self._ctx, 1 if on else 0), "nwe_set_white_background")
 
+    def set_early_termination(self, min_transmittance: float) -> None:
+        """Opt-in early ray termination (include/nwe.h): in the pass that produces the outputs a sample whose transmittance is
+        below ``min_transmittance`` weighs nothing, and a workgroup whose rays are all below stops evaluating.  0 = off (the
+        default); |d rgb|, |d acc| < eps and |d depth| < eps * far by construction.  ``render`` honours it for rgb / depth / acc;
+        every other call raises NotImplementedError while it is on."""
+        self._check(self._lib.nwe_set_early_termination(self._ctx, float(min_transmittance)), "nwe_set_early_termination")
+
+    @property
+    def early_termination(self) -> float:
+        return float(self._lib.nwe_get_early_termination(self._ctx))
+
+    def last_ray_evaluations(self) -> Tuple[int, int]:
+        """(executed, full) ray evaluations of the last render launch: equal unless early termination skipped some."""
+        out = (C.c_int64 * 2)()
+        self._check(self._lib.nwe_last_ray_evaluations(self._ctx, out), "nwe_last_ray_evaluations")
+        return int(out[0]), int(out[1])
+
     def to8b(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = rgb.contiguous()
         out = torch.empty(rgb.shape, dtype=torch.uint8, device=rgb.device)
@@ -391,6 +408,10 @@ class TiledRenderer:
     def debug_set_fold(self, on: bool) -> None:
         for p in self.parts:
             p.debug_set_fold(on)
+
+    def set_early_termination(self, min_transmittance: float) -> None:
+        for p in self.parts:
+            p.set_early_termination(min_transmittance)
 
     def render(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
                rows: Optional[Tuple[int, int]] = None, precision: str = "f16x3",
