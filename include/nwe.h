@@ -302,10 +302,46 @@ int nwe_set_white_background(nwe_ctx *ctx, int on);
 int nwe_set_early_termination(nwe_ctx *ctx, float min_transmittance);
 float nwe_get_early_termination(const nwe_ctx *ctx);
 
+/* A coarse pass shared by k x k pixel blocks, opt-in: k = 1..16; 1 (the default) is off and changes nothing.  Anything else is
+ * NWE_ERR_INVALID and the previous value stays.  Host-side like nwe_set_white_background: copied at launch, works on a
+ * host-only context; nwe_get_shared_coarse returns the value (-1 for a NULL context).
+ * Why: a frame that asks for rgb / depth / acc reads nothing of its coarse pass but the weights that feed sample_pdf.  Near and
+ * far are the frame's, so the coarse depths and z_mid are the same for every ray and only the weights differ from ray to ray,
+ * smoothly in the pixel.  With k > 1 one ray per block runs the coarse pass and the block's pixels draw their importance
+ * samples from its weights: 1 - 1/k^2 of the coarse evaluations of an aligned frame go.  It is an approximation.
+ * The rule, for nwe_render / nwe_render_tiled with n_importance > 0:
+ *   - pixel (h, w) of pose p belongs to block (h / k, w / k) of the WHOLE image, not of the rows of the call;
+ *   - the block's representative pixel is (min(k (h / k) + k / 2, H - 1), min(k (w / k) + k / 2, W - 1));
+ *   - ray r takes the coarse weights of its representative ray rep(r) of the same pose: in reference terms
+ *     sample_pdf(z_mid, weights[rep][..., 1:-1], ...) at nerf_replica_inference_handler.py:237, and since z_vals are the
+ *     frame's, z_fine[r] == z_fine_full[rep(r)], the depths an ordinary frame gives the representative;
+ *   - everything behind that is the ray's own: its points, its view direction, the fine network, the compositing.
+ * Blocks sit on the absolute pixel grid, so a pixel's outputs depend on nothing but the frame: row tiles (whose
+ * representatives may lie outside their rows), pose batches, the work decompositions, the hybrid plan and the tiles of
+ * nwe_render_tiled stay bit-identical to one another, as without it.
+ * With n_importance == 0 there is no pass to share and the call renders exactly as with k = 1.
+ * No ray has a coarse pass of its own then, so the coarse flag bits (NWE_FLAG_*_COARSE) are never raised; the representatives'
+ * coarse pass writes nothing but the weights.
+ * A call is two launches on the caller's stream: a producer over the representatives of the blocks its rows touch, which
+ * writes their weights to a table the launch owns, and behind it a consumer over the call's rays.
+ * With k > 1 every other call is refused with NWE_ERR_UNSUPPORTED and a message that names the setting, behind every refusal
+ * the call has without it and whatever n_importance is: any output beyond rgb / depth / acc / flags, all of nwe_render_rays (no
+ * pixel grid), under the MFMA precisions a network packed unfolded (nwe_debug_set_fold(0); NWE_PREC_F32 renders it), and
+ * every call while early termination is on as well (min_transmittance > 0: the combination is not built). */
+int nwe_set_shared_coarse(nwe_ctx *ctx, int k);
+int nwe_get_shared_coarse(const nwe_ctx *ctx);
+
+/* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
+ * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1, or
+ * n_importance == 0).  nwe_last_kernel_ms spans both launches, nwe_last_launch_parts describes the consumer's. */
+int nwe_last_coarse_launch(nwe_ctx *ctx, float *ms, int64_t *rays);
+
 /* Ray evaluations of the most recent render launch of this context (the launch nwe_last_kernel_ms describes, under the same
  * rules about refused calls; blocks like it): out[0] = executed, counted as the rays of each workgroup times the samples
  * that workgroup walked, out[1] = the full count n_rays * (n_samples [+ n_samples + n_importance]).  A launch without early
- * termination reports out[0] == out[1].  Shows the skip without a clock. */
+ * termination reports out[0] == out[1], except under a shared coarse pass (nwe_set_shared_coarse, k > 1 and n_importance > 0),
+ * where out[0] = n_rep * n_samples + n_rays * (n_samples + n_importance) for the n_rep representatives of the call.  Shows the
+ * skip without a clock. */
 int nwe_last_ray_evaluations(nwe_ctx *ctx, int64_t *out2);
 
 /* Training-mode forward (nerf/training/nerf_replica_training_handler.py:553-580; forward only): the NEXT

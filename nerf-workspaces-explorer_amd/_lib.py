@@ -22,7 +22,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_packed_copy", "nwe_packed_bias_count", "nwe_packed_bias_copy", "nwe_packed_scale",
            "nwe_debug_set_fine_depths", "nwe_debug_set_raw", "nwe_debug_set_coarse_weights", "nwe_debug_set_fold", "nwe_set_train_tables", "nwe_set_white_background", "nwe_debug_set_decomposition", "nwe_debug_last_plan", "nwe_debug_set_stamps", "nwe_selftest",
            "nwe_last_warning", "nwe_debug_peer_access", "nwe_set_network_no_view_dirs", "nwe_last_launch_parts",
-           "nwe_set_early_termination", "nwe_get_early_termination", "nwe_last_ray_evaluations")
+           "nwe_set_early_termination", "nwe_get_early_termination", "nwe_last_ray_evaluations",
+           "nwe_set_shared_coarse", "nwe_get_shared_coarse", "nwe_last_coarse_launch")
 
 
 class Outputs(C.Structure):
@@ -83,6 +84,9 @@ def load() -> C.CDLL:
         "nwe_set_early_termination": (I, [P, F]),
         "nwe_get_early_termination": (F, [P]),
         "nwe_last_ray_evaluations": (I, [P, C.POINTER(I64)]),
+        "nwe_set_shared_coarse": (I, [P, I]),
+        "nwe_get_shared_coarse": (I, [P]),
+        "nwe_last_coarse_launch": (I, [P, C.POINTER(F), C.POINTER(I64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

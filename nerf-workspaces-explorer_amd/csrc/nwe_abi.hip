@@ -64,6 +64,13 @@ struct Slot {
     DevBuf<unsigned long long> evals;
     bool term = false;
     int64_t evals_full = 0;
+    // shared coarse pass (nwe_set_shared_coarse): the launch's own weight table [n_samples][n_rep], which the producer launch
+    // fills and the consumer launch behind it reads (last reader: prepare_slot), the event between the two
+    // (nwe_last_coarse_launch), the representatives and the evaluations the two launches ran
+    DevBuf<float> share_w;
+    Event ev_share;
+    bool has_share = false;
+    int64_t share_rays = 0, evals_run = 0;
 };
 
 thread_local std::string g_create_error;
@@ -97,6 +104,7 @@ struct nwe_ctx {
     std::string warn;                   // nwe_last_warning: what did not fail the call but the caller should know
     int white_bkgd = 0;
     float min_trans = 0.f;    // nwe_set_early_termination: 0 = off
+    int share_k = 1;          // nwe_set_shared_coarse: 1 = off
     int decomposition = -1;   // nwe_debug_set_decomposition
     int last_plan = -1;       // nwe_debug_last_plan
     unsigned long long* stamps = nullptr;   // nwe_debug_set_stamps
@@ -156,9 +164,9 @@ __global__ void create_rays_kernel(RenderArgs a, float* __restrict__ out) {
 // ago, normally long finished).  From here on the slot's events describe no launch until a new one has been recorded.
 int prepare_slot(nwe_ctx* c, Slot& s) {
     if (!s.ev0)
-        for (Event* e : {&s.ev0, &s.ev1, &s.ev_mid}) HIPCHK(c, hipEventCreate(&e->h));
+        for (Event* e : {&s.ev0, &s.ev1, &s.ev_mid, &s.ev_share}) HIPCHK(c, hipEventCreate(&e->h));
     if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
-    s.used = s.has_mid = false;
+    s.used = s.has_mid = s.has_share = false;
     return NWE_OK;
 }
 
@@ -227,7 +235,8 @@ RenderArgs camera_args(const Camera& m, const float* poses_dev) {
     return a;
 }
 
-// pinhole: nwe_render / a tile of nwe_render_tiled (false: nwe_render_rays).  The refusals of early termination come last.
+// pinhole: nwe_render / a tile of nwe_render_tiled (false: nwe_render_rays).  The refusals of early termination and of the
+// shared coarse pass come last.
 int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole) {
     if (!ctx || !out) return fail(ctx, NWE_ERR_INVALID, "null context or outputs");
     if (out->struct_bytes != sizeof(nwe_outputs))
@@ -258,6 +267,29 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhol
                         "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
         if (ctx->ns > mfma_max_samples())
             return fail(ctx, NWE_ERR_UNSUPPORTED, "the MFMA kernel supports n_samples <= 128; use NWE_PREC_F32");
+    }
+    const std::string sharing = "the shared coarse pass is on (nwe_set_shared_coarse, k = " + std::to_string(ctx->share_k) + "): ";
+    const char* share_off = "; set shared_coarse to 1 for this call";
+    if (ctx->share_k > 1 && ctx->min_trans > 0.f)
+        return fail(ctx, NWE_ERR_UNSUPPORTED, sharing + "it is not built together with early termination (nwe_set_early_termination, min_transmittance = " +
+                                                  std::to_string(ctx->min_trans) + "); switch one of them off");
+    if (ctx->share_k > 1) {
+        // a block's pixels share one coarse pass: what only a ray's own coarse pass can give is refused by name
+        if (!pinhole) return fail(ctx, NWE_ERR_UNSUPPORTED, sharing + "nwe_render_rays has no pixel grid to share over" + share_off);
+        nwe_outputs rest = *out;
+        rest.struct_bytes = 0; rest.rgb = rest.depth = rest.acc = nullptr; rest.flags = nullptr;
+        const nwe_outputs none = {};
+        if (std::memcmp(&rest, &none, sizeof(none)) != 0)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, sharing + "only rgb / depth / acc / flags can be requested" + share_off);
+        if (precision != NWE_PREC_F32) {
+            for (int i = 0; i < (ctx->ni > 0 ? 2 : 1); ++i) {
+                const NetState& n = ctx->net[i];
+                if (mfma_share_supported(n.D, n.W, n.skip, n.form)) continue;
+                return fail(ctx, NWE_ERR_UNSUPPORTED,
+                            sharing + (n.form == kFormReference ? "a network packed unfolded (nwe_debug_set_fold(0)) has no sharing MFMA kernel"
+                                                                : "no sharing MFMA kernel was built for this network shape") + "; use NWE_PREC_F32" + share_off);
+            }
+        }
     }
     if (ctx->min_trans > 0.f) {
         // what a terminated call cannot give has no meaning past a stop: refused by name rather than changed in silence
@@ -297,10 +329,32 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         HIPCHK(ctx, hipMemsetAsync(slot.evals.get(), 0, sizeof(unsigned long long), stream));
         a.evals = slot.evals.get();
     }
+    // Shared coarse pass: with importance samples the call is two launches, the producer over the representatives of the blocks
+    // its rows touch (check_ready has refused everything but lean pinhole calls), then the consumer over its rays.
+    const bool share = ctx->share_k > 1 && a.n_importance > 0;
+    RenderArgs prod = {};
+    if (share) {
+        a.share = kShareConsumer | ctx->share_k << 8;
+        const int64_t n_rep = share_n_rep(a, share_grid(a));   // at most n_rays
+        HIPCHK(ctx, slot.share_w.reserve((size_t)n_rep * a.n_samples));
+        a.share_w = slot.share_w.get();
+        prod = a;
+        prod.share = kShareProducer | ctx->share_k << 8; prod.n_rays = n_rep; prod.out = {};
+    }
     const int rc = record_launch(ctx, slot, stream, [&]() -> int {
         slot.has_mid = false; slot.rays_first = slot.rays_total = a.n_rays;
         slot.term = a.min_trans > 0.f;
         slot.evals_full = a.n_rays * (int64_t)(a.n_samples + (a.n_importance > 0 ? a.n_samples + a.n_importance : 0));
+        slot.evals_run = share ? prod.n_rays * a.n_samples + a.n_rays * (int64_t)(a.n_samples + a.n_importance) : slot.evals_full;
+        slot.share_rays = share ? prod.n_rays : 0;
+        const char* shapes_differ = "coarse and fine networks must have the same shape for the MFMA kernel";
+        if (share) {
+            if (precision == NWE_PREC_F32) launch_render_f32(prod, nc.f32, nf.f32, stream);
+            else if (!launch_render_mfma(prod, nc.mf, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, nullptr))
+                return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
+            HIPCHK(ctx, hipEventRecord(slot.ev_share, stream));
+            slot.has_share = true;
+        }
         if (precision == NWE_PREC_F32) {
             launch_render_f32(a, nc.f32, nf.f32, stream);
             return NWE_OK;
@@ -308,7 +362,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         LaunchInfo info;
         info.mid = slot.ev_mid;
         if (!launch_render_mfma(a, nc.mf, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info))
-            return fail(ctx, NWE_ERR_UNSUPPORTED, "coarse and fine networks must have the same shape for the MFMA kernel");
+            return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
         ctx->last_plan = info.plan;
         slot.has_mid = info.mid_recorded; slot.rays_first = info.rays_first;
         return NWE_OK;
@@ -663,12 +717,26 @@ int nwe_last_launch_parts(nwe_ctx* c, float* ms2, int64_t* rays2) {
     ON_DEVICE(c);
     HIPCHK(c, hipEventSynchronize(s->ev1));
     rays2[0] = s->rays_first; rays2[1] = s->rays_total - s->rays_first;
+    const hipEvent_t begin = s->has_share ? s->ev_share : s->ev0;   // behind the producer of a shared coarse pass
     if (s->has_mid) {
-        HIPCHK(c, hipEventElapsedTime(&ms2[0], s->ev0, s->ev_mid));
+        HIPCHK(c, hipEventElapsedTime(&ms2[0], begin, s->ev_mid));
         HIPCHK(c, hipEventElapsedTime(&ms2[1], s->ev_mid, s->ev1));
     } else {
-        HIPCHK(c, hipEventElapsedTime(&ms2[0], s->ev0, s->ev1));
+        HIPCHK(c, hipEventElapsedTime(&ms2[0], begin, s->ev1));
     }
+    return NWE_OK;
+}
+
+int nwe_last_coarse_launch(nwe_ctx* c, float* ms, int64_t* rays) {
+    if (!c || !ms || !rays) return NWE_ERR_INVALID;
+    *ms = -1.f; *rays = 0;
+    const Slot* s = last_render(c);
+    if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
+    if (!s->has_share) return NWE_OK;
+    ON_DEVICE(c);
+    HIPCHK(c, hipEventSynchronize(s->ev1));
+    HIPCHK(c, hipEventElapsedTime(ms, s->ev0, s->ev_share));
+    *rays = s->share_rays;
     return NWE_OK;
 }
 
@@ -679,7 +747,7 @@ int nwe_last_ray_evaluations(nwe_ctx* c, int64_t* out2) {
     if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
     ON_DEVICE(c);
     HIPCHK(c, hipEventSynchronize(s->ev1));
-    out2[0] = out2[1] = s->evals_full;
+    out2[0] = s->evals_run; out2[1] = s->evals_full;
     if (s->term) {
         unsigned long long ran = 0;
         HIPCHK(c, hipMemcpy(&ran, s->evals.get(), sizeof(ran), hipMemcpyDeviceToHost));
@@ -710,6 +778,13 @@ int nwe_set_early_termination(nwe_ctx* c, float min_transmittance) {
     return NWE_OK;
 }
 float nwe_get_early_termination(const nwe_ctx* c) { return c ? c->min_trans : -1.f; }
+int nwe_set_shared_coarse(nwe_ctx* c, int k) {
+    if (!c) return NWE_ERR_INVALID;
+    if (k < 1 || k > 16) return fail(c, NWE_ERR_INVALID, "shared_coarse k must be in 1..16 (1 = off)");
+    c->share_k = k;
+    return NWE_OK;
+}
+int nwe_get_shared_coarse(const nwe_ctx* c) { return c ? c->share_k : -1; }
 int nwe_set_train_tables(nwe_ctx* c, const float* t_rand_dev, const float* noise_coarse_dev, const float* noise_fine_dev, const float* u_sorted_dev) {
     return set_on(c, [&] { c->trn_t = t_rand_dev; c->trn_nc = noise_coarse_dev; c->trn_nf = noise_fine_dev; c->trn_u = u_sorted_dev; });
 }

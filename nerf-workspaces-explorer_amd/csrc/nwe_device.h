@@ -49,8 +49,36 @@ struct RenderArgs {
     // early ray termination (nwe_set_early_termination): read by the terminating instantiations only, which a launch takes
     // exactly if min_trans > 0.  Behind `out`, so that no other kernel's argument offsets move.
     float min_trans;             // eps: in the pass that produces the outputs a sample whose transmittance is below it weighs 0
-    unsigned long long* evals;   // ray evaluations executed, summed over the launch's waves (nwe_last_ray_evaluations)
+    // shared coarse pass (nwe_set_shared_coarse): read by the sharing instantiations only, which a launch takes exactly if
+    // share != 0: role | k << 8 (kShareProducer / kShareConsumer, the block edge in pixels).  It sits in the padding in front of
+    // the pointer and the table shares the pointer's slot - the two modes exclude each other - so that the struct does not
+    // grow: the descriptors behind it keep their offsets, and every other kernel its instructions.
+    int share;
+    union {
+        unsigned long long* evals;   // ray evaluations executed, summed over the launch's waves (nwe_last_ray_evaluations)
+        float* share_w;              // coarse weights of the call's representatives, sample-major: [n_samples][n_rep]
+    };
 };
+
+constexpr int kShareOff = 0, kShareProducer = 1, kShareConsumer = 2;
+__host__ __device__ inline int share_role(const RenderArgs& a) { return a.share & 0xff; }
+
+// The blocks a call's rows touch, from the camera fields both launches of a shared call carry: k, the first block row, the
+// block rows, the block columns of the image (ceil(W / k)).  The producer's rays are the blocks' representative pixels:
+// ray (p * nbr + br - br0) * nbc + bc is the representative of block (br, bc) of pose p, and n_rays = n_rep of them.
+struct ShareGrid { int k, br0, nbr, nbc; };
+__host__ __device__ inline ShareGrid share_grid(const RenderArgs& a) {
+    ShareGrid g;
+    g.k = a.share >> 8;
+    g.br0 = a.row_begin / g.k;
+    g.nbr = (a.row_begin + a.rows - 1) / g.k - g.br0 + 1;
+    g.nbc = (a.W + g.k - 1) / g.k;
+    return g;
+}
+// Representatives of the call = the table's row length: the producer's ray count, n_poses * nbr * nbc for the consumer.
+__host__ __device__ inline int share_n_rep(const RenderArgs& a, const ShareGrid& g) {
+    return share_role(a) == kShareProducer ? (int)a.n_rays : (int)(a.n_rays / ((int64_t)a.rows * a.W)) * g.nbr * g.nbc;
+}
 
 struct Ray {
     float ox, oy, oz, dx, dy, dz, near, far, vx, vy, vz, dnorm;
@@ -81,6 +109,47 @@ __device__ __forceinline__ RaySeed seed_ray(const RenderArgs& a, int64_t idx) {
     s.x = __fdiv_rn(__fsub_rn((float)w, a.cx), a.fx);
     s.y = __fdiv_rn(__fsub_rn((float)h, a.cy), a.fy);
     return s;
+}
+
+// Shared coarse pass, producer: idx is the index of a representative (share_grid), its pixel
+// (min(k br + k/2, H-1), min(k bc + k/2, W-1)) of pose *pose.
+__host__ __device__ inline void share_rep_pixel(const RenderArgs& a, int64_t idx, int* pose, int* h, int* w) {
+    const ShareGrid g = share_grid(a);
+    const int per_pose = g.nbr * g.nbc;
+    *pose = (int)(idx / per_pose);
+    const int rem = (int)(idx - (int64_t)*pose * per_pose);
+    const int br = g.br0 + rem / g.nbc, bc = rem % g.nbc;
+    const int rh = br * g.k + g.k / 2, rw = bc * g.k + g.k / 2;
+    *h = rh < a.H - 1 ? rh : a.H - 1;
+    *w = rw < a.W - 1 ? rw : a.W - 1;
+}
+// ... and its ray: the same two divisions as seed_ray on the same pixel, so the same bits.
+__device__ __forceinline__ RaySeed seed_rep_ray(const RenderArgs& a, int64_t idx) {
+    RaySeed s;
+    int h, w;
+    share_rep_pixel(a, idx, &s.pose, &h, &w);
+    s.x = __fdiv_rn(__fsub_rn((float)w, a.cx), a.fx);
+    s.y = __fdiv_rn(__fsub_rn((float)h, a.cy), a.fy);
+    return s;
+}
+
+// The seed of ray idx of a launch, the producer's representatives included: seed_ray for every kernel but the sharing ones.
+template <bool SHARE>
+__device__ __forceinline__ RaySeed seed_of(const RenderArgs& a, int64_t idx) {
+    if constexpr (SHARE) {
+        if (share_role(a) == kShareProducer) return seed_rep_ray(a, idx);
+    }
+    return seed_ray(a, idx);
+}
+
+// Shared coarse pass, consumer: the table column of ray idx of the call = the index of its block's representative.
+__host__ __device__ inline int share_rep_of(const RenderArgs& a, int64_t idx) {
+    const ShareGrid g = share_grid(a);
+    const int per_pose = a.rows * a.W;
+    const int pose = (int)(idx / per_pose);
+    const int rem = (int)(idx - (int64_t)pose * per_pose);
+    const int h = a.row_begin + rem / a.W, w = rem % a.W;
+    return (pose * g.nbr + (h / g.k - g.br0)) * g.nbc + w / g.k;
 }
 
 // nerf/rays/rays.py:6-32, :61-71.  VIEW: also the normalised view direction (rays.py:24), needed once per ray for gamma(d).

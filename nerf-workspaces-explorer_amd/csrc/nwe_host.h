@@ -8,7 +8,8 @@
 
 namespace nwe {
 
-// a.min_trans > 0 (early ray termination, with a.evals set) takes the terminating instantiation of either kernel
+// a.min_trans > 0 (early ray termination, with a.evals set) takes the terminating instantiation of either kernel,
+// a.share != kShareOff (shared coarse pass, with a.share_w set) the sharing one
 void launch_render_f32(const RenderArgs& a, const NetF32& nc, const NetF32& nf, hipStream_t stream);
 
 // true if a kernel instantiation exists for this shape (in_dir == 0 exactly for kFormNoViewDirs)
@@ -29,6 +30,9 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
 
 // true if the shape's terminating kernels (early ray termination) were built: every supported shape but kFormReference
 bool mfma_term_supported(int D, int W, int skip, int form);
+
+// true if the shape's sharing kernels (shared coarse pass) were built: the same shapes
+bool mfma_share_supported(int D, int W, int skip, int form);
 
 int mfma_max_samples();      // n_samples the MFMA kernel's per-wave LDS buffers are sized for
 

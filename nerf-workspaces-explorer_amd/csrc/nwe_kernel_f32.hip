@@ -83,8 +83,12 @@ __device__ __forceinline__ void encode16(float* dst, const float* src3 /*[3][16]
 // nwe_mfma_render.h).  The 16 owners vote at the top of every sample iteration of the pass that produces the outputs, on a
 // barrier of its own that all 256 threads pass, and the workgroup leaves the loop with no lag: min(S, M) iterations for the
 // largest stop index M of its rays.  One atomic per workgroup counts the ray evaluations.
-template <bool TERM>
+// SHARE: the coarse pass shared by k x k pixel blocks (nwe_set_shared_coarse; render_mfma_kernel, nwe_mfma_render.h): the
+// producer launch walks the representative rays through pass 0 and writes their weights to a.share_w, the consumer launch
+// fills s_w from its rays' representatives and runs the fine pass.
+template <bool TERM, bool SHARE = false>
 __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc, NetF32 nf) {
+    static_assert(!(TERM && SHARE), "shared coarse pass: not with early termination");
     __shared__ __attribute__((aligned(16))) float s_gx[96 * kRP];
     __shared__ __attribute__((aligned(16))) float s_gd[64 * kRP];
     __shared__ __attribute__((aligned(16))) float s_ha[256 * kRP];
@@ -105,9 +109,11 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
     for (int i = tid; i < ns; i += 256) { s_t[i] = a.t_vals[i]; s_omt[i] = a.omt_vals[i]; }
     for (int i = tid; i < ni; i += 256) s_u[i] = a.u_vals[i];
 
+    const bool producer = SHARE && share_role(a) == kShareProducer, consumer = SHARE && share_role(a) == kShareConsumer;
     Ray ray = {};
     if (owner) {
-        ray = load_ray(a, live ? ridx : a.n_rays - 1);
+        const int64_t at = live ? ridx : a.n_rays - 1;
+        ray = make_ray<true>(a, seed_of<SHARE>(a, at));
         s_pt[0 * kRP + tid] = ray.vx; s_pt[1 * kRP + tid] = ray.vy; s_pt[2 * kRP + tid] = ray.vz;
     }
     __syncthreads();
@@ -130,6 +136,16 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
         if (pass == 0 && a.w_in) {                                          // test hook: coarse weights from the caller
             if (owner) for (int s = 0; s < ns; ++s) s_w[s * kRP + tid] = a.w_in[rrow * ns + s];
             continue;
+        }
+        if constexpr (SHARE) {
+            if (pass == 0 && consumer) {                                    // the representative's coarse weights
+                if (owner) {
+                    const float* col = a.share_w + share_rep_of(a, rrow);
+                    const int n_rep = share_n_rep(a, share_grid(a));
+                    for (int s = 0; s < ns; ++s) s_w[s * kRP + tid] = col[(int64_t)s * n_rep];
+                }
+                continue;
+            }
         }
         const bool want_feat = pass == 1 && a.out.feat_map != nullptr && !raw_in;   // uniform
         float facc[kRP];
@@ -204,6 +220,7 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
                 const float4 shaded = Composite::shade(rr, rg, rb, rs, z_cur, z_next, s + 1 == S, ray.dnorm, nz ? nz[rrow * S + s] : 0.f);
                 const float w = TERM ? comp.accumulate_above(shaded, z_cur, eps) : comp.accumulate(shaded, z_cur);
                 if (pass == 0) s_w[s * kRP + tid] = w;
+                if constexpr (SHARE) { if (producer && live) a.share_w[s * a.n_rays + ridx] = w; }   // n_rays = n_rep
                 if (want_feat) s_wcur[tid] = w;
                 if (live) {
                     if (pass == 0 && a.out.weights_coarse) a.out.weights_coarse[ridx * S + s] = w;
@@ -239,6 +256,7 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
             for (int p = 0; p < kRP; ++p)
                 if (base + p < a.n_rays) a.out.feat_map[(base + p) * (net.W / 2) + tid] = facc[p];
         }
+        if (producer) break;   // the table is the producer's only result
         if (live) {
             flags |= store_ray(a.out, ridx, comp, pass == 1, a.white_bkgd != 0);
             if (ni == 0) flags |= store_ray(a.out, ridx, comp, true, a.white_bkgd != 0);   // coarse-only: fill the "fine" slots too
@@ -249,7 +267,8 @@ __global__ void __launch_bounds__(256) render_f32_kernel(RenderArgs a, NetF32 nc
 
 void launch_render_f32(const RenderArgs& a, const NetF32& nc, const NetF32& nf, hipStream_t stream) {
     const int64_t blocks = (a.n_rays + kRP - 1) / kRP;
-    if (a.min_trans > 0.f && a.evals) hipLaunchKernelGGL(render_f32_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, a, nc, nf);
+    if (a.share != kShareOff) hipLaunchKernelGGL((render_f32_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, a, nc, nf);
+    else if (a.min_trans > 0.f && a.evals) hipLaunchKernelGGL(render_f32_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, a, nc, nf);
     else hipLaunchKernelGGL(render_f32_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, a, nc, nf);
 }
 

@@ -11,9 +11,12 @@ template __global__ void render_mfma_kernel<256, 8, 4, true, false, NWE_ONE_KERN
 NWE_SHAPES(NWE_EXTERN_SHAPE_LAUNCHER)
 #ifndef NWE_ONLY_HEADLINE   // diagnostic builds hold no terminating kernels
 NWE_SHAPES(NWE_EXTERN_SHAPE_TERM_LAUNCHER)
+NWE_SHAPES(NWE_EXTERN_SHAPE_SHARE_LAUNCHER)
 #define NWE_TERM_BUILT(FORM_) term_built(FORM_)
+#define NWE_SHARE_BUILT(FORM_) share_built(FORM_)
 #else
 #define NWE_TERM_BUILT(FORM_) false
+#define NWE_SHARE_BUILT(FORM_) false
 #endif
 #define NWE_SHAPE_IS(W_, D_, SKIP_, FORM_) (W == W_ && D == D_ && skip == SKIP_ && form == FORM_)
 
@@ -30,6 +33,12 @@ bool mfma_term_supported(int D, int W, int skip, int form) {
 #undef NWE_OR_TERM_SHAPE
 }
 
+bool mfma_share_supported(int D, int W, int skip, int form) {
+#define NWE_OR_SHARE_SHAPE(W_, D_, SKIP_, FORM_) || (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_) && NWE_SHARE_BUILT(FORM_))
+    return false NWE_SHAPES(NWE_OR_SHARE_SHAPE);
+#undef NWE_OR_SHARE_SHAPE
+}
+
 int mfma_max_samples() { return kSplitMaxSamples; }
 
 // The plan of a call: 0 = all packets, 1 = all sample-split, 2 = hybrid; *full = the rays of the hybrid plan's first launch.
@@ -41,8 +50,12 @@ static int plan_launch(const RenderArgs& a, int decomposition, int64_t* full_out
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (cus <= 0) cus = 256;
     const int64_t rays_wg = kWaves * kRaysPerWave;
-    const double its = (double)(a.n_samples + (a.n_importance > 0 ? a.n_samples + a.n_importance : 0));
-    const double its_split = 1.06 * (double)((a.n_samples + 3) / 4 + (a.n_importance > 0 ? (a.n_samples + a.n_importance + 3) / 4 : 0));
+    // the sample iterations this launch runs: both passes, or - shared coarse pass - the producer's coarse pass alone, the
+    // consumer's fine pass alone
+    const int s_coarse = share_role(a) == kShareConsumer ? 0 : a.n_samples;
+    const int s_fine = share_role(a) == kShareProducer || a.n_importance <= 0 ? 0 : a.n_samples + a.n_importance;
+    const double its = (double)(s_coarse + s_fine);
+    const double its_split = 1.06 * (double)((s_coarse + 3) / 4 + (s_fine + 3) / 4);
     const auto rounds = [&](int64_t rays, int64_t per_wg) { return (double)(((rays + per_wg - 1) / per_wg + cus - 1) / cus); };
     const int64_t full = (a.n_rays / rays_wg / cus) * cus * rays_wg;            // rays in complete rounds of packet workgroups
     const double t_packet = rounds(a.n_rays, rays_wg) * its;
@@ -69,10 +82,13 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
     // the rest by name before it gets here)
     const bool term = a.min_trans > 0.f;
     if (term && (!is_lean(a) || !a.evals || !mfma_term_supported(D, W, skip, form))) return false;
+    // shared coarse pass (a.share): the shape's sharing kernels, under the same conditions
+    const bool share = a.share != kShareOff;
+    if (share && (term || !is_lean(a) || !a.share_w || a.n_importance <= 0 || !mfma_share_supported(D, W, skip, form))) return false;
 #ifndef NWE_ONLY_HEADLINE
 #define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_)                                                          \
     if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {                                                         \
-        launch = term ? launch_one_term<W_, D_, SKIP_, FORM_> : launch_one<W_, D_, SKIP_, FORM_>;     \
+        launch = term ? launch_one_term<W_, D_, SKIP_, FORM_> : share ? launch_one_share<W_, D_, SKIP_, FORM_> : launch_one<W_, D_, SKIP_, FORM_>; \
         n_chunks = Shape<W_, D_>::n_chunks(FORM_);                                                    \
     }
 #else

@@ -1,0 +1,6 @@
+// Instantiations of the MFMA render kernel with the shared coarse pass, group E of nwe_mfma_shapes.h.
+#include "nwe_mfma_kernels.h"
+
+namespace nwe {
+NWE_SHAPES_E(NWE_SHAPE_SHARE_LAUNCHER)
+}  // namespace nwe

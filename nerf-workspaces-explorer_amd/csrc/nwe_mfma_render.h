@@ -114,9 +114,21 @@ __device__ __forceinline__ void read_raw(const float* raw_in, int64_t at, float&
 // The ray evaluations executed go to *a.evals, one atomic per wave: rays of its own x samples its workgroup walked.
 constexpr int kVoteBytes = 2 * kWaves * 4;
 
-template <int W, int D, int SKIP, bool X3, bool SPLIT, int FORM, bool LEAN, bool TERM = false>
+// SHARE: the coarse pass shared by k x k pixel blocks (include/nwe.h, nwe_set_shared_coarse), for the same LEAN kernels.  One
+// instantiation, two launches with a workgroup-uniform role (RenderArgs::share):
+//   producer: its rays are the representative pixels of the call's blocks (seed_rep_ray).  Pass 0 only - density-only where
+//             that is built - and each sample's weight also goes to the table a.share_w[sample][representative]: the 32 rays
+//             of a packet store one 128-byte line per sample.  No per-ray output, no flag.
+//   consumer: the call's rays.  Pass 0 is the fill of fs.wc from the table column of the ray's representative (share_rep_of;
+//             the path of the a.w_in hook, with an index computed from the pixel and gone again before the sample loop), then
+//             build_cdf and the fine pass as in every other kernel.
+// The weights the consumer reads are the bits the producer's Composite::accumulate returned, the ones an ordinary frame puts
+// into fs.wc for the representative ray itself; near and far are the frame's, so the cdf, and with it z_fine, of a ray is
+// its representative's bit for bit.
+template <int W, int D, int SKIP, bool X3, bool SPLIT, int FORM, bool LEAN, bool TERM = false, bool SHARE = false>
 __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMfma nc, NetMfma nf) {
     static_assert(!TERM || (LEAN && FORM != kFormReference), "early termination: lean kernels of the product formulations only");
+    static_assert(!SHARE || (LEAN && !TERM && FORM != kFormReference), "shared coarse pass: lean kernels of the product formulations, not with TERM");
     RenderArgs a = a_in;
     if constexpr (LEAN) {
         a.out.raw_coarse = a.out.raw_fine = a.out.z_fine = a.out.weights_coarse = nullptr;
@@ -160,7 +172,8 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
     // The ray is kept as its three-register seed and expanded at the top of every sample iteration (bit-identical by
     // construction): nothing of it but |d| stays in registers across an MLP evaluation.  The empty asm hides the seed from
     // loop-invariant code motion, which would otherwise hoist the expansion and spill its results.
-    const RaySeed seed = seed_ray(a, rclamp);
+    const bool producer = SHARE && share_role(a) == kShareProducer, consumer = SHARE && share_role(a) == kShareConsumer;
+    const RaySeed seed = seed_of<SHARE>(a, rclamp);
     auto fresh_ray = [&]() __attribute__((always_inline)) {
         RaySeed sd = seed;
         asm volatile("" : "+v"(sd.pose), "+v"(sd.x), "+v"(sd.y));
@@ -217,6 +230,14 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
             if (wc_writer) for (int s = 0; s < ns; ++s) fs.wc[s * kRaysPerWave] = a.w_in[rclamp * ns + s];
             continue;
         }
+        if constexpr (SHARE) {
+            if (pass == 0 && consumer) {                             // the representative's coarse weights instead of a coarse pass
+                const float* col = a.share_w + share_rep_of(a, rclamp);
+                const int n_rep = share_n_rep(a, share_grid(a));
+                if (wc_writer) for (int s = 0; s < ns; ++s) fs.wc[s * kRaysPerWave] = col[(int64_t)s * n_rep];
+                continue;
+            }
+        }
         comp.reset();
         const bool stops = TERM && (pass == 1 || ni == 0);          // the pass that produces the outputs
         const float eps = stops ? a.min_trans : 0.f;                // 0: nothing is ever below
@@ -256,6 +277,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                         const float w = TERM ? comp.accumulate_above(x[k * kRaysPerWave], zp[k], eps) : comp.accumulate(x[k * kRaysPerWave], zp[k]);
                         if (pass == 0) {
                             if (wc_writer) fs.wc[si * kRaysPerWave] = w;
+                            if constexpr (SHARE) { if (producer && live) a.share_w[si * a.n_rays + row] = w; }   // n_rays = n_rep
                             if (live && a.out.weights_coarse) a.out.weights_coarse[ridx * ns + si] = w;
                         }
                     }
@@ -360,6 +382,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                 const float4 shaded = Composite::shade(rr, rg, rb, rs, z_cur, z_next, s + 1 == Stot, ray.dnorm, noise ? noise[rclamp * Stot + s] : 0.f);
                 const float w = TERM ? comp.accumulate_above(shaded, z_cur, eps) : comp.accumulate(shaded, z_cur);
                 if (pass == 0) fs.wc[s * kRaysPerWave] = w;
+                if constexpr (SHARE) { if (producer && lane_live) a.share_w[s * a.n_rays + row] = w; }   // n_rays = n_rep
                 if (lane_live) {
                     if (pass == 0 && a.out.weights_coarse) a.out.weights_coarse[ridx * ns + s] = w;
                     float* raw = pass == 0 ? a.out.raw_coarse : a.out.raw_fine;
@@ -376,6 +399,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                 }
             }
         }
+        if (producer) break;   // the table is the producer's only result
         if (live) {
             // density-only coarse pass: there is no coarse colour whose flag could be raised (include/nwe.h)
             flags |= store_ray(a.out, ridx, comp, pass == 1, a.white_bkgd != 0) & (density_only ? ~(uint32_t)NWE_FLAG_RGB_COARSE : ~0u);
@@ -427,6 +451,27 @@ void launch_one_term(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool th
         const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
         const unsigned blocks = (unsigned)((rays + per_wg - 1) / per_wg);
 #define NWE_KERNEL(X3_, SPLIT_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, true, true>
+        void (*const kernels[4])(RenderArgs, NetMfma, NetMfma) = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true),
+                                                                  NWE_KERNEL(false, false)};
+#undef NWE_KERNEL
+        hipLaunchKernelGGL(kernels[(three_pass ? 0 : 2) + (split ? 0 : 1)], dim3(blocks), dim3(256), 0, stream, a, nc, nf);
+    }
+}
+
+// Whether a shape has the sharing kernels (SHARE): as the terminating ones.
+constexpr bool share_built(int form) { return form != kFormReference; }
+
+// The same launch for the shared coarse pass (a.share: producer or consumer): the shape's four sharing kernels, lean only.
+// Instantiated per shape in files of their own (nwe_mfma_inst_share_*.hip); nothing for a shape that is not share_built.
+template <int W, int D, int SKIP, int FORM>
+void launch_one_share(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_pass, bool split, int64_t ray_first, int64_t rays,
+                      hipStream_t stream) {
+    if constexpr (share_built(FORM)) {
+        if (rays <= 0) return;
+        a.ray_first = ray_first;
+        const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
+        const unsigned blocks = (unsigned)((rays + per_wg - 1) / per_wg);
+#define NWE_KERNEL(X3_, SPLIT_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, true, false, true>
         void (*const kernels[4])(RenderArgs, NetMfma, NetMfma) = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true),
                                                                   NWE_KERNEL(false, false)};
 #undef NWE_KERNEL

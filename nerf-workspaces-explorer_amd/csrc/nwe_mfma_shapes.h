@@ -29,3 +29,8 @@
 #define NWE_SHAPE_TERM_LAUNCHER(W_, D_, SKIP_, FORM_) \
     template void launch_one_term<W_, D_, SKIP_, FORM_>(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);
 #define NWE_EXTERN_SHAPE_TERM_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_TERM_LAUNCHER(W_, D_, SKIP_, FORM_)
+// The launcher of the shape's four sharing kernels (shared coarse pass: producer and consumer are one instantiation; lean,
+// three-pass / single-pass, packets / sample split), in files of their own (nwe_mfma_inst_share_*.hip).  Empty for kFormReference.
+#define NWE_SHAPE_SHARE_LAUNCHER(W_, D_, SKIP_, FORM_) \
+    template void launch_one_share<W_, D_, SKIP_, FORM_>(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);
+#define NWE_EXTERN_SHAPE_SHARE_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_SHARE_LAUNCHER(W_, D_, SKIP_, FORM_)

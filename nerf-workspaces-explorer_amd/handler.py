@@ -49,10 +49,13 @@ def pinhole_intrinsics(H: int, W: int, hfov_deg: float = 90.0) -> Tuple[float, f
 class NeRFReplicaInferenceHandler:
 
     def __init__(self, office_name: str, ckpt_path: str, device: int = 0, precision: str = "auto",
-                 devices: Optional[Sequence[int]] = None, early_termination: float = 0.0) -> None:
+                 devices: Optional[Sequence[int]] = None, early_termination: float = 0.0, shared_coarse: int = 1) -> None:
         """``early_termination`` (or the environment variable NWE_EARLY_TERMINATION, for the same two-argument callers):
         the minimum transmittance of Renderer.set_early_termination, applied in initialize_models(); 0 = off.  While it is on,
         frames (render, render_batch, render_coordinates) are terminated and ``_render_rays`` raises what the ABI says.
+        ``shared_coarse`` (or the environment variable NWE_SHARED_COARSE): the block edge k of Renderer.set_shared_coarse,
+        applied in initialize_models(); 1 = off.  While it is on, frames share their coarse pass over k x k pixel blocks and
+        ``_render_rays`` raises what the ABI says.  It is refused together with ``early_termination > 0``.
         ``devices`` (or the environment variable NWE_DEVICES, e.g. "0,1,2,3", for a caller that constructs the handler
         with the reference's two arguments, application/workspace.py:28-29): render every frame as row tiles on these
         devices from this one process (renderer.TiledRenderer); a device may be listed more than once."""
@@ -67,6 +70,13 @@ class NeRFReplicaInferenceHandler:
         if not 0.0 <= early_termination < 1.0:      # NaN fails too
             raise ValueError("early_termination (min_transmittance) must be in [0, 1)")
         self._early_termination = float(early_termination)
+        if shared_coarse is not True and shared_coarse == 1 and os.environ.get("NWE_SHARED_COARSE"):
+            shared_coarse = int(os.environ["NWE_SHARED_COARSE"])
+        if isinstance(shared_coarse, bool) or not isinstance(shared_coarse, int) or not 1 <= shared_coarse <= 16:
+            raise ValueError("shared_coarse (block edge k) must be an integer in 1..16")
+        if shared_coarse > 1 and self._early_termination > 0.0:
+            raise ValueError("shared_coarse > 1 and early_termination > 0 are not supported together")
+        self._shared_coarse = shared_coarse
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -136,6 +146,7 @@ class NeRFReplicaInferenceHandler:
         self._renderer.set_sampling(self._n_samples, self._n_importance)
         self._renderer.set_white_background(self._white_bkgd)                     # handler.py:57,231,253
         self._renderer.set_early_termination(self._early_termination)
+        self._renderer.set_shared_coarse(self._shared_coarse)
         if self._auto_precision:
             nets = (_lib.NET_COARSE,) + ((_lib.NET_FINE,) if fine is not None else ())
             mfma = all(self._renderer.mfma_supported(w) for w in nets)
@@ -250,6 +261,11 @@ class NeRFReplicaInferenceHandler:
     def early_termination(self) -> float:
         """The minimum transmittance initialize_models() applies (0 = off)."""
         return self._early_termination
+
+    @property
+    def shared_coarse(self) -> int:
+        """The block edge initialize_models() applies (1 = off)."""
+        return self._shared_coarse
 
     @property
     def image_size(self) -> Tuple[int, int]:

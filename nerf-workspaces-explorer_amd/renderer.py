@@ -309,8 +309,27 @@ class Renderer:
     def early_termination(self) -> float:
         return float(self._lib.nwe_get_early_termination(self._ctx))
 
+    def set_shared_coarse(self, k: int) -> None:
+        """Opt-in coarse pass shared by k x k pixel blocks (include/nwe.h): one ray per block of the whole image runs the coarse
+        pass and the block's pixels draw their importance samples from its weights; everything behind is the pixel's own.
+        1 = off (the default), 1..16.  An approximation.  ``render`` honours it for rgb / depth / acc when
+        n_importance > 0; every other call raises NotImplementedError while it is on, and so does every call while early
+        termination is on as well."""
+        self._check(self._lib.nwe_set_shared_coarse(self._ctx, int(k)), "nwe_set_shared_coarse")
+
+    @property
+    def shared_coarse(self) -> int:
+        return int(self._lib.nwe_get_shared_coarse(self._ctx))
+
+    def last_coarse_launch(self) -> Optional[Tuple[float, int]]:
+        """(ms, representative rays) of the producer launch of the last render, None if it had none (k = 1, n_importance == 0)."""
+        ms, rays = C.c_float(), C.c_int64()
+        self._check(self._lib.nwe_last_coarse_launch(self._ctx, C.byref(ms), C.byref(rays)), "nwe_last_coarse_launch")
+        return (float(ms.value), int(rays.value)) if ms.value >= 0 else None
+
     def last_ray_evaluations(self) -> Tuple[int, int]:
-        """(executed, full) ray evaluations of the last render launch: equal unless early termination skipped some."""
+        """(executed, full) ray evaluations of the last render launch: equal unless early termination skipped some or a
+        shared coarse pass left some out."""
         out = (C.c_int64 * 2)()
         self._check(self._lib.nwe_last_ray_evaluations(self._ctx, out), "nwe_last_ray_evaluations")
         return int(out[0]), int(out[1])
@@ -412,6 +431,10 @@ class TiledRenderer:
     def set_early_termination(self, min_transmittance: float) -> None:
         for p in self.parts:
             p.set_early_termination(min_transmittance)
+
+    def set_shared_coarse(self, k: int) -> None:
+        for p in self.parts:
+            p.set_shared_coarse(k)
 
     def render(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
                rows: Optional[Tuple[int, int]] = None, precision: str = "f16x3",
