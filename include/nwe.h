@@ -331,9 +331,49 @@ float nwe_get_early_termination(const nwe_ctx *ctx);
 int nwe_set_shared_coarse(nwe_ctx *ctx, int k);
 int nwe_get_shared_coarse(const nwe_ctx *ctx);
 
+/* Separate passes, opt-in: on = 0 or 1; 0 (the default) is off and changes nothing.  Anything else is NWE_ERR_INVALID and the
+ * previous value stays.  Host-side like nwe_set_white_background: copied at launch, works on a host-only context;
+ * nwe_get_separate_passes returns the value (-1 for a NULL context).
+ * Why: the fused MFMA kernel runs both passes with the instantiation of ONE network shape, so a small coarse network under a
+ * full fine one (net_depth / net_width against net_depth_fine / net_width_fine of the reference's YAML) is refused by the MFMA
+ * precisions although each shape has kernels.  With the mode on, a call with n_importance > 0 under NWE_PREC_F16X3 / F16X1 is
+ * two launches on the caller's stream: a coarse launch over the call's rays with the kernels of the coarse network's shape,
+ * which writes every sample's weight to a table the launch owns (or to weights_coarse, if the caller asked for it), and behind
+ * it a fine launch with the kernels of the fine network's shape, which reads the table where the fused kernel runs its coarse
+ * pass.  The two networks may differ in depth, width and skip; each shape must have an MFMA instantiation, and both must agree
+ * in their encodings and in their formulation (view directions or none; packed folded or not), else the call is refused by name.
+ * It is exact: the table carries the floats the fused kernel keeps on chip between its passes, and each launch computes what
+ * the fused kernel's pass computes.  With two networks of one shape every output of every call is bit-identical to the same
+ * call with the mode off; with two shapes the coarse outputs are those of a (coarse, coarse) context and the others those of a
+ * (fine, fine) context fed these weights through nwe_debug_set_coarse_weights, bit for bit.  Work decompositions, the hybrid
+ * plan, row tiles, pose batches and the tiles of nwe_render_tiled stay bit-identical to one another.
+ * Every call that renders with the mode off renders with it on: nwe_render and nwe_render_tiled with any outputs,
+ * nwe_render_rays, its one-shot hooks and its training tables.  Coarse outputs (raw_coarse, weights_coarse, rgb_coarse /
+ * depth_coarse / acc_coarse / disp_coarse) come from the coarse launch, everything else from the fine launch; *flags is the OR
+ * of both.  A call armed with nwe_debug_set_coarse_weights has no coarse launch.  A call that requests nothing but rgb / depth /
+ * acc / flags of pinhole views takes the lean kernels of the shared coarse pass, each pixel its own representative: its coarse
+ * launch writes nothing but the weights and raises the coarse flag bits the fused call raises (NWE_FLAG_RGB_COARSE under the
+ * rule above).
+ * With n_importance == 0 there is one pass and the call renders as with the mode off.  NWE_PREC_F32 ignores the mode: the fp32
+ * kernel takes two shapes in one launch.
+ * With the shared coarse pass (nwe_set_shared_coarse, k > 1) the two compose - that call already is these two launches: the
+ * producer takes the coarse network's kernels and the consumer the fine network's, under the shared coarse pass's own rules.
+ * Refused with NWE_ERR_UNSUPPORTED and a message that names the setting, behind every refusal the call has without it, under
+ * the MFMA precisions: every call while early termination is on (min_transmittance > 0: terminating consumer kernels are not
+ * built), and two networks of which only one was packed unfolded (nwe_debug_set_fold).
+ * Timing: nwe_last_kernel_ms spans both launches, nwe_last_coarse_launch gives the coarse launch's time and ray count,
+ * nwe_last_launch_parts and nwe_debug_last_plan describe the fine launch (each launch picks its own plan;
+ * nwe_debug_set_decomposition forces both), nwe_last_ray_evaluations reports executed == full.  The table is
+ * n_rays * n_samples floats per launch in flight (164 MB for an 800 x 800 x 64 frame); if it cannot be allocated the call fails
+ * with NWE_ERR_HIP, nothing is launched and the timing calls keep describing the last launch that was made. */
+int nwe_set_separate_passes(nwe_ctx *ctx, int on);
+int nwe_get_separate_passes(const nwe_ctx *ctx);
+
 /* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
- * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1, or
- * n_importance == 0).  nwe_last_kernel_ms spans both launches, nwe_last_launch_parts describes the consumer's. */
+ * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1 without separate
+ * passes, n_importance == 0, or a call armed with nwe_debug_set_coarse_weights).  Under separate passes with k = 1 it is the
+ * coarse launch and *rays the call's rays.  nwe_last_kernel_ms spans both launches, nwe_last_launch_parts describes the
+ * consumer's. */
 int nwe_last_coarse_launch(nwe_ctx *ctx, float *ms, int64_t *rays);
 
 /* Ray evaluations of the most recent render launch of this context (the launch nwe_last_kernel_ms describes, under the same

@@ -23,7 +23,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_debug_set_fine_depths", "nwe_debug_set_raw", "nwe_debug_set_coarse_weights", "nwe_debug_set_fold", "nwe_set_train_tables", "nwe_set_white_background", "nwe_debug_set_decomposition", "nwe_debug_last_plan", "nwe_debug_set_stamps", "nwe_selftest",
            "nwe_last_warning", "nwe_debug_peer_access", "nwe_set_network_no_view_dirs", "nwe_last_launch_parts",
            "nwe_set_early_termination", "nwe_get_early_termination", "nwe_last_ray_evaluations",
-           "nwe_set_shared_coarse", "nwe_get_shared_coarse", "nwe_last_coarse_launch")
+           "nwe_set_shared_coarse", "nwe_get_shared_coarse", "nwe_last_coarse_launch",
+           "nwe_set_separate_passes", "nwe_get_separate_passes")
 
 
 class Outputs(C.Structure):
@@ -87,6 +88,8 @@ def load() -> C.CDLL:
         "nwe_set_shared_coarse": (I, [P, I]),
         "nwe_get_shared_coarse": (I, [P]),
         "nwe_last_coarse_launch": (I, [P, C.POINTER(F), C.POINTER(I64)]),
+        "nwe_set_separate_passes": (I, [P, I]),
+        "nwe_get_separate_passes": (I, [P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -67,7 +67,10 @@ struct Slot {
     // shared coarse pass (nwe_set_shared_coarse): the launch's own weight table [n_samples][n_rep], which the producer launch
     // fills and the consumer launch behind it reads (last reader: prepare_slot), the event between the two
     // (nwe_last_coarse_launch), the representatives and the evaluations the two launches ran
+    // separate passes (nwe_set_separate_passes): the same table between the coarse and the fine launch, [n_rays][n_samples] when
+    // the two are full kernels, and the word the coarse launch's flags go through (queue_coarse_flags)
     DevBuf<float> share_w;
+    DevBuf<uint32_t> coarse_flags;
     Event ev_share;
     bool has_share = false;
     int64_t share_rays = 0, evals_run = 0;
@@ -105,6 +108,7 @@ struct nwe_ctx {
     int white_bkgd = 0;
     float min_trans = 0.f;    // nwe_set_early_termination: 0 = off
     int share_k = 1;          // nwe_set_shared_coarse: 1 = off
+    int separate = 0;         // nwe_set_separate_passes: 0 = off
     int decomposition = -1;   // nwe_debug_set_decomposition
     int last_plan = -1;       // nwe_debug_last_plan
     unsigned long long* stamps = nullptr;   // nwe_debug_set_stamps
@@ -148,6 +152,13 @@ __global__ void to8b_kernel(const float* __restrict__ x, uint8_t* __restrict__ y
 __global__ void or_flags_kernel(const uint32_t* __restrict__ parts, int n, uint32_t* __restrict__ out) {
     uint32_t f = 0;
     for (int i = 0; i < n; ++i) f |= parts[i];
+    if (f) atomicOr(out, f);
+}
+
+// Separate passes: the coarse launch of a full kernel is a single-pass render, which also reports its composite under the
+// main outputs' bits; only the bits in `mask` (the coarse outputs' and NWE_FLAG_RAW) reach the caller's word.
+__global__ void or_masked_flags_kernel(const uint32_t* __restrict__ word, uint32_t mask, uint32_t* __restrict__ out) {
+    const uint32_t f = *word & mask;
     if (f) atomicOr(out, f);
 }
 
@@ -236,7 +247,7 @@ RenderArgs camera_args(const Camera& m, const float* poses_dev) {
 }
 
 // pinhole: nwe_render / a tile of nwe_render_tiled (false: nwe_render_rays).  The refusals of early termination and of the
-// shared coarse pass come last.
+// shared coarse pass come last, and those of separate passes behind them.
 int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole) {
     if (!ctx || !out) return fail(ctx, NWE_ERR_INVALID, "null context or outputs");
     if (out->struct_bytes != sizeof(nwe_outputs))
@@ -311,6 +322,15 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhol
             }
         }
     }
+    if (ctx->separate && precision != NWE_PREC_F32) {
+        const std::string separate = "separate passes are on (nwe_set_separate_passes): ";
+        const char* separate_off = "; set separate_passes to 0 for this call";
+        if (ctx->min_trans > 0.f)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, separate + "they are not built together with early termination (nwe_set_early_termination, min_transmittance = " +
+                                                      std::to_string(ctx->min_trans) + "), which would need terminating consumer kernels; switch one of them off");
+        if (ctx->ni > 0 && ctx->net[0].form != ctx->net[1].form)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, separate + "coarse and fine networks must be packed in the same formulation (nwe_debug_set_fold); use NWE_PREC_F32" + separate_off);
+    }
     return NWE_OK;
 }
 
@@ -331,7 +351,16 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
     }
     // Shared coarse pass: with importance samples the call is two launches, the producer over the representatives of the blocks
     // its rows touch (check_ready has refused everything but lean pinhole calls), then the consumer over its rays.
-    const bool share = ctx->share_k > 1 && a.n_importance > 0;
+    // Separate passes (MFMA precisions): the same two launches for every call with importance samples, each with the kernel of
+    // its own network's shape and with that network in both descriptor slots, so that a kernel copies bias tables of its own
+    // shape only.  A lean call takes the sharing kernels, at k = 1 every pixel its own representative; every other call the
+    // full kernels: the coarse launch is their single-pass render (n_importance = 0) whose weights_coarse output is the table,
+    // the fine launch reads the table through the coarse-weights hook (w_in), which takes the place of pass 0.
+    const bool separate = ctx->separate && precision != NWE_PREC_F32 && a.n_importance > 0;
+    const auto has_share_kernels = [](const NetState& n) { return mfma_share_supported(n.D, n.W, n.skip, n.form); };
+    const bool share = a.n_importance > 0 && (ctx->share_k > 1 || (separate && mfma_is_lean(a) && has_share_kernels(nc) && has_share_kernels(nf)));
+    const bool full = separate && !share;           // separate passes through the full kernels
+    const bool coarse_launch = share || (full && !a.w_in);   // with the coarse-weights hook armed there is no coarse pass
     RenderArgs prod = {};
     if (share) {
         a.share = kShareConsumer | ctx->share_k << 8;
@@ -340,18 +369,52 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         a.share_w = slot.share_w.get();
         prod = a;
         prod.share = kShareProducer | ctx->share_k << 8; prod.n_rays = n_rep; prod.out = {};
+        // k = 1 (separate passes): every ray runs its own coarse pass, whose flag bits are the fused kernel's; a representative's
+        // coarse pass (k > 1) describes no ray of the call
+        if (ctx->share_k == 1) prod.out.flags = a.out.flags;
     }
+    if (full) {
+        a.share = kShareConsumer | 1 << 8;   // the full kernels do not read it: plan_launch costs the launch by its role
+        if (coarse_launch) {
+            float* table = a.out.weights_coarse;   // the caller's own table [n_rays][n_samples] if it asked for one
+            if (!table) {
+                HIPCHK(ctx, slot.share_w.reserve((size_t)a.n_rays * a.n_samples));
+                table = slot.share_w.get();
+            }
+            prod = a;
+            prod.share = kShareProducer | 1 << 8; prod.n_importance = 0;
+            prod.z_fine_in = prod.raw_in_f = prod.noise_f = prod.u_rand = nullptr;
+            prod.out = {};
+            prod.out.struct_bytes = a.out.struct_bytes;
+            prod.out.raw_coarse = a.out.raw_coarse; prod.out.weights_coarse = table;
+            prod.out.rgb_coarse = a.out.rgb_coarse; prod.out.depth_coarse = a.out.depth_coarse;
+            prod.out.acc_coarse = a.out.acc_coarse; prod.out.disp_coarse = a.out.disp_coarse;
+            if (a.out.flags) {
+                HIPCHK(ctx, slot.coarse_flags.reserve(1));
+                HIPCHK(ctx, hipMemsetAsync(slot.coarse_flags.get(), 0, sizeof(uint32_t), stream));
+                prod.out.flags = slot.coarse_flags.get();
+            }
+            a.w_in = table;
+        }
+        a.raw_in_c = a.noise_c = nullptr;   // the coarse launch's
+        a.out.raw_coarse = a.out.weights_coarse = a.out.rgb_coarse = a.out.depth_coarse = a.out.acc_coarse = a.out.disp_coarse = nullptr;
+    }
+    // the descriptors of the coarse and of the fine launch: (coarse, fine) for one fused kernel, its own network twice otherwise
+    const NetMfma &prod_f = separate ? nc.mf : nf.mf, &cons_c = separate ? nf.mf : nc.mf;
     const int rc = record_launch(ctx, slot, stream, [&]() -> int {
         slot.has_mid = false; slot.rays_first = slot.rays_total = a.n_rays;
         slot.term = a.min_trans > 0.f;
         slot.evals_full = a.n_rays * (int64_t)(a.n_samples + (a.n_importance > 0 ? a.n_samples + a.n_importance : 0));
-        slot.evals_run = share ? prod.n_rays * a.n_samples + a.n_rays * (int64_t)(a.n_samples + a.n_importance) : slot.evals_full;
-        slot.share_rays = share ? prod.n_rays : 0;
+        slot.evals_run = coarse_launch ? prod.n_rays * a.n_samples + a.n_rays * (int64_t)(a.n_samples + a.n_importance) : slot.evals_full;
+        slot.share_rays = coarse_launch ? prod.n_rays : 0;
         const char* shapes_differ = "coarse and fine networks must have the same shape for the MFMA kernel";
-        if (share) {
+        if (coarse_launch) {
             if (precision == NWE_PREC_F32) launch_render_f32(prod, nc.f32, nf.f32, stream);
-            else if (!launch_render_mfma(prod, nc.mf, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, nullptr))
+            else if (!launch_render_mfma(prod, nc.mf, prod_f, precision == NWE_PREC_F16X3, ctx->decomposition, stream, nullptr))
                 return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
+            if (full && prod.out.flags)
+                hipLaunchKernelGGL(or_masked_flags_kernel, dim3(1), dim3(1), 0, stream, prod.out.flags,
+                                   ~(uint32_t)(NWE_FLAG_RGB | NWE_FLAG_DEPTH | NWE_FLAG_ACC | NWE_FLAG_DISP), a.out.flags);
             HIPCHK(ctx, hipEventRecord(slot.ev_share, stream));
             slot.has_share = true;
         }
@@ -361,7 +424,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         }
         LaunchInfo info;
         info.mid = slot.ev_mid;
-        if (!launch_render_mfma(a, nc.mf, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info))
+        if (!launch_render_mfma(a, cons_c, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info))
             return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
         ctx->last_plan = info.plan;
         slot.has_mid = info.mid_recorded; slot.rays_first = info.rays_first;
@@ -785,6 +848,13 @@ int nwe_set_shared_coarse(nwe_ctx* c, int k) {
     return NWE_OK;
 }
 int nwe_get_shared_coarse(const nwe_ctx* c) { return c ? c->share_k : -1; }
+int nwe_set_separate_passes(nwe_ctx* c, int on) {
+    if (!c) return NWE_ERR_INVALID;
+    if (on != 0 && on != 1) return fail(c, NWE_ERR_INVALID, "separate_passes must be 0 or 1 (0 = off)");
+    c->separate = on;
+    return NWE_OK;
+}
+int nwe_get_separate_passes(const nwe_ctx* c) { return c ? c->separate : -1; }
 int nwe_set_train_tables(nwe_ctx* c, const float* t_rand_dev, const float* noise_coarse_dev, const float* noise_fine_dev, const float* u_sorted_dev) {
     return set_on(c, [&] { c->trn_t = t_rand_dev; c->trn_nc = noise_coarse_dev; c->trn_nf = noise_fine_dev; c->trn_u = u_sorted_dev; });
 }

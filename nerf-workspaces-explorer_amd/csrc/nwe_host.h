@@ -34,6 +34,10 @@ bool mfma_term_supported(int D, int W, int skip, int form);
 // true if the shape's sharing kernels (shared coarse pass) were built: the same shapes
 bool mfma_share_supported(int D, int W, int skip, int form);
 
+// true if the MFMA launch of `a` takes the lean instantiations: no output beyond rgb / depth / acc / flags, no hook, no table, no
+// precomputed rays (is_lean, nwe_mfma_render.h)
+bool mfma_is_lean(const RenderArgs& a);
+
 int mfma_max_samples();      // n_samples the MFMA kernel's per-wave LDS buffers are sized for
 
 // Self-test kernels (nwe_selftest.hip)

@@ -39,6 +39,8 @@ bool mfma_share_supported(int D, int W, int skip, int form) {
 #undef NWE_OR_SHARE_SHAPE
 }
 
+bool mfma_is_lean(const RenderArgs& a) { return is_lean(a); }
+
 int mfma_max_samples() { return kSplitMaxSamples; }
 
 // The plan of a call: 0 = all packets, 1 = all sample-split, 2 = hybrid; *full = the rays of the hybrid plan's first launch.
@@ -82,9 +84,13 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
     // the rest by name before it gets here)
     const bool term = a.min_trans > 0.f;
     if (term && (!is_lean(a) || !a.evals || !mfma_term_supported(D, W, skip, form))) return false;
-    // shared coarse pass (a.share): the shape's sharing kernels, under the same conditions
-    const bool share = a.share != kShareOff;
-    if (share && (term || !is_lean(a) || !a.share_w || a.n_importance <= 0 || !mfma_share_supported(D, W, skip, form))) return false;
+    // shared coarse pass (a.share) of a lean call: the shape's sharing kernels, under the same conditions.  A call that is
+    // not lean carries a role only under separate passes (nwe_abi.hip): its two launches are full kernels, which do not read
+    // it - the coarse one renders a single pass, the fine one takes the coarse weights from a.w_in - and plan_launch costs each
+    // by its role
+    const bool share = a.share != kShareOff && is_lean(a);
+    if (a.share != kShareOff && !share && (term || (share_role(a) == kShareProducer ? a.n_importance != 0 : !a.w_in))) return false;
+    if (share && (term || !a.share_w || a.n_importance <= 0 || !mfma_share_supported(D, W, skip, form))) return false;
 #ifndef NWE_ONLY_HEADLINE
 #define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_)                                                          \
     if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {                                                         \

@@ -118,7 +118,8 @@ constexpr int kVoteBytes = 2 * kWaves * 4;
 // instantiation, two launches with a workgroup-uniform role (RenderArgs::share):
 //   producer: its rays are the representative pixels of the call's blocks (seed_rep_ray).  Pass 0 only - density-only where
 //             that is built - and each sample's weight also goes to the table a.share_w[sample][representative]: the 32 rays
-//             of a packet store one 128-byte line per sample.  No per-ray output, no flag.
+//             of a packet store one 128-byte line per sample.  No per-ray output; the coarse flag bits of its composite go to
+//             a.out.flags, which is null unless every ray is its own representative (k = 1 under separate passes).
 //   consumer: the call's rays.  Pass 0 is the fill of fs.wc from the table column of the ray's representative (share_rep_of;
 //             the path of the a.w_in hook, with an index computed from the pixel and gone again before the sample loop), then
 //             build_cdf and the fine pass as in every other kernel.
@@ -399,12 +400,14 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
                 }
             }
         }
-        if (producer) break;   // the table is the producer's only result
         if (live) {
             // density-only coarse pass: there is no coarse colour whose flag could be raised (include/nwe.h)
             flags |= store_ray(a.out, ridx, comp, pass == 1, a.white_bkgd != 0) & (density_only ? ~(uint32_t)NWE_FLAG_RGB_COARSE : ~0u);
             if (ni == 0) flags |= store_ray(a.out, ridx, comp, true, a.white_bkgd != 0);
         }
+        // the table is the producer's only result; its coarse flag bits reach a flag word only where the launcher gave it one
+        // (separate passes at k = 1, where every ray runs its own coarse pass: nwe_abi.hip)
+        if (producer) break;
     }
     if (flags && a.out.flags) atomicOr(a.out.flags, flags);
 #ifdef NWE_STAMPS

@@ -49,13 +49,18 @@ def pinhole_intrinsics(H: int, W: int, hfov_deg: float = 90.0) -> Tuple[float, f
 class NeRFReplicaInferenceHandler:
 
     def __init__(self, office_name: str, ckpt_path: str, device: int = 0, precision: str = "auto",
-                 devices: Optional[Sequence[int]] = None, early_termination: float = 0.0, shared_coarse: int = 1) -> None:
+                 devices: Optional[Sequence[int]] = None, early_termination: float = 0.0, shared_coarse: int = 1,
+                 separate_passes: Optional[bool] = None) -> None:
         """``early_termination`` (or the environment variable NWE_EARLY_TERMINATION, for the same two-argument callers):
         the minimum transmittance of Renderer.set_early_termination, applied in initialize_models(); 0 = off.  While it is on,
         frames (render, render_batch, render_coordinates) are terminated and ``_render_rays`` raises what the ABI says.
         ``shared_coarse`` (or the environment variable NWE_SHARED_COARSE): the block edge k of Renderer.set_shared_coarse,
         applied in initialize_models(); 1 = off.  While it is on, frames share their coarse pass over k x k pixel blocks and
         ``_render_rays`` raises what the ABI says.  It is refused together with ``early_termination > 0``.
+        ``separate_passes`` (or the environment variable NWE_SEPARATE_PASSES = 0 / 1, read when the argument is None):
+        Renderer.set_separate_passes, applied in initialize_models(); off by default.  While it is on, "auto" keeps a coarse and
+        a fine network of two different MFMA shapes on the MFMA path (f16x3): the coarse and the fine pass are launched
+        separately, each with the kernel of its own shape.  It is refused together with ``early_termination > 0``.
         ``devices`` (or the environment variable NWE_DEVICES, e.g. "0,1,2,3", for a caller that constructs the handler
         with the reference's two arguments, application/workspace.py:28-29): render every frame as row tiles on these
         devices from this one process (renderer.TiledRenderer); a device may be listed more than once."""
@@ -77,6 +82,16 @@ class NeRFReplicaInferenceHandler:
         if shared_coarse > 1 and self._early_termination > 0.0:
             raise ValueError("shared_coarse > 1 and early_termination > 0 are not supported together")
         self._shared_coarse = shared_coarse
+        if separate_passes is None:
+            env = os.environ.get("NWE_SEPARATE_PASSES", "0").strip()
+            if env not in ("", "0", "1"):
+                raise ValueError("NWE_SEPARATE_PASSES (separate_passes) must be 0 or 1")
+            separate_passes = env == "1"
+        if not isinstance(separate_passes, bool):
+            raise ValueError("separate_passes must be True, False or None")
+        if separate_passes and self._early_termination > 0.0:
+            raise ValueError("separate_passes and early_termination > 0 are not supported together")
+        self._separate_passes = separate_passes
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -147,16 +162,23 @@ class NeRFReplicaInferenceHandler:
         self._renderer.set_white_background(self._white_bkgd)                     # handler.py:57,231,253
         self._renderer.set_early_termination(self._early_termination)
         self._renderer.set_shared_coarse(self._shared_coarse)
+        self._renderer.set_separate_passes(self._separate_passes)
         if self._auto_precision:
             nets = (_lib.NET_COARSE,) + ((_lib.NET_FINE,) if fine is not None else ())
-            mfma = all(self._renderer.mfma_supported(w) for w in nets)
+            each = all(self._renderer.mfma_supported(w) for w in nets)
+            mfma, hint = each, ""
             if mfma and fine is not None and self._renderer.shapes[_lib.NET_COARSE] != self._renderer.shapes[_lib.NET_FINE]:
-                mfma = False                  # the fused MFMA kernel runs both passes with one instantiation
+                # the fused MFMA kernel runs both passes with one instantiation; separate passes launch one per network, which
+                # must still share their encodings (in_xyz, in_dir)
+                same_encodings = self._renderer.shapes[_lib.NET_COARSE][2:4] == self._renderer.shapes[_lib.NET_FINE][2:4]
+                mfma = self._separate_passes and same_encodings
+                if same_encodings and not mfma:
+                    hint = "; separate_passes=True or NWE_SEPARATE_PASSES=1 renders such a pair with the MFMA kernels"
             self._precision = "f16x3" if mfma else "f32"
             if not mfma:
                 shapes = " / ".join(str(self._renderer.shapes.get(w)) for w in nets)
                 print(f"[nwe] network shape {shapes} has no MFMA instantiation: rendering with the "
-                      "fp32 vector-ALU kernel (same results, ~25x slower)")
+                      f"fp32 vector-ALU kernel (same results, ~25x slower){hint}")
 
     def _need_renderer(self) -> Renderer:
         if self._renderer is None:
@@ -266,6 +288,11 @@ class NeRFReplicaInferenceHandler:
     def shared_coarse(self) -> int:
         """The block edge initialize_models() applies (1 = off)."""
         return self._shared_coarse
+
+    @property
+    def separate_passes(self) -> bool:
+        """What initialize_models() hands to Renderer.set_separate_passes."""
+        return self._separate_passes
 
     @property
     def image_size(self) -> Tuple[int, int]:

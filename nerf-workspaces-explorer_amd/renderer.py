@@ -321,8 +321,20 @@ class Renderer:
     def shared_coarse(self) -> int:
         return int(self._lib.nwe_get_shared_coarse(self._ctx))
 
+    def set_separate_passes(self, on: bool) -> None:
+        """Opt-in separate passes (include/nwe.h): under the MFMA precisions a call with n_importance > 0 is a coarse launch
+        with the coarse network's kernels and a fine launch with the fine network's, so the two networks may differ in depth,
+        width and skip.  Exact: with one shape every output is bit-identical to the fused call.  Off by default; every call
+        raises NotImplementedError while early termination is on as well."""
+        self._check(self._lib.nwe_set_separate_passes(self._ctx, 1 if on else 0), "nwe_set_separate_passes")
+
+    @property
+    def separate_passes(self) -> bool:
+        return int(self._lib.nwe_get_separate_passes(self._ctx)) == 1
+
     def last_coarse_launch(self) -> Optional[Tuple[float, int]]:
-        """(ms, representative rays) of the producer launch of the last render, None if it had none (k = 1, n_importance == 0)."""
+        """(ms, rays) of the coarse (producer) launch of the last render, None if it had none (k = 1 without separate passes,
+        n_importance == 0)."""
         ms, rays = C.c_float(), C.c_int64()
         self._check(self._lib.nwe_last_coarse_launch(self._ctx, C.byref(ms), C.byref(rays)), "nwe_last_coarse_launch")
         return (float(ms.value), int(rays.value)) if ms.value >= 0 else None
@@ -435,6 +447,10 @@ class TiledRenderer:
     def set_shared_coarse(self, k: int) -> None:
         for p in self.parts:
             p.set_shared_coarse(k)
+
+    def set_separate_passes(self, on: bool) -> None:
+        for p in self.parts:
+            p.set_separate_passes(on)
 
     def render(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
                rows: Optional[Tuple[int, int]] = None, precision: str = "f16x3",
