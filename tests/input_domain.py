@@ -86,8 +86,11 @@ class Case:
         return {"disp": ACC0, "disp_coarse": ACC0, **e}
 
 
-def nets(case: Case, D: int, Wd: int, form: str, seed: int = 4100) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
-    """Thin-fog coarse network and a plain random fine network (tests/test_gpu_accuracy._nets), spoiled as the case says."""
+def nets(case: Case, D: int, Wd: int, form: str, seed: int = 4100,
+         fine_fog: Optional[Tuple[float, float]] = None) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+    """Thin-fog coarse network and a plain random fine network (tests/test_gpu_accuracy._nets), spoiled as the case says.
+    `fine_fog` = (sigma, spread): the fine network's density head is that fog as well (before the spoil), dense enough to end
+    rays - the scenes of early termination (tests/mode_domain.py)."""
     novd = form == "no_view_dirs"
     if novd:
         sd_c = synthetic.thin_fog_output(synthetic.make_state_dict(seed + D + Wd, D, Wd, use_view_dirs=False))
@@ -95,6 +98,8 @@ def nets(case: Case, D: int, Wd: int, form: str, seed: int = 4100) -> Tuple[Dict
     else:
         sd_c = synthetic.thin_fog(synthetic.make_state_dict(seed + D + Wd, D, Wd))
         sd_f = synthetic.make_state_dict(seed + 1 + D + Wd, D, Wd)
+    if fine_fog is not None:
+        sd_f = (synthetic.thin_fog_output if novd else synthetic.thin_fog)(sd_f, *fine_fog)
     sp = case.spoil_novd if novd and case.spoil_novd is not None else case.spoil
     if sp is not None:
         which, key, idx, value = sp
@@ -315,9 +320,9 @@ NS, NI = 64, 128
 
 
 def run_oracle(case: Case, D: int, Wd: int, form: str, dtype: torch.dtype = torch.float32, ns: int = NS, ni: int = NI,
-               big: bool = False):
+               big: bool = False, fine_fog: Optional[Tuple[float, float]] = None):
     """(rays, coarse state, fine state, oracle outputs) of a case in `dtype`."""
-    sd_c, sd_f = nets(case, D, Wd, form)
+    sd_c, sd_f = nets(case, D, Wd, form, fine_fog=fine_fog)
     rays = case.make_rays(form != "no_view_dirs", big)
     res = O.render_rays(rays, tensors(sd_c), tensors(sd_f) if ni else None, O.RenderConfig(n_samples=ns, n_importance=ni), dtype=dtype)
     return rays, sd_c, sd_f, res

@@ -14,6 +14,7 @@ import nwe_amd
 from nwe_amd import synthetic
 from oracle import nerf_oracle as O
 from tests import early_termination as E
+from tests import mode_domain as M
 from tests import shape_domain as S
 from tests import shared_coarse as SC
 
@@ -25,8 +26,8 @@ COARSE = ("rgb_coarse", "depth_coarse", "acc_coarse", "disp_coarse", "raw_coarse
 REST = ("rgb", "depth", "acc", "disp", "z_std", "raw_fine", "z_fine", "sample_cond", "sample_amp", "sample_switch")
 FULL = REST + COARSE
 FRAMES = {"7x19x2": (7, 19, 2), "12x64": (12, 64, 1)}
-# name -> (depth, width, view directions)
-NETS = {"4x128": (4, 128, True), "8x256": (8, 256, True), "4x128-noview": (4, 128, False), "8x256-noview": (8, 256, False)}
+# name -> (depth, width, view directions): "4x128", "8x256", "4x128-noview", "8x256-noview" and every other shape with MFMA kernels
+NETS = M.NETS
 
 
 def _sd(kind, seed):
@@ -150,13 +151,7 @@ MIXED = [
 def _expected_mixed(coarse, fine, ns, ni, precision, white, rays):
     """Context A holds (coarse, coarse): its coarse outputs and weights.  Context B holds (fine, fine): everything else, on A's
     weights through the coarse-weights hook.  Both render with the fused kernels."""
-    A, B = _renderer(coarse, (coarse, 1000), ns, ni, white=white), _renderer((fine, 1001), fine, ns, ni, white=white)
-    try:
-        a = A.render_rays(rays, precision=precision, outputs=COARSE)
-        b = B.render_rays(rays, precision=precision, outputs=REST, debug_coarse_weights=a["weights_coarse"])
-        return a, b
-    finally:
-        A.close(); B.close()
+    return M.expected_mixed(lambda c, f: _renderer(c, f, ns, ni, white=white), coarse, fine, precision, rays, COARSE, REST)
 
 
 @pytest.mark.parametrize("coarse,fine,ns,ni,precision,white", MIXED)

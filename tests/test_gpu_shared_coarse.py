@@ -14,6 +14,7 @@ import nwe_amd
 from nwe_amd import synthetic
 from oracle import nerf_oracle as O
 from tests import early_termination as E
+from tests import mode_domain as M
 from tests import shared_coarse as SC
 
 pytestmark = pytest.mark.gpu
@@ -21,8 +22,9 @@ pytestmark = pytest.mark.gpu
 LEAN = ("rgb", "depth", "acc")
 TOL = {"rgb": 1e-4, "depth": 1e-4 * E.FAR, "acc": 1e-4}
 FRAMES = {"7x19x2": (7, 19, 2), "12x64": (12, 64, 1)}
-# name -> (depth, width, view directions): the bench's kind of raw random networks, the roughest weights there are
-NETS = {"4x128": (4, 128, True), "8x256": (8, 256, True), "4x128-noview": (4, 128, False)}
+# name -> (depth, width, view directions): the bench's kind of raw random networks, the roughest weights there are; "4x128",
+# "8x256", "4x128-noview" and every other shape the sharing kernels are built for
+NETS = M.NETS
 
 
 def _nets(kind, seed=1000):
@@ -75,10 +77,7 @@ def _same_as_expected(got, want, ctx):
 def _expected(r, H, W, n_poses, k, precision, view=True):
     """What the rule says, from entry points that exist without it: (a) the ordinary render's fine depths Z of the frame's
     rays, (b) every ray's fine pass on Z[rep].  The context must have k = 1 while this runs."""
-    rays = r.create_rays(_poses(n_poses), H, W, use_view_dirs=view, **_camera(H, W))
-    Z = r.render_rays(rays, precision=precision, outputs=LEAN + ("z_fine",))["z_fine"]
-    rep = torch.from_numpy(SC.rep_index(H, W, k, 0, H, n_poses)).to(Z.device)
-    return r.render_rays(rays, precision=precision, outputs=LEAN, debug_fine_depths=Z[rep].contiguous())
+    return M.expected_shared(r, _poses(n_poses), H, W, k, precision, view, _camera(H, W))
 
 
 # ---- 1. the rule, bit for bit -------------------------------------------------------------------------------------------------
