@@ -232,7 +232,10 @@ float nwe_last_kernel_ms(nwe_ctx *ctx);
 /* The same launch taken apart: a frame whose last round of workgroups is ragged is rendered as TWO launches of the kernel
  * template back to back (the full rounds as four-packet workgroups, the rest sample-split; nwe_debug_last_plan == 2).
  * ms2[0], rays2[0]: the first (or only) launch; ms2[1], rays2[1]: the second, -1 / 0 if there was none.  Blocks like
- * nwe_last_kernel_ms. */
+ * nwe_last_kernel_ms.  With the work queue on (nwe_debug_set_work_queue, the default for frames larger than the device) the
+ * second launch runs BESIDE the first: ms2[1] is then how long the frame ran beyond its first launch, not the second kernel's
+ * time, often next to nothing: a rate computed from it means nothing.  The parts are positive (never 0: a part below the
+ * timer's step of 1e-5 ms is reported as that step) and add up to nwe_last_kernel_ms to within that step. */
 int nwe_last_launch_parts(nwe_ctx *ctx, float *ms2, int64_t *rays2);
 
 /* --- test hooks ------------------------------------------------------------------------------- */
@@ -407,8 +410,41 @@ int nwe_debug_set_decomposition(nwe_ctx *ctx, int mode);
  * none yet: lets a test check the launcher's choice without timing anything. */
 int nwe_debug_last_plan(const nwe_ctx *ctx);
 
-/* Diagnostic builds only (make -C csrc stamps): DEVICE buffer of 10 uint64 per wave that a -DNWE_STAMPS build of the MFMA
- * kernel fills with s_memtime cycle sums (tools/stamp_run.py); the product build never touches it.  NULL switches it off. */
+/* How the workgroups of a plain MFMA launch get their work ("Dealing"; bit-identical results).  The hardware
+ * hands workgroup b of a launch to XCD (b + c) mod 8: an eighth of the launch per XCD, whatever pace the XCD runs at, and the
+ * launch ends with the slowest.  A QUEUED launch of n work items instead starts nwe_debug_queue_grid(n) workgroups, each of
+ * which takes a ticket from a counter as its first act and renders that item - or leaves at once if the ticket is not below
+ * n - so a faster XCD takes more of the frame.  Under the hybrid plan with queues on, the sample-split launch is also sent to
+ * a low-priority stream of the context's own that forks from the caller's stream in front of the packets launch and is
+ * joined behind it: its quarter-size items fill the CUs that have run out of packets while the slowest XCD finishes.
+ *   mode -1 (default): queue a launch that has more workgroups than the device has CUs
+ *   mode  0: never queue - the hardware's dealing, grid for grid
+ *   mode  1: queue every plain MFMA launch whatever its size (tests)
+ * NWE_WORK_QUEUE=0 / 1 in the environment sets the mode a new context starts with; NWE_WORK_QUEUE_BACKFILL=0 keeps a new
+ * context's second launch on the caller's stream behind the first (A/B timing of the backfill on one library).  Early termination, the shared coarse pass,
+ * separate passes and NWE_PREC_F32 keep their launches as they are and report no queue.
+ * nwe_last_launch_parts under a backfilled hybrid plan: ms2[0] is the packets launch as before; ms2[1] is how long the frame
+ * ran BEYOND its first launch, not the time of the second launch (which ran beside the first), so a rate computed from it
+ * means nothing.  Both stay positive and add up to nwe_last_kernel_ms to within the timer's step: the three events lie on the
+ * caller's stream in order, the last behind the join, and a part below that step is reported as the step (1e-5 ms). */
+int nwe_debug_set_work_queue(nwe_ctx *ctx, int mode);
+int nwe_debug_get_work_queue(const nwe_ctx *ctx);               /* -2 for a null context */
+int nwe_debug_get_work_queue_backfill(const nwe_ctx *ctx);      /* 1, or 0 under NWE_WORK_QUEUE_BACKFILL=0; -1 for a null context */
+/* The grid of a queued launch of `items` work items: items plus a quarter, rounded up to a multiple of 8.  No device needed. */
+unsigned nwe_debug_queue_grid(unsigned items);
+/* The most recent recorded render launch of this context, per launch of its plan: its work items, its grid and the final value
+ * of its ticket counter (= grid when every workgroup took one); zeros = not queued.  *side_stream (may be NULL): 1 if the
+ * second launch ran on the context's low-priority stream.  Waits for the launch, like the timing calls. */
+int nwe_debug_last_queue(nwe_ctx *ctx, unsigned *items2, unsigned *grid2, unsigned *taken2, int *side_stream);
+
+/* Diagnostic builds only (make -C csrc stamps): DEVICE buffer of 14 uint64 per wave that a -DNWE_STAMPS build of the MFMA
+ * kernel fills with s_memtime cycle sums (tools/stamp_run.py); the product build never touches it.  NULL switches it off.
+ * Row = (work item of its launch) * 4 + wave, however the items were dealt (nwe_debug_set_work_queue), and the rows of the hybrid
+ * plan's second launch follow the first's: the buffer holds 4 rows per work item of the call, i.e. 4 * ceil(rays / 128) for a
+ * packets launch plus 4 * ceil(rays / 32) for a sample-split one, whatever the grid.  Words 0-7:
+ * cycle sums per segment, 8: the wave's lifetime in 100 MHz ticks (s_memrealtime), 9: s_memtime at its start, 10:
+ * HW_REG_XCC_ID (the XCD: low four bits) | HW_REG_HW_ID << 32, 11: the work item it rendered, 12 / 13: its start / end on
+ * the 100 MHz clock. */
 int nwe_debug_set_stamps(nwe_ctx *ctx, unsigned long long *per_wave_dev);
 
 /* Device self-test of the hardware assumptions the MFMA kernel relies on (fragment layouts of

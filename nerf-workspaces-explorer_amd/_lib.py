@@ -24,7 +24,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_last_warning", "nwe_debug_peer_access", "nwe_set_network_no_view_dirs", "nwe_last_launch_parts",
            "nwe_set_early_termination", "nwe_get_early_termination", "nwe_last_ray_evaluations",
            "nwe_set_shared_coarse", "nwe_get_shared_coarse", "nwe_last_coarse_launch",
-           "nwe_set_separate_passes", "nwe_get_separate_passes")
+           "nwe_set_separate_passes", "nwe_get_separate_passes",
+           "nwe_debug_set_work_queue", "nwe_debug_get_work_queue", "nwe_debug_get_work_queue_backfill", "nwe_debug_queue_grid", "nwe_debug_last_queue")
 
 
 class Outputs(C.Structure):
@@ -90,6 +91,11 @@ def load() -> C.CDLL:
         "nwe_last_coarse_launch": (I, [P, C.POINTER(F), C.POINTER(I64)]),
         "nwe_set_separate_passes": (I, [P, I]),
         "nwe_get_separate_passes": (I, [P]),
+        "nwe_debug_set_work_queue": (I, [P, I]),
+        "nwe_debug_get_work_queue": (I, [P]),
+        "nwe_debug_get_work_queue_backfill": (I, [P]),
+        "nwe_debug_queue_grid": (C.c_uint, [C.c_uint]),
+        "nwe_debug_last_queue": (I, [P, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(I)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

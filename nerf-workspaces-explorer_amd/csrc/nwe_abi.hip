@@ -1,5 +1,6 @@
 // C ABI of libnwe_hip.so (include/nwe.h): context, device resources, table upload, kernel launches.  Weight packing: nwe_pack.cpp.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -74,6 +75,14 @@ struct Slot {
     Event ev_share;
     bool has_share = false;
     int64_t share_rays = 0, evals_run = 0;
+    // work queue (nwe_debug_set_work_queue): the two ticket counters of the call, one per launch of its plan, zeroed on the
+    // caller's stream in front of the launches (last reader: prepare_slot); the low-priority stream the second launch of the
+    // hybrid plan backfills the first from, and the events of its fork and join; what nwe_debug_last_queue reports
+    DevBuf<unsigned> queue;
+    Stream side;
+    Event ev_fork, ev_join;
+    unsigned q_items[2] = {0, 0}, q_grid[2] = {0, 0};
+    bool side_used = false;
 };
 
 thread_local std::string g_create_error;
@@ -110,6 +119,8 @@ struct nwe_ctx {
     int share_k = 1;          // nwe_set_shared_coarse: 1 = off
     int separate = 0;         // nwe_set_separate_passes: 0 = off
     int decomposition = -1;   // nwe_debug_set_decomposition
+    int work_queue = -1;      // nwe_debug_set_work_queue; a new context takes NWE_WORK_QUEUE=0|1 from the environment
+    bool backfill = true;     // the hybrid plan's second launch on the slot's own stream; NWE_WORK_QUEUE_BACKFILL=0: behind the first
     int last_plan = -1;       // nwe_debug_last_plan
     unsigned long long* stamps = nullptr;   // nwe_debug_set_stamps
     const float *trn_t = nullptr, *trn_nc = nullptr, *trn_nf = nullptr, *trn_u = nullptr;   // nwe_set_train_tables, one call
@@ -399,10 +410,29 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         a.raw_in_c = a.noise_c = nullptr;   // the coarse launch's
         a.out.raw_coarse = a.out.weights_coarse = a.out.rgb_coarse = a.out.depth_coarse = a.out.acc_coarse = a.out.disp_coarse = nullptr;
     }
+    // Work queue: a call that is one fused plain MFMA kernel (early termination, the shared coarse pass and separate passes keep
+    // their launches as they are) may deal its workgroups from the slot's counters, and its hybrid plan's second launch may
+    // backfill the first from the slot's own stream: created on first use with the lowest priority there is, so that the
+    // quarter-size work items wait behind the packets until those run out.
+    const bool may_queue = ctx->work_queue != 0 && precision != NWE_PREC_F32 && !separate && !share && !(a.min_trans > 0.f) &&
+                           mfma_queues(a, ctx->decomposition, ctx->work_queue);   // a call that queues nothing pays nothing
+    if (may_queue) {
+        HIPCHK(ctx, slot.queue.reserve(2));
+        // every slot's stream with the first call that queues a launch, not one with each of the ring's first four: creating a stream takes
+        // milliseconds, which belong to a context's first frame and to no later one
+        for (Slot& s : ctx->slots) {
+            if (!ctx->backfill || s.side) continue;
+            int least = 0, greatest = 0;
+            HIPCHK(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
+            HIPCHK(ctx, hipStreamCreateWithPriority(&s.side.h, hipStreamNonBlocking, least));
+            for (Event* e : {&s.ev_fork, &s.ev_join}) HIPCHK(ctx, hipEventCreateWithFlags(&e->h, hipEventDisableTiming));
+        }
+    }
     // the descriptors of the coarse and of the fine launch: (coarse, fine) for one fused kernel, its own network twice otherwise
     const NetMfma &prod_f = separate ? nc.mf : nf.mf, &cons_c = separate ? nf.mf : nc.mf;
     const int rc = record_launch(ctx, slot, stream, [&]() -> int {
         slot.has_mid = false; slot.rays_first = slot.rays_total = a.n_rays;
+        slot.q_items[0] = slot.q_items[1] = slot.q_grid[0] = slot.q_grid[1] = 0; slot.side_used = false;
         slot.term = a.min_trans > 0.f;
         slot.evals_full = a.n_rays * (int64_t)(a.n_samples + (a.n_importance > 0 ? a.n_samples + a.n_importance : 0));
         slot.evals_run = coarse_launch ? prod.n_rays * a.n_samples + a.n_rays * (int64_t)(a.n_samples + a.n_importance) : slot.evals_full;
@@ -424,9 +454,21 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         }
         LaunchInfo info;
         info.mid = slot.ev_mid;
-        if (!launch_render_mfma(a, cons_c, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info))
-            return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
+        if (may_queue) {
+            HIPCHK(ctx, hipMemsetAsync(slot.queue.get(), 0, 2 * sizeof(unsigned), stream));
+            info.queue = slot.queue.get(); info.queue_mode = ctx->work_queue;
+            info.side = slot.side; info.fork = slot.ev_fork; info.join = slot.ev_join;
+        }
+        if (!launch_render_mfma(a, cons_c, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info)) {
+            if (!info.side_used) return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
+            // the side launch is queued and the caller's stream could not be made to wait for it: nothing of this call may
+            // still run when the call returns its error
+            (void)hipStreamSynchronize(slot.side);
+            return fail(ctx, NWE_ERR_HIP, std::string("work queue: joining the side stream: ") + hipGetErrorString(hipGetLastError()));
+        }
         ctx->last_plan = info.plan;
+        for (int i = 0; i < 2; ++i) { slot.q_items[i] = info.items[i]; slot.q_grid[i] = info.grid[i]; }
+        slot.side_used = info.side_used;
         slot.has_mid = info.mid_recorded; slot.rays_first = info.rays_first;
         return NWE_OK;
     });
@@ -603,6 +645,9 @@ int copy_out(const std::vector<T>* v, void* host_dst, int64_t count) {
 template <class Set>
 int set_on(nwe_ctx* c, Set&& set) { if (!c) return NWE_ERR_INVALID; set(); return NWE_OK; }
 
+// The least nwe_last_launch_parts reports for a part, in ms: the 10 ns step of the event timer
+constexpr float kMinPartMs = 1e-5f;
+
 // The most recent recorded render launch (nwe_last_kernel_ms, nwe_last_launch_parts), or null
 const Slot* last_render(const nwe_ctx* c) { return c->host_only || c->last_slot < 0 || !c->slots[c->last_slot].used ? nullptr : &c->slots[c->last_slot]; }
 
@@ -615,6 +660,10 @@ int nwe_create(nwe_ctx** out, int device) {
     nwe_ctx* c = new nwe_ctx();
     c->device = device;
     c->host_only = device < 0;
+    if (const char* e = std::getenv("NWE_WORK_QUEUE"))   // the default of a new context: A/B timing on one library
+        if ((e[0] == '0' || e[0] == '1') && !e[1]) c->work_queue = e[0] - '0';
+    if (const char* e = std::getenv("NWE_WORK_QUEUE_BACKFILL"))   // A/B timing of the queue with and without the backfill
+        if (e[0] == '0' && !e[1]) c->backfill = false;
     if (!c->host_only) {
         const hipError_t e = hipSetDevice(device);
         if (e != hipSuccess) { delete c; return fail(nullptr, NWE_ERR_HIP, std::string("nwe_create: ") + hipGetErrorString(e)); }
@@ -784,6 +833,10 @@ int nwe_last_launch_parts(nwe_ctx* c, float* ms2, int64_t* rays2) {
     if (s->has_mid) {
         HIPCHK(c, hipEventElapsedTime(&ms2[0], begin, s->ev_mid));
         HIPCHK(c, hipEventElapsedTime(&ms2[1], s->ev_mid, s->ev1));
+        // begin, ev_mid and ev1 lie on the caller's stream in this order, also when the second launch runs on the side stream
+        // (ev1 behind the join), so no part is negative; one that is below the timer's step is reported as that step, never as 0
+        // (the sum then exceeds nwe_last_kernel_ms by less than that step)
+        for (int i = 0; i < 2; ++i) ms2[i] = std::max(ms2[i], kMinPartMs);
     } else {
         HIPCHK(c, hipEventElapsedTime(&ms2[0], begin, s->ev1));
     }
@@ -832,6 +885,24 @@ int nwe_debug_set_raw(nwe_ctx* c, const float* raw_coarse_dev, const float* raw_
 int nwe_debug_set_coarse_weights(nwe_ctx* c, const float* weights_dev) { return set_on(c, [&] { c->dbg_w = weights_dev; }); }
 int nwe_debug_set_fold(nwe_ctx* c, int on) { return set_on(c, [&] { c->fold = on ? 1 : 0; }); }
 int nwe_debug_set_decomposition(nwe_ctx* c, int mode) { return set_on(mode < -1 || mode > 2 ? nullptr : c, [&] { c->decomposition = mode; }); }
+int nwe_debug_set_work_queue(nwe_ctx* c, int mode) { return set_on(mode < -1 || mode > 1 ? nullptr : c, [&] { c->work_queue = mode; }); }
+int nwe_debug_get_work_queue(const nwe_ctx* c) { return c ? c->work_queue : -2; }
+int nwe_debug_get_work_queue_backfill(const nwe_ctx* c) { return c ? (c->backfill ? 1 : 0) : -1; }
+unsigned nwe_debug_queue_grid(unsigned items) { return queue_grid(items); }
+int nwe_debug_last_queue(nwe_ctx* c, unsigned* items2, unsigned* grid2, unsigned* taken2, int* side_stream) {
+    if (!c || !items2 || !grid2 || !taken2) return NWE_ERR_INVALID;
+    for (int i = 0; i < 2; ++i) items2[i] = grid2[i] = taken2[i] = 0;
+    if (side_stream) *side_stream = 0;
+    const Slot* s = last_render(c);
+    if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
+    ON_DEVICE(c);
+    HIPCHK(c, hipEventSynchronize(s->ev1));
+    unsigned taken[2] = {0, 0};
+    if (s->q_grid[0] || s->q_grid[1]) HIPCHK(c, hipMemcpy(taken, s->queue.get(), sizeof(taken), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 2; ++i) { items2[i] = s->q_items[i]; grid2[i] = s->q_grid[i]; taken2[i] = s->q_grid[i] ? taken[i] : 0; }
+    if (side_stream) *side_stream = s->side_used ? 1 : 0;
+    return NWE_OK;
+}
 int nwe_debug_set_stamps(nwe_ctx* c, unsigned long long* per_wave_dev) { return set_on(c, [&] { c->stamps = per_wave_dev; }); }
 int nwe_set_white_background(nwe_ctx* c, int on) { return set_on(c, [&] { c->white_bkgd = on ? 1 : 0; }); }
 int nwe_set_early_termination(nwe_ctx* c, float min_transmittance) {

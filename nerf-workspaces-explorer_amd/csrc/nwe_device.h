@@ -23,6 +23,7 @@ struct RenderArgs {
     // ray source: either precomputed rays [n_rays,11] or pinhole poses
     const float* rays;       // device, may be null -> generate from poses
     int ray_cols;            // columns of `rays`: 11, or 8 for networks without view directions (rays.py:22-30)
+    unsigned queue_items;    // a queued launch (`queue` below): its work items; in the padding in front of the pointer
     const float* poses;      // device, n_poses x 16 (row-major c2w)
     int64_t n_rays;          // total rays of the call
     int64_t ray_first;       // first ray of THIS launch (a call may be split into launches with different decompositions)
@@ -57,8 +58,16 @@ struct RenderArgs {
     union {
         unsigned long long* evals;   // ray evaluations executed, summed over the launch's waves (nwe_last_ray_evaluations)
         float* share_w;              // coarse weights of the call's representatives, sample-major: [n_samples][n_rep]
+        // Work queue (nwe_debug_set_work_queue), read by the plain MFMA kernels only - the terminating and the sharing ones
+        // have the slot taken.  Null: workgroup b renders work item b.  Else a zeroed counter: every workgroup takes a ticket
+        // from it and renders that work item, or nothing when the ticket is not below queue_items.
+        unsigned* queue;
     };
 };
+static_assert(sizeof(RenderArgs) == 360, "RenderArgs must not grow: every kernel's argument offsets and scalar loads depend on it");
+
+// Diagnostic builds (-DNWE_STAMPS): uint64 words of a wave's stamp row (include/nwe.h, nwe_debug_set_stamps).
+constexpr int kStampWords = 14;
 
 constexpr int kShareOff = 0, kShareProducer = 1, kShareConsumer = 2;
 __host__ __device__ inline int share_role(const RenderArgs& a) { return a.share & 0xff; }

@@ -19,12 +19,29 @@ bool mfma_supported(int D, int W, int in_xyz, int in_dir, int skip, int form);
 // last round as 1 in a second launch (bit-identical results)
 // *info (may be null): in, `mid` = an event to record between the two launches of plan 2 (or null); out, the plan taken
 // (0 / 1 / 2 as above) and the rays the first launch got (all of them unless plan 2)
+// Work queue (nwe_debug_set_work_queue; plain kernels only, a terminating or sharing launch stays static): in, `queue` = two
+// zeroed device counters, one per launch of the plan, or null, and queue_mode: -1 = queue a launch with more workgroups than the
+// device has CUs, 1 = every launch; out, per launch its work items and its grid (0, 0 = not queued).  With a queue the second
+// launch of plan 2 goes to `side` (in: a low-priority stream, with `fork` and `join` events of the caller's; all three or
+// none), which starts behind `fork` on the caller's stream in front of the first launch and which the caller's stream joins
+// behind the second; out, side_used.  false with a side launch queued: the join could not be queued, *info says side_used.
 struct LaunchInfo {
     hipEvent_t mid = nullptr;
     int plan = -1;
     int64_t rays_first = 0;
     bool mid_recorded = false;
+    unsigned* queue = nullptr;
+    int queue_mode = -1;
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    unsigned items[2] = {0, 0}, grid[2] = {0, 0};
+    bool side_used = false;
 };
+// true if a plain launch of `a` under this decomposition and queue mode deals at least one launch of its plan from a queue: the
+// same plan and the same size test as launch_render_mfma's, for the caller that has to provide the counters and the stream
+bool mfma_queues(const RenderArgs& a, int decomposition, int queue_mode);
+// workgroups of a launch of `rays` rays (split: one packet per workgroup)
+unsigned mfma_workgroups(int64_t rays, bool split);
 bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& nf, bool three_pass, int decomposition, hipStream_t stream,
                         LaunchInfo* info);
 

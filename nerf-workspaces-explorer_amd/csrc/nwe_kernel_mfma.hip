@@ -43,14 +43,22 @@ bool mfma_is_lean(const RenderArgs& a) { return is_lean(a); }
 
 int mfma_max_samples() { return kSplitMaxSamples; }
 
+static int device_cus() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus > 0 ? cus : 256;
+}
+
+unsigned mfma_workgroups(int64_t rays, bool split) {
+    const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
+    return (unsigned)((rays + per_wg - 1) / per_wg);
+}
+
 // The plan of a call: 0 = all packets, 1 = all sample-split, 2 = hybrid; *full = the rays of the hybrid plan's first launch.
-static int plan_launch(const RenderArgs& a, int decomposition, int64_t* full_out) {
+static int plan_launch(const RenderArgs& a, int decomposition, int cus, int64_t* full_out) {
     // One workgroup per CU at a time, so a launch costs (rounds of workgroups) x (sample iterations per workgroup).  Three
     // plans, same arithmetic: all packets; all sample-split (finer units, ~6 % overhead: redundant sequential part and
     // exchange); or the full rounds as packets and the ragged last round sample-split in a second launch behind it.
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
     const int64_t rays_wg = kWaves * kRaysPerWave;
     // the sample iterations this launch runs: both passes, or - shared coarse pass - the producer's coarse pass alone, the
     // consumer's fine pass alone
@@ -71,6 +79,15 @@ static int plan_launch(const RenderArgs& a, int decomposition, int64_t* full_out
     if (a.n_samples > kPacketMaxSamples) plan = 1;  // only the single-packet workgroup has LDS for that many coarse weights
     *full_out = full;
     return plan;
+}
+
+bool mfma_queues(const RenderArgs& a, int decomposition, int queue_mode) {
+    if (queue_mode == 0) return false;
+    int64_t full = 0;
+    const int cus = device_cus();
+    const int plan = plan_launch(a, decomposition, cus, &full);
+    const auto queued = [&](int64_t rays, bool split) { return rays > 0 && (queue_mode == 1 || mfma_workgroups(rays, split) > (unsigned)cus); };
+    return plan == 2 ? queued(full, false) || queued(a.n_rays - full, true) : queued(a.n_rays, plan == 1);
 }
 
 bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& nf, bool three_pass, int decomposition, hipStream_t stream,
@@ -106,14 +123,45 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
     if (!launch) return false;
     if (nc.n_chunks != n_chunks || (a.n_importance > 0 && nf.n_chunks != n_chunks)) return false;   // the kernel copies n_chunks bias rows
     int64_t full = 0;
-    const int plan = plan_launch(a, decomposition, &full);
+    const int cus = device_cus();
+    const int plan = plan_launch(a, decomposition, cus, &full);
     if (info) { info->plan = plan; info->rays_first = plan == 2 ? full : a.n_rays; info->mid_recorded = false; }
+    // Dealing: the hardware hands workgroup b of a launch to XCD (b + c) mod 8, an eighth of the launch each
+    // whatever pace an XCD runs at.  A queued launch deals tickets instead (render_mfma_kernel), from a counter of its own.
+    // i = the launch of the plan; returns the arguments that launch takes.
+    const bool may_queue = info && info->queue && !term && !share;
+    const auto dealt = [&](int i, int64_t rays, bool split) {
+        RenderArgs q = a;
+        const unsigned wgs = mfma_workgroups(rays, split);
+        if (may_queue && rays > 0 && (info->queue_mode == 1 || wgs > (unsigned)cus)) {
+            q.queue = info->queue + i;
+            info->items[i] = wgs; info->grid[i] = queue_grid(wgs);
+        }
+        return q;
+    };
     if (plan == 2) {
-        launch(a, nc, nf, three_pass, false, 0, full, stream);
+        const RenderArgs first = dealt(0, full, false);
+        RenderArgs second = dealt(1, a.n_rays - full, true);
+#ifdef NWE_STAMPS   // the second launch's stamp rows lie behind the first's: rows are indexed by work item within a launch
+        if (second.stamps) second.stamps += (size_t)mfma_workgroups(full, false) * kWaves * kStampWords;
+#endif
+        // With queues on, the second launch backfills the first: it goes to the side stream, which forks from the caller's
+        // stream in front of the first launch, so that its quarter-size work items are there for a CU the moment the packet
+        // items run out; the side stream's low priority keeps them behind the packets until then.
+        hipStream_t second_stream = stream;
+        if (info && info->side && info->fork && info->join && (first.queue || second.queue) &&
+            hipEventRecord(info->fork, stream) == hipSuccess && hipStreamWaitEvent(info->side, info->fork, 0) == hipSuccess)
+            second_stream = info->side;
+        launch(first, nc, nf, three_pass, false, 0, full, stream);
         if (info && info->mid) info->mid_recorded = hipEventRecord(info->mid, stream) == hipSuccess;   // the two launches timed apart
-        launch(a, nc, nf, three_pass, true, full, a.n_rays - full, stream);
+        launch(second, nc, nf, three_pass, true, full, a.n_rays - full, second_stream);
+        if (second_stream != stream) {
+            info->side_used = true;
+            // the caller's stream goes on when the side launch has finished; if that cannot be queued the caller is told
+            if (hipEventRecord(info->join, second_stream) != hipSuccess || hipStreamWaitEvent(stream, info->join, 0) != hipSuccess) return false;
+        }
     } else {
-        launch(a, nc, nf, three_pass, plan == 1, 0, a.n_rays, stream);
+        launch(dealt(0, a.n_rays, plan == 1), nc, nf, three_pass, plan == 1, 0, a.n_rays, stream);
     }
     return true;
 }

@@ -142,6 +142,24 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
     using SM = Smem<W, D, SPLIT>;
     __shared__ __attribute__((aligned(16))) char smem[SM::TOTAL + (TERM && !SPLIT ? kVoteBytes : 0)];
 
+    // The work item: the workgroup's own index, or - a queued launch (RenderArgs::queue; DESIGN.md section 5, "Dealing") - a
+    // ticket, which thread 0 takes as the kernel's first act and publishes through the first word of the chunk buffers: nothing
+    // else touches them before the barrier behind the table copies.  A ticket that is not below the launch's items leaves at
+    // once, all threads alike.  Nothing waits for another workgroup; the counter is the only state workgroups share.
+    static_assert(SM::CHUNKS >= 4 && SM::BOFF >= SM::CHUNKS && SM::WOFF > SM::BOFF && SM::TOFF > SM::BOFF && SM::GOFF > SM::BOFF,
+                  "the ticket's word lies in the chunk buffers, below every region the prologue writes in front of its barrier");
+    unsigned item = blockIdx.x;
+    if constexpr (!TERM && !SHARE) {
+        if (a.queue) {
+            unsigned* s_item = reinterpret_cast<unsigned*>(smem);
+            if (threadIdx.x == 0) *s_item = atomicAdd(a.queue, 1u);
+            __syncthreads();
+            const unsigned ticket = *s_item;            // tested as the vector value it is read as: with the test behind the
+            if (ticket >= a.queue_items) return;        // readfirstlane the full sample-split 8x256 kernel spills 12 bytes
+            item = __builtin_amdgcn_readfirstlane(ticket);
+        }
+    }
+
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5;
@@ -161,7 +179,7 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
         if (ni > 0) s_bias[SM::BIAS_BYTES / 4 + i] = nf.bias[i];
     }
 
-    const int64_t packet = SPLIT ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * kWaves + wave;
+    const int64_t packet = SPLIT ? (int64_t)item : (int64_t)item * kWaves + wave;
     const int64_t ridx64 = a.ray_first + packet * kRaysPerWave + (lane & 31);
     const bool lane_live = ridx64 < a.n_rays && half == 0;    // this lane stores per-sample outputs of its ray
     const bool live = lane_live && (!SPLIT || wave == 0);      // ... and the per-ray results (every wave holds them in SPLIT mode)
@@ -208,6 +226,8 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
     fs.cd.t_tab = s_t; fs.cd.omt_tab = s_omt; fs.cd.ns = ns;
     fs.cd.jitter = a.t_rand; fs.cd.row = row;                         // training-mode forward: host-drawn random rows
     fs.u_rand = a.u_rand;
+    // Up to this barrier nothing may write the chunk buffers (no LDS-DMA piece, no priming): their first word carries a queued
+    // launch's ticket until every wave has read it, which this barrier is the first to guarantee.
     __syncthreads();
 
     Composite comp;
@@ -412,10 +432,15 @@ __global__ void __launch_bounds__(256) render_mfma_kernel(RenderArgs a_in, NetMf
     if (flags && a.out.flags) atomicOr(a.out.flags, flags);
 #ifdef NWE_STAMPS
     if (a.stamps && lane == 0) {   // diagnostic build only: a buffer no other code reads
-        unsigned long long* o = a.stamps + ((size_t)blockIdx.x * kWaves + wave) * 10;
+        unsigned long long* o = a.stamps + ((size_t)item * kWaves + wave) * kStampWords;   // by work item: however it was dealt
         o[0] = st_enc; o[1] = st_sync; o[2] = st_mlp; o[3] = st_comp; o[4] = __builtin_amdgcn_s_memtime() - st_begin;
         o[5] = wk.st_pre; o[6] = wk.st_wait; o[7] = wk.st_post;
-        o[8] = __builtin_amdgcn_s_memrealtime() - st_real; o[9] = st_begin;
+        const unsigned long long st_real_end = __builtin_amdgcn_s_memrealtime();
+        o[8] = st_real_end - st_real; o[9] = st_begin;
+        // where and when the wave ran: HW_REG_XCC_ID (register 20; the XCD is its low four bits) with HW_REG_HW_ID (register 4:
+        // wave, SIMD, CU, shader array and engine) above it, the work item, and the wave's span on the 100 MHz clock
+        o[10] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) | (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32;
+        o[11] = item; o[12] = st_real; o[13] = st_real_end;
     }
 #endif
 }
@@ -431,12 +456,15 @@ void launch_one(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_p
     a.ray_first = ray_first;
     const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
     const unsigned blocks = (unsigned)((rays + per_wg - 1) / per_wg);
+    // a queued launch (a.queue: a zeroed counter of this launch's own) deals its `blocks` work items to a larger grid
+    if (a.queue) a.queue_items = blocks;
+    const unsigned grid = a.queue ? queue_grid(blocks) : blocks;
 #define NWE_KERNEL(X3_, SPLIT_, LEAN_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, LEAN_>
     void (*const kernels[8])(RenderArgs, NetMfma, NetMfma) = {   // index: 4 single-pass + 2 packets + 1 not lean
         NWE_KERNEL(true, true, true),  NWE_KERNEL(true, true, false),  NWE_KERNEL(true, false, true),  NWE_KERNEL(true, false, false),
         NWE_KERNEL(false, true, true), NWE_KERNEL(false, true, false), NWE_KERNEL(false, false, true), NWE_KERNEL(false, false, false)};
 #undef NWE_KERNEL
-    hipLaunchKernelGGL(kernels[(three_pass ? 0 : 4) + (split ? 0 : 2) + (is_lean(a) ? 0 : 1)], dim3(blocks), dim3(256), 0, stream, a, nc, nf);
+    hipLaunchKernelGGL(kernels[(three_pass ? 0 : 4) + (split ? 0 : 2) + (is_lean(a) ? 0 : 1)], dim3(grid), dim3(256), 0, stream, a, nc, nf);
 }
 
 // Whether a shape has the terminating kernels (TERM): the product formulations do, kFormReference is a comparison path.

@@ -294,6 +294,23 @@ class Renderer:
         """Test hook: the decomposition the last MFMA launch took (0 packets, 1 sample split, 2 packets + split rest)."""
         return int(self._lib.nwe_debug_last_plan(self._ctx))
 
+    def debug_set_work_queue(self, mode: int) -> None:
+        """How a plain MFMA launch's workgroups get their work (include/nwe.h; bit-identical results): -1 = tickets from a queue
+        when the launch has more workgroups than the device has CUs (the default, or what NWE_WORK_QUEUE set when the renderer
+        was created), 0 = the hardware's static dealing, 1 = queue every launch."""
+        self._check(self._lib.nwe_debug_set_work_queue(self._ctx, int(mode)), "nwe_debug_set_work_queue")
+
+    def debug_get_work_queue(self) -> int:
+        return int(self._lib.nwe_debug_get_work_queue(self._ctx))
+
+    def debug_last_queue(self):
+        """{"items", "grid", "taken": (first launch, second launch), "side_stream": bool} of the last render: the work items of
+        each launch of its plan, its grid and the tickets taken (zeros = not queued), and whether the hybrid plan's second
+        launch ran on the renderer's own low-priority stream."""
+        items, grid, taken, side = (C.c_uint * 2)(), (C.c_uint * 2)(), (C.c_uint * 2)(), C.c_int(0)
+        self._check(self._lib.nwe_debug_last_queue(self._ctx, items, grid, taken, C.byref(side)), "nwe_debug_last_queue")
+        return {"items": tuple(items), "grid": tuple(grid), "taken": tuple(taken), "side_stream": bool(side.value)}
+
     def set_white_background(self, on: bool) -> None:
         """rendering.white_background (model_utils.py:97-98): rgb += 1 - acc on every rgb output."""
         self._check(self._lib.nwe_set_white_background(self._ctx, 1 if on else 0), "nwe_set_white_background")
@@ -439,6 +456,10 @@ class TiledRenderer:
     def debug_set_fold(self, on: bool) -> None:
         for p in self.parts:
             p.debug_set_fold(on)
+
+    def debug_set_work_queue(self, mode: int) -> None:
+        for p in self.parts:
+            p.debug_set_work_queue(mode)
 
     def set_early_termination(self, min_transmittance: float) -> None:
         for p in self.parts:
