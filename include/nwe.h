@@ -397,7 +397,22 @@ int nwe_last_ray_evaluations(nwe_ctx *ctx, int64_t *out2);
  *   u_sorted     [n_rays, n_importance]             the uniform numbers of sample_pdf(det=False) (nerf/rays/rays.py:98),
  *                                                   sorted ascending per ray: sample_pdf is element-wise in u and the
  *                                                   reference sorts the union of depths afterwards (:580), so the order of
- *                                                   u does not change any output */
+ *                                                   u does not change any output
+ * A table row belongs to its ray: row i of every table is read for ray i of the call, whatever packet, workgroup, work item or
+ * launch of the call's plan the ray lands in, so a call over rays [a, b) of a larger call with rows [a, b) of its tables gives
+ * rows [a, b) of the larger call's outputs bit for bit.  A noise table of 0.0 and a u_sorted equal to the u of nwe_set_sampling
+ * give the inference result bit for bit.  With n_importance == 0, noise_fine and u_sorted are not read.
+ * Tables together with the one-shot hooks above - a hook replaces its stage and nothing else, in both kernels:
+ *   nwe_debug_set_coarse_weights  the coarse pass does not run, so noise_coarse has nothing to act on (the call equals the call
+ *                                 without it bit for bit); t_rand still defines the coarse depths and with them the bin edges
+ *                                 z_mid and the coarse members of z_fine; u_sorted is used as ever;
+ *   nwe_debug_set_raw             noise_coarse / noise_fine are added to the CALLER's sigma_raw of that pass before the ReLU;
+ *                                 t_rand and u_sorted are used as ever (the depths enter the compositing and z_fine);
+ *   nwe_debug_set_fine_depths     the fine pass runs at the caller's depths with noise_fine; the importance samples feed nothing
+ *                                 into it, so rgb / depth / acc / raw_fine / z_fine do not depend on u_sorted, but z_std and
+ *                                 sample_cond / sample_amp / sample_switch still describe the call's OWN importance samples
+ *                                 (drawn with u_sorted, from the call's coarse weights), not the caller's depths.
+ * (tests/train_domain.py lists the cases.) */
 int nwe_set_train_tables(nwe_ctx *ctx, const float *t_rand_dev, const float *noise_coarse_dev, const float *noise_fine_dev,
                          const float *u_sorted_dev);
 
