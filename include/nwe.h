@@ -234,7 +234,8 @@ float nwe_last_kernel_ms(nwe_ctx *ctx);
  * ms2[0], rays2[0]: the first (or only) launch; ms2[1], rays2[1]: the second, -1 / 0 if there was none.  Blocks like
  * nwe_last_kernel_ms.  With the work queue on (nwe_debug_set_work_queue, the default for frames larger than the device) the
  * second launch runs BESIDE the first: ms2[1] is then how long the frame ran beyond its first launch, not the second kernel's
- * time, often next to nothing: a rate computed from it means nothing.  The parts are positive (never 0: a part below the
+ * time, often next to nothing: a rate computed from it means nothing.  On the tail path (nwe_debug_set_work_queue) the first launch
+ * renders the second's rays as well: ms2[0] is the whole frame, ms2[1] an empty launch, rays2 the plan's split all the same.  The parts are positive (never 0: a part below the
  * timer's step of 1e-5 ms is reported as that step) and add up to nwe_last_kernel_ms to within that step. */
 int nwe_last_launch_parts(nwe_ctx *ctx, float *ms2, int64_t *rays2);
 
@@ -441,7 +442,19 @@ int nwe_debug_last_plan(const nwe_ctx *ctx);
  * nwe_last_launch_parts under a backfilled hybrid plan: ms2[0] is the packets launch as before; ms2[1] is how long the frame
  * ran BEYOND its first launch, not the time of the second launch (which ran beside the first), so a rate computed from it
  * means nothing.  Both stay positive and add up to nwe_last_kernel_ms to within the timer's step: the three events lie on the
- * caller's stream in order, the last behind the join, and a part below that step is reported as the step (1e-5 ms). */
+ * caller's stream in order, the last behind the join, and a part below that step is reported as the step (1e-5 ms).
+ * The tail path: a lean call under the hybrid plan whose packets launch is queued, with the backfill on, and whose surplus
+ * workgroups - nwe_debug_queue_grid(items) - items of the packets launch - are at least as many as the sample-split items, renders
+ * those items in the packets launch itself: a surplus workgroup, instead of leaving at once, takes a number from a third counter
+ * and renders that split item.  The surplus is placed when the packet tickets have run out, so the split items sit at the
+ * end of the frame, on the CUs that come free first.  The second launch stays - same grid, counter and stream, now forked
+ * behind the first launch - and renders the items whose number is not below the third counter's final value: none.  Nothing
+ * waits for anything.  items, grid, taken and side_stream of nwe_debug_last_queue are what they are without the path.
+ * nwe_last_launch_parts then: ms2[0] is the packets launch INCLUDING the split items, ms2[1] the few microseconds of the emptied
+ * second launch; rays2 is unchanged.  NWE_WORK_QUEUE_TAIL=0 in the environment keeps a new context off the path (A/B timing).  There
+ * is NO run-time switch: the variable is read once, by nwe_create, and holds for the context's life (nwe_debug_get_work_queue_tail);
+ * NWE_WORK_QUEUE_BACKFILL=0 does so too.  Every other call - not lean, a smaller surplus, early termination, shared coarse pass,
+ * separate passes - runs the launches it ran without the path. */
 int nwe_debug_set_work_queue(nwe_ctx *ctx, int mode);
 int nwe_debug_get_work_queue(const nwe_ctx *ctx);               /* -2 for a null context */
 int nwe_debug_get_work_queue_backfill(const nwe_ctx *ctx);      /* 1, or 0 under NWE_WORK_QUEUE_BACKFILL=0; -1 for a null context */
@@ -451,6 +464,14 @@ unsigned nwe_debug_queue_grid(unsigned items);
  * of its ticket counter (= grid when every workgroup took one); zeros = not queued.  *side_stream (may be NULL): 1 if the
  * second launch ran on the context's low-priority stream.  Waits for the launch, like the timing calls. */
 int nwe_debug_last_queue(nwe_ctx *ctx, unsigned *items2, unsigned *grid2, unsigned *taken2, int *side_stream);
+int nwe_debug_get_work_queue_tail(const nwe_ctx *ctx);          /* 1, or 0 under NWE_WORK_QUEUE_TAIL=0; -1 for a null context */
+/* *stolen: the sample-split items that the packets launch of the most recent recorded render launch rendered in its tail (all
+ * of them when the tail path was taken), 0 when it was not.  Waits for the launch, like the timing calls. */
+int nwe_debug_last_tail(nwe_ctx *ctx, unsigned *stolen);
+/* *rendered: the sample-split items that the SECOND launch of that render launch rendered on the tail path (the ones whose number
+ * was not below the third counter's final value), 0 when the path was not taken.  stolen + rendered == the plan's split items
+ * says that every item was rendered exactly once; with the path's condition (the surplus covers every item) rendered is 0. */
+int nwe_debug_last_tail_rest(nwe_ctx *ctx, unsigned *rendered);
 
 /* Diagnostic builds only (make -C csrc stamps): DEVICE buffer of 14 uint64 per wave that a -DNWE_STAMPS build of the MFMA
  * kernel fills with s_memtime cycle sums (tools/stamp_run.py); the product build never touches it.  NULL switches it off.

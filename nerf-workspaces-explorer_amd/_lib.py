@@ -25,7 +25,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_set_early_termination", "nwe_get_early_termination", "nwe_last_ray_evaluations",
            "nwe_set_shared_coarse", "nwe_get_shared_coarse", "nwe_last_coarse_launch",
            "nwe_set_separate_passes", "nwe_get_separate_passes",
-           "nwe_debug_set_work_queue", "nwe_debug_get_work_queue", "nwe_debug_get_work_queue_backfill", "nwe_debug_queue_grid", "nwe_debug_last_queue")
+           "nwe_debug_set_work_queue", "nwe_debug_get_work_queue", "nwe_debug_get_work_queue_backfill", "nwe_debug_queue_grid", "nwe_debug_last_queue",
+           "nwe_debug_get_work_queue_tail", "nwe_debug_last_tail", "nwe_debug_last_tail_rest")
 
 
 class Outputs(C.Structure):
@@ -96,6 +97,9 @@ def load() -> C.CDLL:
         "nwe_debug_get_work_queue_backfill": (I, [P]),
         "nwe_debug_queue_grid": (C.c_uint, [C.c_uint]),
         "nwe_debug_last_queue": (I, [P, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(I)]),
+        "nwe_debug_get_work_queue_tail": (I, [P]),
+        "nwe_debug_last_tail": (I, [P, C.POINTER(C.c_uint)]),
+        "nwe_debug_last_tail_rest": (I, [P, C.POINTER(C.c_uint)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -83,6 +83,8 @@ struct Slot {
     Event ev_fork, ev_join;
     unsigned q_items[2] = {0, 0}, q_grid[2] = {0, 0};
     bool side_used = false;
+    // the tail path (nwe_debug_last_tail): the split items of a launch that took it, whose third counter lies behind the two
+    unsigned tail_items = 0;
 };
 
 thread_local std::string g_create_error;
@@ -121,6 +123,7 @@ struct nwe_ctx {
     int decomposition = -1;   // nwe_debug_set_decomposition
     int work_queue = -1;      // nwe_debug_set_work_queue; a new context takes NWE_WORK_QUEUE=0|1 from the environment
     bool backfill = true;     // the hybrid plan's second launch on the slot's own stream; NWE_WORK_QUEUE_BACKFILL=0: behind the first
+    bool tail = true;         // the hybrid plan's split items in the packets launch's tail; NWE_WORK_QUEUE_TAIL=0: as without it
     int last_plan = -1;       // nwe_debug_last_plan
     unsigned long long* stamps = nullptr;   // nwe_debug_set_stamps
     const float *trn_t = nullptr, *trn_nc = nullptr, *trn_nf = nullptr, *trn_u = nullptr;   // nwe_set_train_tables, one call
@@ -417,7 +420,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
     const bool may_queue = ctx->work_queue != 0 && precision != NWE_PREC_F32 && !separate && !share && !(a.min_trans > 0.f) &&
                            mfma_queues(a, ctx->decomposition, ctx->work_queue);   // a call that queues nothing pays nothing
     if (may_queue) {
-        HIPCHK(ctx, slot.queue.reserve(2));
+        HIPCHK(ctx, slot.queue.reserve(4));   // the two launches' tickets, the tail path's, the items its second launch rendered
         // every slot's stream with the first call that queues a launch, not one with each of the ring's first four: creating a stream takes
         // milliseconds, which belong to a context's first frame and to no later one
         for (Slot& s : ctx->slots) {
@@ -432,7 +435,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
     const NetMfma &prod_f = separate ? nc.mf : nf.mf, &cons_c = separate ? nf.mf : nc.mf;
     const int rc = record_launch(ctx, slot, stream, [&]() -> int {
         slot.has_mid = false; slot.rays_first = slot.rays_total = a.n_rays;
-        slot.q_items[0] = slot.q_items[1] = slot.q_grid[0] = slot.q_grid[1] = 0; slot.side_used = false;
+        slot.q_items[0] = slot.q_items[1] = slot.q_grid[0] = slot.q_grid[1] = 0; slot.side_used = false; slot.tail_items = 0;
         slot.term = a.min_trans > 0.f;
         slot.evals_full = a.n_rays * (int64_t)(a.n_samples + (a.n_importance > 0 ? a.n_samples + a.n_importance : 0));
         slot.evals_run = coarse_launch ? prod.n_rays * a.n_samples + a.n_rays * (int64_t)(a.n_samples + a.n_importance) : slot.evals_full;
@@ -455,9 +458,10 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         LaunchInfo info;
         info.mid = slot.ev_mid;
         if (may_queue) {
-            HIPCHK(ctx, hipMemsetAsync(slot.queue.get(), 0, 2 * sizeof(unsigned), stream));
+            HIPCHK(ctx, hipMemsetAsync(slot.queue.get(), 0, 4 * sizeof(unsigned), stream));
             info.queue = slot.queue.get(); info.queue_mode = ctx->work_queue;
             info.side = slot.side; info.fork = slot.ev_fork; info.join = slot.ev_join;
+            info.tail = ctx->tail;
         }
         if (!launch_render_mfma(a, cons_c, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info)) {
             if (!info.side_used) return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
@@ -468,7 +472,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         }
         ctx->last_plan = info.plan;
         for (int i = 0; i < 2; ++i) { slot.q_items[i] = info.items[i]; slot.q_grid[i] = info.grid[i]; }
-        slot.side_used = info.side_used;
+        slot.side_used = info.side_used; slot.tail_items = info.tail_items;
         slot.has_mid = info.mid_recorded; slot.rays_first = info.rays_first;
         return NWE_OK;
     });
@@ -664,6 +668,8 @@ int nwe_create(nwe_ctx** out, int device) {
         if ((e[0] == '0' || e[0] == '1') && !e[1]) c->work_queue = e[0] - '0';
     if (const char* e = std::getenv("NWE_WORK_QUEUE_BACKFILL"))   // A/B timing of the queue with and without the backfill
         if (e[0] == '0' && !e[1]) c->backfill = false;
+    if (const char* e = std::getenv("NWE_WORK_QUEUE_TAIL"))       // A/B timing of the tail path on one library
+        if ((e[0] == '0' || e[0] == '1') && !e[1]) c->tail = e[0] == '1';
     if (!c->host_only) {
         const hipError_t e = hipSetDevice(device);
         if (e != hipSuccess) { delete c; return fail(nullptr, NWE_ERR_HIP, std::string("nwe_create: ") + hipGetErrorString(e)); }
@@ -903,6 +909,23 @@ int nwe_debug_last_queue(nwe_ctx* c, unsigned* items2, unsigned* grid2, unsigned
     if (side_stream) *side_stream = s->side_used ? 1 : 0;
     return NWE_OK;
 }
+int nwe_debug_get_work_queue_tail(const nwe_ctx* c) { return c ? (c->tail ? 1 : 0) : -1; }
+// which = 0: the split items the first launch rendered; 1: the ones the second launch rendered
+static int last_tail(nwe_ctx* c, unsigned* out, int which) {
+    if (!c || !out) return NWE_ERR_INVALID;
+    *out = 0;
+    const Slot* s = last_render(c);
+    if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
+    if (!s->tail_items) return NWE_OK;
+    ON_DEVICE(c);
+    HIPCHK(c, hipEventSynchronize(s->ev1));
+    unsigned word = 0;   // every surplus workgroup of the first launch took a number: the items it rendered are the numbers below tail_items
+    HIPCHK(c, hipMemcpy(&word, s->queue.get() + 2 + which, sizeof(word), hipMemcpyDeviceToHost));
+    *out = which == 0 ? std::min(word, s->tail_items) : word;
+    return NWE_OK;
+}
+int nwe_debug_last_tail(nwe_ctx* c, unsigned* stolen) { return last_tail(c, stolen, 0); }
+int nwe_debug_last_tail_rest(nwe_ctx* c, unsigned* rendered) { return last_tail(c, rendered, 1); }
 int nwe_debug_set_stamps(nwe_ctx* c, unsigned long long* per_wave_dev) { return set_on(c, [&] { c->stamps = per_wave_dev; }); }
 int nwe_set_white_background(nwe_ctx* c, int on) { return set_on(c, [&] { c->white_bkgd = on ? 1 : 0; }); }
 int nwe_set_early_termination(nwe_ctx* c, float min_transmittance) {

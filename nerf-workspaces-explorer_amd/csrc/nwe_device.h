@@ -36,7 +36,13 @@ struct RenderArgs {
     const float* z_fine_in;  // test hook: fine depths [n_rays, ns+ni] instead of importance sampling
     const float* raw_in_c;   // test hook: network outputs [n_rays, ns, 4] of the coarse pass instead of evaluating the MLP
     const float* raw_in_f;   // test hook: ... [n_rays, ns+ni, 4] of the fine pass
-    const float* w_in;       // test hook: coarse weights [n_rays, ns] instead of the coarse pass (its outputs are not written)
+    union {
+        const float* w_in;   // test hook: coarse weights [n_rays, ns] instead of the coarse pass (its outputs are not written)
+        // The tail kernel only (render_mfma_tail_kernel; its calls have no hook): the call's third counter, zeroed with the two
+        // of `queue`, from which the surplus workgroups of the packets launch take the plan's sample-split items.
+        // tail[1], zeroed with it, counts the items the second launch rendered.
+        unsigned* tail;
+    };
     // training-mode forward (nerf/training/nerf_replica_training_handler.py:553-580): random numbers drawn by the host
     // where the reference calls torch.rand / torch.randn, one row per ray of this call; each may be null (= inference)
     const float* t_rand;     // [n_rays, ns]      stratified jitter in [0,1)                 (:560-562)
@@ -53,7 +59,8 @@ struct RenderArgs {
     // shared coarse pass (nwe_set_shared_coarse): read by the sharing instantiations only, which a launch takes exactly if
     // share != 0: role | k << 8 (kShareProducer / kShareConsumer, the block edge in pixels).  It sits in the padding in front of
     // the pointer and the table shares the pointer's slot - the two modes exclude each other - so that the struct does not
-    // grow: the descriptors behind it keep their offsets, and every other kernel its instructions.
+    // grow: the descriptors behind it keep their offsets, and every other kernel its instructions.  The tail kernel (plain, never
+    // sharing) reads it as its role: kTailSecond marks the plan's second launch (nwe_mfma_render.h).
     int share;
     union {
         unsigned long long* evals;   // ray evaluations executed, summed over the launch's waves (nwe_last_ray_evaluations)

@@ -25,6 +25,9 @@ bool mfma_supported(int D, int W, int in_xyz, int in_dir, int skip, int form);
 // launch of plan 2 goes to `side` (in: a low-priority stream, with `fork` and `join` events of the caller's; all three or
 // none), which starts behind `fork` on the caller's stream in front of the first launch and which the caller's stream joins
 // behind the second; out, side_used.  false with a side launch queued: the join could not be queued, *info says side_used.
+// Tail path (render_mfma_tail_kernel): `queue` then has a third zeroed counter; in, `tail` = the caller allows it; out, tail_items =
+// the plan's split items if the path was taken - lean call, queued first launch whose surplus workgroups cover them all, tail
+// kernel built, side stream given - and 0 otherwise.  The side stream then forks behind the first launch, not in front of it.
 struct LaunchInfo {
     hipEvent_t mid = nullptr;
     int plan = -1;
@@ -36,6 +39,8 @@ struct LaunchInfo {
     hipEvent_t fork = nullptr, join = nullptr;
     unsigned items[2] = {0, 0}, grid[2] = {0, 0};
     bool side_used = false;
+    bool tail = false;
+    unsigned tail_items = 0;
 };
 // true if a plain launch of `a` under this decomposition and queue mode deals at least one launch of its plan from a queue: the
 // same plan and the same size test as launch_render_mfma's, for the caller that has to provide the counters and the stream

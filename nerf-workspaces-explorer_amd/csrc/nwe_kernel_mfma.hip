@@ -12,9 +12,17 @@ NWE_SHAPES(NWE_EXTERN_SHAPE_LAUNCHER)
 #ifndef NWE_ONLY_HEADLINE   // diagnostic builds hold no terminating kernels
 NWE_SHAPES(NWE_EXTERN_SHAPE_TERM_LAUNCHER)
 NWE_SHAPES(NWE_EXTERN_SHAPE_SHARE_LAUNCHER)
+NWE_SHAPES(NWE_EXTERN_SHAPE_TAIL_LAUNCHER)
+#define NWE_TAIL_BUILT(FORM_) tail_built(FORM_)
 #define NWE_TERM_BUILT(FORM_) term_built(FORM_)
 #define NWE_SHARE_BUILT(FORM_) share_built(FORM_)
 #else
+#ifdef NWE_DIAG_TAIL   // `make stamps` holds the headline shape's tail kernel (nwe_mfma_inst_tail_a.hip), the other diagnostic builds none
+NWE_SHAPES(NWE_EXTERN_SHAPE_TAIL_LAUNCHER)
+#define NWE_TAIL_BUILT(FORM_) tail_built(FORM_)
+#else
+#define NWE_TAIL_BUILT(FORM_) false
+#endif
 #define NWE_TERM_BUILT(FORM_) false
 #define NWE_SHARE_BUILT(FORM_) false
 #endif
@@ -95,7 +103,7 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
     if (a.n_importance > 0 && (nf.D != nc.D || nf.W != nc.W || nf.skip != nc.skip || nf.form != nc.form)) return false;
     if (a.n_samples > kSplitMaxSamples) return false;
     const int D = nc.D, W = nc.W, skip = nc.skip, form = nc.form;
-    decltype(&launch_one<256, 8, 4, kFormFolded>) launch = nullptr;
+    decltype(&launch_one<256, 8, 4, kFormFolded>) launch = nullptr, launch_tail = nullptr;
     int n_chunks = -1;
     // early termination (a.min_trans > 0): the shape's terminating kernels, which exist for lean calls only (nwe_abi.hip refuses
     // the rest by name before it gets here)
@@ -108,18 +116,26 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
     const bool share = a.share != kShareOff && is_lean(a);
     if (a.share != kShareOff && !share && (term || (share_role(a) == kShareProducer ? a.n_importance != 0 : !a.w_in))) return false;
     if (share && (term || !a.share_w || a.n_importance <= 0 || !mfma_share_supported(D, W, skip, form))) return false;
+#define NWE_PICK_TAIL(W_, D_, SKIP_, FORM_) \
+    if constexpr (NWE_TAIL_BUILT(FORM_)) launch_tail = launch_one_tail<W_, D_, SKIP_, FORM_>;
 #ifndef NWE_ONLY_HEADLINE
 #define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_)                                                          \
     if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {                                                         \
         launch = term ? launch_one_term<W_, D_, SKIP_, FORM_> : share ? launch_one_share<W_, D_, SKIP_, FORM_> : launch_one<W_, D_, SKIP_, FORM_>; \
         n_chunks = Shape<W_, D_>::n_chunks(FORM_);                                                    \
+        NWE_PICK_TAIL(W_, D_, SKIP_, FORM_)                                                           \
     }
 #else
-#define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_) \
-    if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) { launch = launch_one<W_, D_, SKIP_, FORM_>; n_chunks = Shape<W_, D_>::n_chunks(FORM_); }
+#define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_)                \
+    if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {               \
+        launch = launch_one<W_, D_, SKIP_, FORM_>;          \
+        n_chunks = Shape<W_, D_>::n_chunks(FORM_);          \
+        NWE_PICK_TAIL(W_, D_, SKIP_, FORM_)                 \
+    }
 #endif
     NWE_SHAPES(NWE_PICK_SHAPE)
 #undef NWE_PICK_SHAPE
+#undef NWE_PICK_TAIL
     if (!launch) return false;
     if (nc.n_chunks != n_chunks || (a.n_importance > 0 && nf.n_chunks != n_chunks)) return false;   // the kernel copies n_chunks bias rows
     int64_t full = 0;
@@ -140,16 +156,45 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
         return q;
     };
     if (plan == 2) {
-        const RenderArgs first = dealt(0, full, false);
+        RenderArgs first = dealt(0, full, false);
         RenderArgs second = dealt(1, a.n_rays - full, true);
 #ifdef NWE_STAMPS   // the second launch's stamp rows lie behind the first's: rows are indexed by work item within a launch
         if (second.stamps) second.stamps += (size_t)mfma_workgroups(full, false) * kWaves * kStampWords;
 #endif
+        const bool backfill = info && info->side && info->fork && info->join;
+        // The tail path: the surplus workgroups of the queued packets launch render the split items, one ticket each from the
+        // call's third counter, and the second launch - the same kernel, behind the first on the device - renders what they
+        // left, which is nothing when the surplus covers every item; only then is the path taken.  Otherwise nothing changes.
+#ifdef NWE_STAMPS
+        RenderArgs plain = a; plain.stamps = nullptr;
+        const bool lean = is_lean(plain);
+#else
+        const bool lean = is_lean(a);
+#endif
+        const unsigned items1 = mfma_workgroups(a.n_rays - full, true);
+        if (first.queue && backfill && info->tail && lean && !term && !share && launch_tail && a.n_rays > full &&
+            info->grid[0] - info->items[0] >= items1) {
+            first.tail = second.tail = info->queue + 2;
+            second.share = kTailSecond;
+            launch_tail(first, nc, nf, three_pass, false, 0, full, stream);
+            if (info->mid) info->mid_recorded = hipEventRecord(info->mid, stream) == hipSuccess;
+            info->tail_items = items1;
+            // the side stream starts behind the first launch here: the second reads the third counter's final value
+            hipStream_t second_stream = stream;
+            if (hipEventRecord(info->fork, stream) == hipSuccess && hipStreamWaitEvent(info->side, info->fork, 0) == hipSuccess)
+                second_stream = info->side;
+            launch_tail(second, nc, nf, three_pass, true, full, a.n_rays - full, second_stream);
+            if (second_stream != stream) {
+                info->side_used = true;
+                if (hipEventRecord(info->join, second_stream) != hipSuccess || hipStreamWaitEvent(stream, info->join, 0) != hipSuccess) return false;
+            }
+            return true;
+        }
         // With queues on, the second launch backfills the first: it goes to the side stream, which forks from the caller's
         // stream in front of the first launch, so that its quarter-size work items are there for a CU the moment the packet
         // items run out; the side stream's low priority keeps them behind the packets until then.
         hipStream_t second_stream = stream;
-        if (info && info->side && info->fork && info->join && (first.queue || second.queue) &&
+        if (backfill && (first.queue || second.queue) &&
             hipEventRecord(info->fork, stream) == hipSuccess && hipStreamWaitEvent(info->side, info->fork, 0) == hipSuccess)
             second_stream = info->side;
         launch(first, nc, nf, three_pass, false, 0, full, stream);

@@ -1,0 +1,6 @@
+// Instantiations of the MFMA tail kernel (split items in the packets launch's tail), group E of nwe_mfma_shapes.h.
+#include "nwe_mfma_kernels.h"
+
+namespace nwe {
+NWE_SHAPES_E(NWE_SHAPE_TAIL_LAUNCHER)
+}  // namespace nwe

@@ -34,3 +34,8 @@
 #define NWE_SHAPE_SHARE_LAUNCHER(W_, D_, SKIP_, FORM_) \
     template void launch_one_share<W_, D_, SKIP_, FORM_>(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);
 #define NWE_EXTERN_SHAPE_SHARE_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_SHARE_LAUNCHER(W_, D_, SKIP_, FORM_)
+// The launcher of the shape's two tail kernels (a hybrid plan's split items in the packets launch's tail; lean, three-pass /
+// single-pass, each holding both decompositions), in files of their own (nwe_mfma_inst_tail_*.hip).
+#define NWE_SHAPE_TAIL_LAUNCHER(W_, D_, SKIP_, FORM_) \
+    template void launch_one_tail<W_, D_, SKIP_, FORM_>(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);
+#define NWE_EXTERN_SHAPE_TAIL_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_TAIL_LAUNCHER(W_, D_, SKIP_, FORM_)

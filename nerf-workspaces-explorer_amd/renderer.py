@@ -311,6 +311,24 @@ class Renderer:
         self._check(self._lib.nwe_debug_last_queue(self._ctx, items, grid, taken, C.byref(side)), "nwe_debug_last_queue")
         return {"items": tuple(items), "grid": tuple(grid), "taken": tuple(taken), "side_stream": bool(side.value)}
 
+    def debug_last_tail(self) -> int:
+        """The sample-split items that the packets launch of the last render rendered in its tail (include/nwe.h: the tail path of
+        the work queue; all of the plan's split items when the path was taken), 0 when it was not."""
+        stolen = C.c_uint(0)
+        self._check(self._lib.nwe_debug_last_tail(self._ctx, C.byref(stolen)), "nwe_debug_last_tail")
+        return int(stolen.value)
+
+    def debug_last_tail_rest(self) -> int:
+        """The split items that the SECOND launch of the last render rendered on the tail path: debug_last_tail() plus this is the
+        plan's split items exactly if every item was rendered once; 0 when the path was not taken."""
+        n = C.c_uint(0)
+        self._check(self._lib.nwe_debug_last_tail_rest(self._ctx, C.byref(n)), "nwe_debug_last_tail_rest")
+        return int(n.value)
+
+    def debug_get_work_queue_tail(self) -> bool:
+        """Whether this renderer may take the tail path: fixed when it was created (NWE_WORK_QUEUE_TAIL=0 in the environment then)."""
+        return bool(self._lib.nwe_debug_get_work_queue_tail(self._ctx))
+
     def set_white_background(self, on: bool) -> None:
         """rendering.white_background (model_utils.py:97-98): rgb += 1 - acc on every rgb output."""
         self._check(self._lib.nwe_set_white_background(self._ctx, 1 if on else 0), "nwe_set_white_background")

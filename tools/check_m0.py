@@ -95,8 +95,8 @@ def check(lib_path: str) -> int:
                     if body:
                         checked += analyse(body, addrs, x3)[0]
                     body, addrs = [], []
-                    in_kernel = "render_mfma_kernel" in m.group(1)
-                    mx = re.search(r"render_mfma_kernelILi\d+ELi\d+ELi(?:n?\d+)ELb([01])", m.group(1))
+                    in_kernel = bool(re.search(r"render_mfma_(?:tail_)?kernel", m.group(1)))   # the tail kernel holds both bodies
+                    mx = re.search(r"render_mfma_(?:tail_)?kernelILi\d+ELi\d+ELi(?:n?\d+)ELb([01])", m.group(1))
                     x3 = bool(mx and mx.group(1) == "1")
                     continue
                 if not in_kernel:

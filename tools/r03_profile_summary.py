@@ -16,19 +16,22 @@ OUT, PROF = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
 def counters(d):
     """{counter: mean per FRAME} of one --pmc pass: a frame is one dispatch of the packets instantiation of render_mfma_kernel
     plus, under the hybrid launch plan, one of the sample-split instantiation right behind it (template argument 5); the
-    counters of both are summed."""
+    counters of both are summed.  On the tail path both launches of a frame are render_mfma_tail_kernel: two dispatches a frame."""
     agg = collections.defaultdict(float)
-    frames, launches = set(), set()
+    frames, launches, tails = set(), set(), set()
     for f in glob.glob(f"{d}/**/*_counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             if "render_mfma" not in r["Kernel_Name"]:
                 continue
             agg[r["Counter_Name"]] += float(r["Counter_Value"])
             launches.add(r["Dispatch_Id"])
+            if "render_mfma_tail_kernel" in r["Kernel_Name"]:
+                tails.add(r["Dispatch_Id"])
+                continue
             args = r["Kernel_Name"].split("<", 1)[-1].split(",")
             if len(args) > 4 and args[4].strip() == "false":
                 frames.add(r["Dispatch_Id"])
-    n = max(len(frames) or len(launches), 1)
+    n = max(len(frames) + len(tails) // 2 or len(launches), 1)
     return {k: v / n for k, v in agg.items()}, n
 
 
