@@ -213,6 +213,56 @@ int nwe_create_rays(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, f
 int nwe_render_rays(nwe_ctx *ctx, const float *rays_dev, int64_t n_rays, int precision, const nwe_outputs *out,
                     void *stream);
 
+/* Device outputs of nwe_query_points, owned by the caller; raw or sigma may be NULL, not both. */
+typedef struct nwe_point_outputs {
+    uint64_t struct_bytes;  /* = sizeof(nwe_point_outputs), checked like nwe_outputs.struct_bytes */
+    float *raw;             /* [n_points,4]  [rgb_raw(3), sigma_raw]: run_network's row, no sigmoid, no ReLU */
+    float *sigma;           /* [n_points]    sigma_raw alone */
+    uint32_t *flags;        /* [1]  NWE_FLAG_RAW OR-ed in when a value written is NaN or inf (caller zeroes it) */
+} nwe_point_outputs;
+
+/* The point query: network `which` at arbitrary points, on the kernels that render.
+ * Replaces: run_network (nerf/models/model_utils.py:13-30): points [N,S,3] and view directions [N,3] give the raw network
+ * output [N,S,4] (the `show_endpoint` feature columns are not produced).
+ *   points_dev      DEVICE [n_points,3] fp32 world coordinates; the kernel divides by 10 itself, as everywhere
+ *                   (handler.py:93).
+ *   dirs_dev        DEVICE [ceil(n_points / points_per_dir),3]: point i is evaluated with direction i / points_per_dir.
+ *                   The reference's viewdirs[:, None].expand(inputs.shape) is points_per_dir = S; 1 = a direction per point.
+ *                   Used as given, not normalised, like the view-direction columns of nwe_render_rays (handler.py:210-214).
+ *                   NULL: required for a network set with nwe_set_network_no_view_dirs (a pointer there is NWE_ERR_INVALID);
+ *                   accepted for a network with view directions only when out->raw is NULL - sigma does not depend on the
+ *                   direction.
+ *   out             raw and / or sigma.  With out->raw == NULL, a direction given or not, the MFMA kernels evaluate the
+ *                   density trunk only where the shape has that path (the folded formulation except 6-deep networks with
+ *                   the skip after layer 4) and the full network with the colour dropped elsewhere; sigma has the same bits
+ *                   either way, and the bits of raw[.., 3].
+ * Every output row depends on its point and its direction and on nothing else: not on n_points, the rows around it, its
+ * place in a workgroup, nwe_debug_set_query_steps, the stream, or which outputs were requested.  It is, bit for bit, what
+ * nwe_render_rays writes to raw_coarse for a sample that sits at that point (o = p, near = far = 0) with that view direction.
+ * Needs network `which` set and nothing else: no nwe_set_sampling, no second network, and no rule about the other network's
+ * shape - a context that holds a 4x128 coarse and an 8x256 fine network answers queries to both under the MFMA precisions.
+ * Ignores white background, early termination, shared coarse pass, separate passes, decomposition and work queue.  Neither
+ * uses nor clears the one-shot hooks and training tables, and moves none of nwe_last_kernel_ms, nwe_last_launch_parts,
+ * nwe_debug_last_plan, nwe_last_ray_evaluations, nwe_debug_last_queue: its launches have events of their own.
+ * Refuses, in this order and before anything is queued: NULL or host-only context (NWE_ERR_STATE); NULL out, wrong
+ * struct_bytes, which not 0 / 1, n_points < 0 or >= 2^31, points_per_dir < 1, NULL points_dev with n_points > 0, neither raw
+ * nor sigma (NWE_ERR_INVALID); unknown precision (NWE_ERR_INVALID); network not set (NWE_ERR_STATE); the dirs_dev rules
+ * (NWE_ERR_INVALID); an MFMA precision for a shape without an MFMA kernel (NWE_ERR_UNSUPPORTED, "use NWE_PREC_F32").
+ * n_points == 0 is NWE_OK: nothing is launched and nwe_last_query_ms does not change.
+ * Asynchronous on `stream`.  Query launches have an event ring of their own (four launches in flight; a fifth call waits for
+ * the oldest), which the wait of nwe_set_network / nwe_set_sampling covers on whatever streams they are: weights a query
+ * still reads are never repacked under it.
+ * Non-finite and out-of-range coordinates follow the render path's rule above: never a finite wrong value under
+ * NWE_PREC_F16X3 / F16X1 (NaN, and NWE_FLAG_RAW), every finite coordinate defined under NWE_PREC_F32. */
+int nwe_query_points(nwe_ctx *ctx, int which, const float *points_dev, int64_t n_points, const float *dirs_dev,
+                     int64_t points_per_dir, int precision, const nwe_point_outputs *out, void *stream);
+/* Time of the most recent query launch, from HIP events of its own (like nwe_create_rays, it is no render launch); blocks
+ * until it has finished; < 0 if there was none yet. */
+float nwe_last_query_ms(nwe_ctx *ctx);
+/* Test hook: the packets (128 points under the MFMA precisions, 16 under NWE_PREC_F32) a query workgroup walks, 1..256;
+ * 0 = automatic (the default): packets / (8 x the device's CUs), at least 1 and at most 256.  Results do not depend on it. */
+int nwe_debug_set_query_steps(nwe_ctx *ctx, int steps);
+
 /* uint8 = (255 * clip(x,0,1)) truncated, elementwise over n floats on the device.
  * Replaces: to8b_np (nerf/models/model_utils.py:9) of render_coordinates' tail (handler.py:183). */
 int nwe_to8b(nwe_ctx *ctx, const float *rgb_dev, uint8_t *out_dev, int64_t n, void *stream);

@@ -26,7 +26,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_set_shared_coarse", "nwe_get_shared_coarse", "nwe_last_coarse_launch",
            "nwe_set_separate_passes", "nwe_get_separate_passes",
            "nwe_debug_set_work_queue", "nwe_debug_get_work_queue", "nwe_debug_get_work_queue_backfill", "nwe_debug_queue_grid", "nwe_debug_last_queue",
-           "nwe_debug_get_work_queue_tail", "nwe_debug_last_tail", "nwe_debug_last_tail_rest")
+           "nwe_debug_get_work_queue_tail", "nwe_debug_last_tail", "nwe_debug_last_tail_rest",
+           "nwe_query_points", "nwe_last_query_ms", "nwe_debug_set_query_steps")
 
 
 class Outputs(C.Structure):
@@ -34,6 +35,18 @@ class Outputs(C.Structure):
 
     def __init__(self, **kw):
         super().__init__(struct_bytes=C.sizeof(Outputs), **kw)
+
+
+POINT_OUTPUT_FIELDS = ("raw", "sigma", "flags")
+NWE_FLAG_RAW = 1 << 8
+
+
+class PointOutputs(C.Structure):
+    """nwe_point_outputs of nwe_query_points."""
+    _fields_ = [("struct_bytes", C.c_uint64)] + [(name, C.c_void_p) for name in POINT_OUTPUT_FIELDS]
+
+    def __init__(self, **kw):
+        super().__init__(struct_bytes=C.sizeof(PointOutputs), **kw)
 
 
 _lib = None
@@ -100,6 +113,9 @@ def load() -> C.CDLL:
         "nwe_debug_get_work_queue_tail": (I, [P]),
         "nwe_debug_last_tail": (I, [P, C.POINTER(C.c_uint)]),
         "nwe_debug_last_tail_rest": (I, [P, C.POINTER(C.c_uint)]),
+        "nwe_query_points": (I, [P, I, P, I64, P, I64, I, C.POINTER(PointOutputs), P]),
+        "nwe_last_query_ms": (F, [P]),
+        "nwe_debug_set_query_steps": (I, [P, I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -103,6 +103,11 @@ struct nwe_ctx {
     // next_slot: the slot the next render takes.  last_slot: the most recent render launch that was RECORDED
     // (nwe_last_kernel_ms); both move only when launch() has succeeded, so a refused launch leaves the timing calls alone.
     int next_slot = 0, last_slot = -1;
+    // nwe_query_points: a ring of its own, outside the render ring like rays_slot, so that a query moves none of the render
+    // launches' reports; last_query: the most recent query launch that was recorded (nwe_last_query_ms)
+    Slot query_slots[kSlots];
+    int next_query = 0, last_query = -1;
+    int query_steps = 0;      // nwe_debug_set_query_steps: 0 = automatic
     const float* dbg_z_fine = nullptr;
     const float *dbg_raw_c = nullptr, *dbg_raw_f = nullptr, *dbg_w = nullptr;   // nwe_debug_set_raw / _coarse_weights, one call
     int fold = 1;             // nwe_debug_set_fold: read by nwe_set_network
@@ -214,6 +219,8 @@ int wait_for_launches(nwe_ctx* c) {
     for (Slot& s : c->slots)
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     if (c->rays_slot.used) HIPCHK(c, hipEventSynchronize(c->rays_slot.ev1));
+    for (Slot& s : c->query_slots)   // a query streams the weights of its network throughout
+        if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     return NWE_OK;
 }
 
@@ -788,6 +795,63 @@ int nwe_create_rays(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, flo
         return NWE_OK;
     });
 }
+
+int nwe_query_points(nwe_ctx* c, int which, const float* points_dev, int64_t n_points, const float* dirs_dev, int64_t points_per_dir,
+                     int precision, const nwe_point_outputs* out, void* stream_) {
+    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
+    if (!out) return fail(c, NWE_ERR_INVALID, "null outputs");
+    if (out->struct_bytes != sizeof(nwe_point_outputs))
+        return fail(c, NWE_ERR_INVALID, "nwe_point_outputs.struct_bytes != sizeof(nwe_point_outputs): the caller was built against another version of include/nwe.h");
+    if (which != NWE_NET_COARSE && which != NWE_NET_FINE) return fail(c, NWE_ERR_INVALID, "which must be 0 or 1");
+    if (n_points < 0 || n_points > INT32_MAX) return fail(c, NWE_ERR_INVALID, "bad n_points (negative, or more than 2^31 - 1)");
+    if (points_per_dir < 1) return fail(c, NWE_ERR_INVALID, "points_per_dir must be at least 1");
+    if (!points_dev && n_points > 0) return fail(c, NWE_ERR_INVALID, "null points");
+    if (!out->raw && !out->sigma) return fail(c, NWE_ERR_INVALID, "neither raw nor sigma requested");
+    if (precision != NWE_PREC_F16X3 && precision != NWE_PREC_F16X1 && precision != NWE_PREC_F32)
+        return fail(c, NWE_ERR_INVALID, "unknown precision");
+    const NetState& net = c->net[which];
+    if (!net.set) return fail(c, NWE_ERR_STATE, which == NWE_NET_COARSE ? "coarse network not set" : "fine network not set");
+    if (net.in_dir == 0 && dirs_dev)
+        return fail(c, NWE_ERR_INVALID, "the network takes no view directions (nwe_set_network_no_view_dirs): dirs_dev must be null");
+    if (net.in_dir != 0 && !dirs_dev && out->raw)
+        return fail(c, NWE_ERR_INVALID, "raw output of a network with view directions needs dirs_dev (only sigma does not depend on the direction)");
+    if (precision != NWE_PREC_F32 && !net.mfma_ok)
+        return fail(c, NWE_ERR_UNSUPPORTED,
+                    "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
+    if (n_points == 0) return NWE_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    ON_DEVICE(c);
+    Slot& slot = c->query_slots[c->next_query];   // not a slot of the render ring (see nwe_create_rays)
+    TRY(prepare_slot(c, slot));
+    QueryArgs a = {};
+    a.points = points_dev; a.dirs = dirs_dev; a.raw = out->raw; a.sigma = out->sigma; a.flags = out->flags;
+    a.n_points = (int)n_points;
+    a.points_per_dir = (int)std::min(points_per_dir, n_points);   // one direction for all of them from there on
+    a.density_only = out->raw ? 0 : 1;
+    TRY(record_launch(c, slot, stream, [&]() -> int {
+        if (precision == NWE_PREC_F32) launch_query_f32(a, net.f32, c->query_steps, stream);
+        else if (!launch_query_mfma(a, net.mf, precision == NWE_PREC_F16X3, c->query_steps, stream))
+            return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
+        return NWE_OK;
+    }));
+    c->last_query = (int)(&slot - c->query_slots);
+    c->next_query = (c->last_query + 1) % nwe_ctx::kSlots;
+    return NWE_OK;
+}
+
+float nwe_last_query_ms(nwe_ctx* c) {
+    if (!c || c->host_only || c->last_query < 0 || !c->query_slots[c->last_query].used) return -1.f;
+    const Slot& s = c->query_slots[c->last_query];
+    DeviceGuard guard;
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = hipEventSynchronize(s.ev1);
+    float ms = -1.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, s.ev0, s.ev1);
+    if (e != hipSuccess) { c->err = std::string("nwe_last_query_ms: ") + hipGetErrorString(e); (void)hipGetLastError(); return -1.f; }
+    return ms;
+}
+
+int nwe_debug_set_query_steps(nwe_ctx* c, int steps) { return set_on(steps < 0 || steps > kQueryMaxSteps ? nullptr : c, [&] { c->query_steps = steps; }); }
 
 int nwe_render_rays(nwe_ctx* c, const float* rays_dev, int64_t n_rays, int precision, const nwe_outputs* out, void* stream) {
     HookReset hooks{c};   // every return below, refusals included, consumes the one-shot hooks

@@ -62,6 +62,36 @@ bool mfma_is_lean(const RenderArgs& a);
 
 int mfma_max_samples();      // n_samples the MFMA kernel's per-wave LDS buffers are sized for
 
+// ---- point query (nwe_query_points): run_network at arbitrary points ----
+// Kernel arguments of a query launch (by value).  n_points is below 2^31 (the ABI refuses more), points_per_dir is at least 1
+// and clamped to n_points by the launcher, so row and direction indices are 32-bit; offsets are formed in 64 bits.
+struct QueryArgs {
+    const float* points;    // [n_points, 3] world coordinates (the kernel divides by 10, handler.py:93)
+    const float* dirs;      // [ceil(n_points / points_per_dir), 3] view directions, used as given; null: zeros (sigma needs none)
+    float* raw;             // [n_points, 4] or null
+    float* sigma;           // [n_points] or null
+    uint32_t* flags;        // [1] or null
+    int n_points;
+    int points_per_dir;
+    int steps;              // packets (128 points on the MFMA kernels, 16 on the fp32 kernel) a workgroup walks, one per step
+    int density_only;       // launch-uniform: raw is null, so the colour layers may be left out where the shape has that path
+};
+
+constexpr int kQueryPacket = 128;      // points per step of query_mfma_kernel (32 per wave)
+constexpr int kQueryPacketF32 = 16;    // ... of query_f32_kernel
+constexpr int kQueryMaxSteps = 256;    // steps per workgroup at the most: one packet workgroup's worth of evaluations of the bench frame (64 + 192 samples)
+
+// Steps per workgroup of a query of `packets` packets; forced (nwe_debug_set_query_steps) > 0 overrides the rule.
+// The rule: a workgroup holds a CU by itself, so a launch runs in rounds of one workgroup per CU.  A large query gets EIGHT
+// workgroups per CU - the last round, in which CUs idle once their workgroup is done, is then an eighth of the launch at the
+// most - and as many steps per workgroup as that leaves, up to kQueryMaxSteps: steps = clamp(packets / (8 CUs), 1, 256).
+// The prologue a workgroup amortises over its steps is small (one bias table, ~10 KB from L2, and a barrier: a few per cent
+// of ONE step), so a query of up to 8 CUs packets runs one step per workgroup and spreads as widely as it can.
+int query_steps(int64_t packets, int forced);
+void launch_query_f32(const QueryArgs& a, const NetF32& net, int forced_steps, hipStream_t stream);
+// false: no query kernel for the network's shape (the shapes of mfma_supported), or its stream does not fit the instantiation
+bool launch_query_mfma(const QueryArgs& a, const NetMfma& net, bool three_pass, int forced_steps, hipStream_t stream);
+
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);
 

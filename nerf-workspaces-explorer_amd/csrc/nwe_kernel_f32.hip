@@ -272,4 +272,93 @@ void launch_render_f32(const RenderArgs& a, const NetF32& nc, const NetF32& nf, 
     else hipLaunchKernelGGL(render_f32_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, a, nc, nf);
 }
 
+// The point query of the fp32 path (include/nwe.h: nwe_query_points; the MFMA one: nwe_mfma_query.h): run_network of
+// nerf/models/model_utils.py:13-30 in the arithmetic of render_f32_kernel's evaluation block - encode16 and dense16, the trunk
+// with its skip, then the heads - for any shape of the fp32 domain.  A workgroup owns a.steps x 16 consecutive points and
+// walks them 16 per step: the first 16 threads own one point each, gamma(d) is encoded again every step (the direction
+// belongs to the point), a thread past n_points takes the last point and stores nothing, and a step that lies wholly past
+// n_points is not run (uniform: it depends on the block, the step and n_points).  With raw == null the evaluation is still the
+// full one and the colour is dropped.  VIEW: the network has view directions (net.in_dir != 0), else the one output layer.
+template <bool VIEW>
+__global__ void __launch_bounds__(256) query_f32_kernel(QueryArgs a, NetF32 net) {
+    __shared__ __attribute__((aligned(16))) float s_gx[96 * kRP];
+    __shared__ __attribute__((aligned(16))) float s_gd[64 * kRP];
+    __shared__ __attribute__((aligned(16))) float s_ha[256 * kRP];
+    __shared__ __attribute__((aligned(16))) float s_hb[256 * kRP];
+    __shared__ __attribute__((aligned(16))) float s_pt[3 * kRP];
+    __shared__ __attribute__((aligned(16))) float s_dir[3 * kRP];
+    __shared__ __attribute__((aligned(16))) float s_raw[4 * kRP];
+    static_assert(kQueryPacketF32 == kRP, "a step is one packet of the fp32 kernels");
+    const int tid = threadIdx.x;
+    const bool owner = tid < kRP;
+    const int n = a.n_points;
+    uint32_t flags = 0;
+    for (int step = 0; step < a.steps; ++step) {
+        const int64_t first = ((int64_t)blockIdx.x * a.steps + step) * kRP;
+        if (first >= n) break;
+        const int64_t idx = first + tid;
+        if (owner) {
+            const int row = (int)(idx < n ? idx : n - 1);
+            const float* p = a.points + (int64_t)row * 3;
+            s_pt[0 * kRP + tid] = p[0]; s_pt[1 * kRP + tid] = p[1]; s_pt[2 * kRP + tid] = p[2];
+            if constexpr (VIEW) {
+                float vx = 0.f, vy = 0.f, vz = 0.f;      // no directions given: sigma does not depend on them
+                if (a.dirs) {
+                    const float* d = a.dirs + (int64_t)(row / a.points_per_dir) * 3;
+                    vx = d[0]; vy = d[1]; vz = d[2];
+                }
+                s_dir[0 * kRP + tid] = vx; s_dir[1 * kRP + tid] = vy; s_dir[2 * kRP + tid] = vz;
+            }
+        }
+        __syncthreads();
+        if constexpr (VIEW) encode16(s_gd, s_dir, net.in_dir, 1.f);   // handler.py:101 scalar_factor = 1
+        encode16(s_gx, s_pt, net.in_xyz, 10.f);   // handler.py:93 scalar_factor = 10
+        __syncthreads();
+        // trunk: nerf_model.py:53-59
+        float* cur = s_ha; float* nxt = s_hb;
+        dense16(net.blob, net.pts[0], s_gx, net.in_xyz, nullptr, 0, cur, true);
+        for (int i = 1; i < net.D; ++i) {
+            if (i == net.skip + 1) dense16(net.blob, net.pts[i], s_gx, net.in_xyz, cur, net.W, nxt, true);
+            else dense16(net.blob, net.pts[i], cur, net.W, nullptr, 0, nxt, true);
+            float* t = cur; cur = nxt; nxt = t;
+        }
+        if constexpr (!VIEW) {
+            // use_view_dirs=False, nerf_model.py:82-83: channels 0..2 rgb_raw, 3 sigma_raw of _output_linear(h)
+            dense16(net.blob, net.output, cur, net.W, nullptr, 0, nxt, false);
+            if (tid < 4 * kRP) s_raw[tid] = nxt[tid];
+            __syncthreads();
+        } else {
+            // heads: nerf_model.py:63-74
+            dense16(net.blob, net.alpha, cur, net.W, nullptr, 0, s_raw + 3 * kRP, false);
+            dense16(net.blob, net.feature, cur, net.W, nullptr, 0, nxt, false);
+            dense16(net.blob, net.views, nxt, net.W, s_gd, net.in_dir, cur, true);
+            dense16(net.blob, net.rgb, cur, net.W / 2, nullptr, 0, s_raw, false);
+        }
+        if (owner && idx < n) {
+            const float rr = s_raw[0 * kRP + tid], rg = s_raw[1 * kRP + tid], rb = s_raw[2 * kRP + tid], rs = s_raw[3 * kRP + tid];
+            if (a.raw) {
+                *reinterpret_cast<float4*>(a.raw + idx * 4) = make_float4(rr, rg, rb, rs);
+                if (bad(rr) || bad(rg) || bad(rb) || bad(rs)) flags |= NWE_FLAG_RAW;
+            }
+            if (a.sigma) {
+                a.sigma[idx] = rs;
+                if (bad(rs)) flags |= NWE_FLAG_RAW;
+            }
+        }
+        // s_pt / s_dir are rewritten at the top of the next step, behind the barrier every thread passed after encode16 read
+        // them; s_raw only behind the next step's barriers, which an owner reaches after its reads above.
+    }
+    if (flags && a.flags) atomicOr(a.flags, flags);
+}
+
+void launch_query_f32(const QueryArgs& a_in, const NetF32& net, int forced_steps, hipStream_t stream) {
+    if (a_in.n_points <= 0) return;
+    QueryArgs a = a_in;
+    const int64_t packets = ((int64_t)a.n_points + kRP - 1) / kRP;
+    a.steps = query_steps(packets, forced_steps);
+    const dim3 grid((unsigned)((packets + a.steps - 1) / a.steps));
+    if (net.in_dir != 0) hipLaunchKernelGGL(query_f32_kernel<true>, grid, dim3(256), 0, stream, a, net);
+    else hipLaunchKernelGGL(query_f32_kernel<false>, grid, dim3(256), 0, stream, a, net);
+}
+
 }  // namespace nwe

@@ -1,6 +1,7 @@
 // Launch planning and dispatch of the MFMA render kernel (templates: nwe_mfma_kernels.h).  The instantiations are compiled in
 // separate translation units (nwe_mfma_inst_*.hip, one group of nwe_mfma_shapes.h each) so that they build in parallel.
 #include "nwe_mfma_kernels.h"
+#include "nwe_mfma_query.h"
 
 namespace nwe {
 
@@ -13,6 +14,7 @@ NWE_SHAPES(NWE_EXTERN_SHAPE_LAUNCHER)
 NWE_SHAPES(NWE_EXTERN_SHAPE_TERM_LAUNCHER)
 NWE_SHAPES(NWE_EXTERN_SHAPE_SHARE_LAUNCHER)
 NWE_SHAPES(NWE_EXTERN_SHAPE_TAIL_LAUNCHER)
+NWE_SHAPES(NWE_EXTERN_SHAPE_QUERY_LAUNCHER)
 #define NWE_TAIL_BUILT(FORM_) tail_built(FORM_)
 #define NWE_TERM_BUILT(FORM_) term_built(FORM_)
 #define NWE_SHARE_BUILT(FORM_) share_built(FORM_)
@@ -209,6 +211,38 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
         launch(dealt(0, a.n_rays, plan == 1), nc, nf, three_pass, plan == 1, 0, a.n_rays, stream);
     }
     return true;
+}
+
+// ---- point query (nwe_query_points) ----
+
+int query_steps(int64_t packets, int forced) {
+    if (forced > 0) return forced < kQueryMaxSteps ? forced : kQueryMaxSteps;
+    const int64_t steps = packets / (8 * (int64_t)device_cus());   // the rule: nwe_host.h
+    return (int)(steps < 1 ? 1 : (steps > kQueryMaxSteps ? kQueryMaxSteps : steps));
+}
+
+bool launch_query_mfma(const QueryArgs& a_in, const NetMfma& net, bool three_pass, int forced_steps, hipStream_t stream) {
+#ifdef NWE_ONLY_HEADLINE   // diagnostic builds hold no query kernels
+    return false;
+#else
+    const int D = net.D, W = net.W, skip = net.skip, form = net.form;
+    decltype(&launch_one_query<256, 8, 4, kFormFolded>) launch = nullptr;
+    int n_chunks = -1;
+#define NWE_PICK_QUERY(W_, D_, SKIP_, FORM_)                \
+    if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {               \
+        launch = launch_one_query<W_, D_, SKIP_, FORM_>;    \
+        n_chunks = Shape<W_, D_>::n_chunks(FORM_);          \
+    }
+    NWE_SHAPES(NWE_PICK_QUERY)
+#undef NWE_PICK_QUERY
+    if (!launch || net.n_chunks != n_chunks) return false;   // the kernel copies n_chunks bias rows
+    if (a_in.n_points <= 0) return true;
+    QueryArgs a = a_in;
+    const int64_t packets = ((int64_t)a.n_points + kQueryPacket - 1) / kQueryPacket;
+    a.steps = query_steps(packets, forced_steps);
+    launch(a, net, three_pass, (unsigned)((packets + a.steps - 1) / a.steps), stream);
+    return true;
+#endif
 }
 
 }  // namespace nwe

@@ -39,3 +39,8 @@
 #define NWE_SHAPE_TAIL_LAUNCHER(W_, D_, SKIP_, FORM_) \
     template void launch_one_tail<W_, D_, SKIP_, FORM_>(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);
 #define NWE_EXTERN_SHAPE_TAIL_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_TAIL_LAUNCHER(W_, D_, SKIP_, FORM_)
+// The launcher of the shape's two query kernels (nwe_query_points: run_network at arbitrary points; three-pass / single-pass),
+// in files of their own (nwe_mfma_inst_query_*.hip, the same groups): a shape is queryable exactly if it renders.
+#define NWE_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_) \
+    template void launch_one_query<W_, D_, SKIP_, FORM_>(QueryArgs, const NetMfma&, bool, unsigned, hipStream_t);
+#define NWE_EXTERN_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_)

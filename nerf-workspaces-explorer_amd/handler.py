@@ -8,7 +8,8 @@ Same three public methods with the same argument types and return value as the r
 * ``render_coordinates(init_coordinates, coordinates) -> uint8 [H,W,3]`` (handler.py:166)
 
 plus the call surface BASELINE.json names, ``render(camera_pose, H, W)`` / ``render_batch(poses, H, W)``,
-and the internal seam ``_render_rays(flat_rays)`` (handler.py:187).  Python here does weight loading,
+the internal seam ``_render_rays(flat_rays)`` (handler.py:187), and the point query ``run_network(inputs, viewdirs)``
+(model_utils.py:13-30) with ``density_grid(lo, hi, resolution)`` on top of it.  Python here does weight loading,
 pose math and I/O only; rays, sampling, encoding, both MLPs and compositing run in libnwe_hip.so.
 Dropped side effects of the reference (none affects results): ``torch.cuda.empty_cache()`` (:86),
 ``eval()`` on YAML strings (:42-50), the tqdm bar, the ConfigParser singleton.
@@ -273,6 +274,68 @@ class NeRFReplicaInferenceHandler:
         res = r.render_rays(flat_rays, precision=precision, outputs=outputs, train=train)
         rename = {"rgb": "rgb_fine", "disp": "disp_fine", "acc": "acc_fine", "depth": "depth_fine", "feat_map": "feat_map_fine"}
         return {rename.get(k, k): v for k, v in res.items() if not k.startswith("_")}
+
+    # ------------------------------------------------------------------------------------------------
+    def _query_net(self, which) -> Tuple[int, str]:
+        """(network index, precision) of a point query: "auto" resolves per network - a query runs one network, so a coarse
+        and a fine network of two MFMA shapes both stay on the MFMA kernels."""
+        names = {"coarse": _lib.NET_COARSE, "fine": _lib.NET_FINE, _lib.NET_COARSE: _lib.NET_COARSE, _lib.NET_FINE: _lib.NET_FINE}
+        if isinstance(which, bool) or which not in names:
+            raise ValueError("which must be 'coarse' or 'fine'")
+        w = names[which]
+        r = self._need_renderer()
+        if not self._auto_precision:
+            return w, self._precision
+        return w, "f16x3" if r.mfma_supported(w) else "f32"
+
+    def run_network(self, inputs: torch.Tensor, viewdirs: Optional[torch.Tensor], which="fine",
+                    precision: Optional[str] = None) -> torch.Tensor:
+        """The reference's run_network (nerf/models/model_utils.py:13-30) on the render kernels: points ``inputs`` [N,S,3] and
+        view directions ``viewdirs`` [N,3] (None with rendering.use_view_dirs = False) -> raw [N,S,4] = rgb_raw, sigma_raw of
+        the ``which`` network.  World coordinates; the directions are used as given."""
+        if inputs.dim() != 3 or inputs.shape[-1] != 3:
+            raise ValueError(f"inputs must be [N,S,3], got {tuple(inputs.shape)}")
+        if viewdirs is not None and tuple(viewdirs.shape) != (inputs.shape[0], 3):
+            raise ValueError(f"viewdirs must be [N,3] = [{inputs.shape[0]},3], got {tuple(viewdirs.shape)}")
+        w, auto = self._query_net(which)
+        return self._need_renderer().query_points(inputs, viewdirs, which=w, precision=precision or auto, outputs=("raw",))["raw"]
+
+    @staticmethod
+    def grid_centres(lo: Sequence[float], hi: Sequence[float], resolution: Sequence[int], start: int = 0,
+                     count: Optional[int] = None, device=None) -> torch.Tensor:
+        """Cell centres [count,3] (float32) of the axis-aligned box lo..hi cut into resolution = (rx, ry, rz) cells, for the flat
+        cell indices start .. start + count - 1 of the [rx, ry, rz] grid (z fastest).  Along an axis with r cells, cell i has
+        its centre at (i + 0.5) * step + lo with step = (hi - lo) / r rounded to float32 once: a float32 product, then a
+        float32 sum."""
+        rx, ry, rz = (int(r) for r in resolution)
+        count = rx * ry * rz - start if count is None else count
+        i = torch.arange(start, start + count, dtype=torch.int64, device=device)
+        index = (i // (ry * rz), (i // rz) % ry, i % rz)
+        cols = []
+        for idx, l, h, r in zip(index, lo, hi, (rx, ry, rz)):
+            step = float(np.float32((float(h) - float(l)) / r))
+            cols.append((idx.to(torch.float32) + 0.5) * step + float(np.float32(l)))
+        return torch.stack(cols, -1)
+
+    def density_grid(self, lo: Sequence[float], hi: Sequence[float], resolution, which="fine", chunk: int = 1 << 20,
+                     precision: Optional[str] = None) -> torch.Tensor:
+        """sigma_raw of the ``which`` network at the cell centres of the box lo..hi (world coordinates), [rx, ry, rz] on the
+        device; ``resolution`` = one int or (rx, ry, rz).  The centres are generated on the device (grid_centres) and
+        evaluated with the sigma-only query, ``chunk`` points at a time at the most."""
+        res3 = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(r) for r in resolution)
+        if len(res3) != 3 or min(res3) < 1 or len(lo) != 3 or len(hi) != 3:
+            raise ValueError("density_grid needs lo, hi of three coordinates and a resolution of one or three positive ints")
+        if int(chunk) < 1:
+            raise ValueError("chunk must be at least 1")
+        w, auto = self._query_net(which)
+        r = self._need_renderer()
+        total = res3[0] * res3[1] * res3[2]
+        out = torch.empty(total, dtype=torch.float32, device=r.device)
+        for start in range(0, total, int(chunk)):
+            count = min(int(chunk), total - start)
+            pts = self.grid_centres(lo, hi, res3, start, count, device=r.device)
+            out[start:start + count] = r.query_points(pts, None, which=w, precision=precision or auto, outputs=("sigma",))["sigma"]
+        return out.reshape(res3)
 
     # ------------------------------------------------------------------------------------------------
     @property

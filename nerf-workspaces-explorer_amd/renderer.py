@@ -381,6 +381,78 @@ class Renderer:
         self._check(self._lib.nwe_last_ray_evaluations(self._ctx, out), "nwe_last_ray_evaluations")
         return int(out[0]), int(out[1])
 
+    # -- point query ------------------------------------------------------------------------------
+    @staticmethod
+    def query_layout(points_shape: Sequence[int], dirs_shape: Optional[Sequence[int]]) -> Tuple[int, int]:
+        """(n_points, points_per_dir) of a query, or ValueError: ``points`` is [..., 3]; ``dirs`` is None, or one row per
+        point (the shape of ``points``), or [N,3] against ``points`` of shape [N,S,3] (run_network's layout,
+        model_utils.py:23-25: points_per_dir = S)."""
+        points_shape = tuple(int(d) for d in points_shape)
+        if len(points_shape) < 1 or points_shape[-1] != 3:
+            raise ValueError(f"points must be [..., 3], got {points_shape}")
+        n = int(np.prod(points_shape[:-1], dtype=np.int64))
+        if dirs_shape is None:
+            return n, 1
+        dirs_shape = tuple(int(d) for d in dirs_shape)
+        if dirs_shape == points_shape:
+            return n, 1
+        if len(points_shape) == 3 and dirs_shape == (points_shape[0], 3):
+            return n, max(points_shape[1], 1)
+        raise ValueError(f"dirs must be one row per point {points_shape} or [N,3] against points [N,S,3], got {dirs_shape} against {points_shape}")
+
+    def query_points(self, points: torch.Tensor, dirs: Optional[torch.Tensor] = None, *, which: int = _lib.NET_FINE,
+                     precision: str = "f16x3", outputs: Sequence[str] = ("raw",)) -> Dict[str, torch.Tensor]:
+        """Network ``which`` at arbitrary points (nwe_query_points; the reference's run_network, model_utils.py:13-30):
+        ``points`` float32 [..., 3] world coordinates on this renderer's device, ``dirs`` float32 view directions, used as
+        given (see query_layout; None for networks without view directions, and allowed when only sigma is asked for).
+        ``outputs`` of "raw" ([..., 4] = rgb_raw, sigma_raw: no sigmoid, no ReLU) and "sigma" ([...] = sigma_raw); the
+        result also holds "flags" (NWE_FLAG_RAW when a value written is NaN or inf).  Needs nothing but that network set."""
+        n, ppd = self.query_layout(points.shape, None if dirs is None else dirs.shape)
+        if points.dtype != torch.float32 or (dirs is not None and dirs.dtype != torch.float32):
+            raise ValueError("points and dirs must be float32")
+        outputs = tuple(outputs)
+        if not outputs or set(outputs) - {"raw", "sigma"} or len(set(outputs)) != len(outputs):
+            raise ValueError(f"outputs must be a non-empty choice of 'raw' and 'sigma', got {outputs!r}")
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"unknown precision {precision!r}")
+        if which not in (_lib.NET_COARSE, _lib.NET_FINE):
+            raise ValueError("which must be 0 (coarse) or 1 (fine)")
+        o = _lib.PointOutputs()
+        if self.device is None:   # a host-only context: the ABI's own refusal
+            self._check(self._lib.nwe_query_points(self._ctx, which, None, n, None, ppd, _lib.PRECISIONS[precision], C.byref(o), None),
+                        "nwe_query_points")
+        points = points.to(self.device).contiguous()
+        dirs = None if dirs is None else dirs.to(self.device).contiguous()
+        lead = tuple(points.shape[:-1])
+        with torch.cuda.device(self.device):
+            res: Dict[str, torch.Tensor] = {"flags": torch.zeros(1, dtype=torch.int32, device=self.device)}
+            # at least one row each, so that an empty query still hands the ABI the pointers that say what was asked for
+            base = {"flags": res["flags"]}
+            if "raw" in outputs:
+                base["raw"] = torch.empty((max(n, 1), 4), dtype=torch.float32, device=self.device)
+                res["raw"] = base["raw"][:n].reshape(lead + (4,))
+            if "sigma" in outputs:
+                base["sigma"] = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+                res["sigma"] = base["sigma"][:n].reshape(lead)
+            for name in _lib.POINT_OUTPUT_FIELDS:
+                setattr(o, name, base[name].data_ptr() if name in base else None)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            if dirs is not None and dirs.numel() == 0:   # likewise: "directions were given"
+                dirs = torch.zeros(3, dtype=torch.float32, device=self.device)
+            rc = self._lib.nwe_query_points(self._ctx, which, points.data_ptr() if n else None, n, None if dirs is None else dirs.data_ptr(),
+                                            ppd, _lib.PRECISIONS[precision], C.byref(o), stream)
+        self._check(rc, "nwe_query_points")
+        res["_keepalive_points"] = (points, dirs)
+        return res
+
+    def last_query_ms(self) -> float:
+        """Time of the last query launch (events of its own: no render moves it, and it moves no render's); < 0 if none yet."""
+        return float(self._lib.nwe_last_query_ms(self._ctx))
+
+    def debug_set_query_steps(self, steps: int) -> None:
+        """Test hook: the packets a query workgroup walks (1..256; 0 = automatic).  Results do not depend on it."""
+        self._check(self._lib.nwe_debug_set_query_steps(self._ctx, int(steps)), "nwe_debug_set_query_steps")
+
     def to8b(self, rgb: torch.Tensor) -> torch.Tensor:
         rgb = rgb.contiguous()
         out = torch.empty(rgb.shape, dtype=torch.uint8, device=rgb.device)

@@ -1,6 +1,6 @@
 """The MFMA render kernels keep the LDS-DMA destination in M0 across statements (one write per group of pieces), which is
 sound only while hipcc emits no M0 use of its own in those kernels: disassemble the built library and check, for every
-render_mfma_kernel, that
+render_mfma_kernel, render_mfma_tail_kernel and query_mfma_kernel, that
 
 * every instruction touching m0 is one of ours: `s_mov_b32 m0, <scalar register>` immediately followed by `s_nop 0` and the
   `global_load_lds_dwordx4` it addresses - the one asm statement of Walker::piece;
@@ -26,6 +26,7 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 IMPLICIT = re.compile(r"^(s_set_gpr_idx_\w+|s_movrel\w*|v_movrel\w*|ds_gws_\w+|ds_ordered_count|ds_\w+_gs\w*|s_sendmsg\w*|s_ttracedata\w*|"
                       r"v_interp_\w+|s_getreg_b32 \S+ hwreg\(HW_REG_M0|buffer_\w+ .*\blds\b|ds_\w+ .*\bgds\b)")
 PIECE = "global_load_lds_dwordx4"
+KERNEL = r"(?:render_mfma_(?:tail_)?|query_mfma_)kernel"   # the kernels that own M0
 
 
 def analyse(body, addrs=None, x3=True):
@@ -95,8 +96,10 @@ def check(lib_path: str) -> int:
                     if body:
                         checked += analyse(body, addrs, x3)[0]
                     body, addrs = [], []
-                    in_kernel = bool(re.search(r"render_mfma_(?:tail_)?kernel", m.group(1)))   # the tail kernel holds both bodies
-                    mx = re.search(r"render_mfma_(?:tail_)?kernelILi\d+ELi\d+ELi(?:n?\d+)ELb([01])", m.group(1))
+                    # the tail kernel holds both bodies; the query kernel (nwe_mfma_query.h) walks the same weight stream, and its
+                    # template arguments begin like the render kernels': W, D, SKIP, X3
+                    in_kernel = bool(re.search(KERNEL, m.group(1)))
+                    mx = re.search(KERNEL + r"ILi\d+ELi\d+ELi(?:n?\d+)ELb([01])", m.group(1))
                     x3 = bool(mx and mx.group(1) == "1")
                     continue
                 if not in_kernel:
