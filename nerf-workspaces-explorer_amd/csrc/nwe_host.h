@@ -45,8 +45,6 @@ struct LaunchInfo {
 // true if a plain launch of `a` under this decomposition and queue mode deals at least one launch of its plan from a queue: the
 // same plan and the same size test as launch_render_mfma's, for the caller that has to provide the counters and the stream
 bool mfma_queues(const RenderArgs& a, int decomposition, int queue_mode);
-// workgroups of a launch of `rays` rays (split: one packet per workgroup)
-unsigned mfma_workgroups(int64_t rays, bool split);
 bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& nf, bool three_pass, int decomposition, hipStream_t stream,
                         LaunchInfo* info);
 

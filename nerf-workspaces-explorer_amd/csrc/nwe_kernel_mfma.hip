@@ -1,52 +1,83 @@
-// Launch planning and dispatch of the MFMA render kernel (templates: nwe_mfma_kernels.h).  The instantiations are compiled in
-// separate translation units (nwe_mfma_inst_*.hip, one group of nwe_mfma_shapes.h each) so that they build in parallel.
+// Launch planning and dispatch of the MFMA render kernel (templates: nwe_mfma_kernels.h).  This file compiles no kernel: the
+// instantiations are translation units of their own (nwe_mfma_inst.hip, once per group of nwe_mfma_shapes.h and kernel variant)
+// so that they build in parallel, and are reached through the table below.
 #include "nwe_mfma_kernels.h"
 #include "nwe_mfma_query.h"
 
 namespace nwe {
 
-#ifdef NWE_ONE_KERNEL   // register-pressure experiments: `make one` compiles just the headline instantiation to assembly
-template __global__ void render_mfma_kernel<256, 8, 4, true, false, NWE_ONE_KERNEL, true>(RenderArgs, NetMfma, NetMfma);
-}  // namespace nwe
+#define NWE_DECLARE_SHAPE(W_, D_, SKIP_, FORM_)                                                                                   \
+    NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantPlain) NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantTerm)   \
+    NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantShare) NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantTail)   \
+    NWE_EXTERN_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_)
+NWE_SHAPES(NWE_DECLARE_SHAPE)
+#undef NWE_DECLARE_SHAPE
+
+// What this library links of a shape in the table.  The product: every variant the shape has, and its query kernels.  A
+// diagnostic build (-DNWE_ONLY_HEADLINE: the headline shape alone) links the plain kernels and - `make stamps`,
+// -DNWE_DIAG_TAIL - the tail kernel; what is not linked is not named, so its table entry is null.
+constexpr bool linked(int variant) {
+#if !defined(NWE_ONLY_HEADLINE)
+    return true;
+#elif defined(NWE_DIAG_TAIL)
+    return variant == kVariantPlain || variant == kVariantTail;
 #else
-NWE_SHAPES(NWE_EXTERN_SHAPE_LAUNCHER)
-#ifndef NWE_ONLY_HEADLINE   // diagnostic builds hold no terminating kernels
-NWE_SHAPES(NWE_EXTERN_SHAPE_TERM_LAUNCHER)
-NWE_SHAPES(NWE_EXTERN_SHAPE_SHARE_LAUNCHER)
-NWE_SHAPES(NWE_EXTERN_SHAPE_TAIL_LAUNCHER)
-NWE_SHAPES(NWE_EXTERN_SHAPE_QUERY_LAUNCHER)
-#define NWE_TAIL_BUILT(FORM_) tail_built(FORM_)
-#define NWE_TERM_BUILT(FORM_) term_built(FORM_)
-#define NWE_SHARE_BUILT(FORM_) share_built(FORM_)
-#else
-#ifdef NWE_DIAG_TAIL   // `make stamps` holds the headline shape's tail kernel (nwe_mfma_inst_tail_a.hip), the other diagnostic builds none
-NWE_SHAPES(NWE_EXTERN_SHAPE_TAIL_LAUNCHER)
-#define NWE_TAIL_BUILT(FORM_) tail_built(FORM_)
-#else
-#define NWE_TAIL_BUILT(FORM_) false
+    return variant == kVariantPlain;
 #endif
-#define NWE_TERM_BUILT(FORM_) false
-#define NWE_SHARE_BUILT(FORM_) false
+}
+#ifdef NWE_ONLY_HEADLINE
+constexpr bool kQueryLinked = false;
+#else
+constexpr bool kQueryLinked = true;
 #endif
-#define NWE_SHAPE_IS(W_, D_, SKIP_, FORM_) (W == W_ && D == D_ && skip == SKIP_ && form == FORM_)
+
+using QueryLauncher = void (*)(QueryArgs, const NetMfma&, bool, unsigned, hipStream_t);
+
+template <int W, int D, int SKIP, int FORM, int VARIANT>
+constexpr RenderLauncher render_launcher() {
+    if constexpr (linked(VARIANT) && variant_built(VARIANT, FORM)) return launch_one<W, D, SKIP, FORM, VARIANT>;
+    else return nullptr;
+}
+template <int W, int D, int SKIP, int FORM>
+constexpr QueryLauncher query_launcher() {
+    if constexpr (kQueryLinked) return launch_one_query<W, D, SKIP, FORM>;
+    else return nullptr;
+}
+
+// One row per built shape: what identifies it, the chunks of its weight stream (the kernel copies that many bias rows), its
+// render launcher per variant and its query launcher.  A null launcher: not built.
+struct ShapeRow {
+    int W, D, skip, form, n_chunks;
+    RenderLauncher render[kVariants];
+    QueryLauncher query;
+};
+#define NWE_SHAPE_ROW(W_, D_, SKIP_, FORM_)                                                                                  \
+    {W_, D_, SKIP_, FORM_, Shape<W_, D_>::n_chunks(FORM_),                                                                   \
+     {render_launcher<W_, D_, SKIP_, FORM_, kVariantPlain>(), render_launcher<W_, D_, SKIP_, FORM_, kVariantTerm>(),         \
+      render_launcher<W_, D_, SKIP_, FORM_, kVariantShare>(), render_launcher<W_, D_, SKIP_, FORM_, kVariantTail>()},        \
+     query_launcher<W_, D_, SKIP_, FORM_>()},
+static const ShapeRow kShapes[] = {NWE_SHAPES(NWE_SHAPE_ROW)};
+#undef NWE_SHAPE_ROW
+
+static const ShapeRow* find_shape(int D, int W, int skip, int form) {
+    for (const ShapeRow& r : kShapes)
+        if (r.W == W && r.D == D && r.skip == skip && r.form == form) return &r;
+    return nullptr;
+}
 
 bool mfma_supported(int D, int W, int in_xyz, int in_dir, int skip, int form) {
     if (in_xyz != 63 || in_dir != (form == kFormNoViewDirs ? 0 : 27)) return false;
-#define NWE_OR_SHAPE(W_, D_, SKIP_, FORM_) || NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)
-    return false NWE_SHAPES(NWE_OR_SHAPE);
-#undef NWE_OR_SHAPE
+    return find_shape(D, W, skip, form) != nullptr;
 }
 
 bool mfma_term_supported(int D, int W, int skip, int form) {
-#define NWE_OR_TERM_SHAPE(W_, D_, SKIP_, FORM_) || (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_) && NWE_TERM_BUILT(FORM_))
-    return false NWE_SHAPES(NWE_OR_TERM_SHAPE);
-#undef NWE_OR_TERM_SHAPE
+    const ShapeRow* shape = find_shape(D, W, skip, form);
+    return shape && shape->render[kVariantTerm];
 }
 
 bool mfma_share_supported(int D, int W, int skip, int form) {
-#define NWE_OR_SHARE_SHAPE(W_, D_, SKIP_, FORM_) || (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_) && NWE_SHARE_BUILT(FORM_))
-    return false NWE_SHAPES(NWE_OR_SHARE_SHAPE);
-#undef NWE_OR_SHARE_SHAPE
+    const ShapeRow* shape = find_shape(D, W, skip, form);
+    return shape && shape->render[kVariantShare];
 }
 
 bool mfma_is_lean(const RenderArgs& a) { return is_lean(a); }
@@ -57,11 +88,6 @@ static int device_cus() {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     return cus > 0 ? cus : 256;
-}
-
-unsigned mfma_workgroups(int64_t rays, bool split) {
-    const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
-    return (unsigned)((rays + per_wg - 1) / per_wg);
 }
 
 // The plan of a call: 0 = all packets, 1 = all sample-split, 2 = hybrid; *full = the rays of the hybrid plan's first launch.
@@ -105,8 +131,6 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
     if (a.n_importance > 0 && (nf.D != nc.D || nf.W != nc.W || nf.skip != nc.skip || nf.form != nc.form)) return false;
     if (a.n_samples > kSplitMaxSamples) return false;
     const int D = nc.D, W = nc.W, skip = nc.skip, form = nc.form;
-    decltype(&launch_one<256, 8, 4, kFormFolded>) launch = nullptr, launch_tail = nullptr;
-    int n_chunks = -1;
     // early termination (a.min_trans > 0): the shape's terminating kernels, which exist for lean calls only (nwe_abi.hip refuses
     // the rest by name before it gets here)
     const bool term = a.min_trans > 0.f;
@@ -118,28 +142,12 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
     const bool share = a.share != kShareOff && is_lean(a);
     if (a.share != kShareOff && !share && (term || (share_role(a) == kShareProducer ? a.n_importance != 0 : !a.w_in))) return false;
     if (share && (term || !a.share_w || a.n_importance <= 0 || !mfma_share_supported(D, W, skip, form))) return false;
-#define NWE_PICK_TAIL(W_, D_, SKIP_, FORM_) \
-    if constexpr (NWE_TAIL_BUILT(FORM_)) launch_tail = launch_one_tail<W_, D_, SKIP_, FORM_>;
-#ifndef NWE_ONLY_HEADLINE
-#define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_)                                                          \
-    if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {                                                         \
-        launch = term ? launch_one_term<W_, D_, SKIP_, FORM_> : share ? launch_one_share<W_, D_, SKIP_, FORM_> : launch_one<W_, D_, SKIP_, FORM_>; \
-        n_chunks = Shape<W_, D_>::n_chunks(FORM_);                                                    \
-        NWE_PICK_TAIL(W_, D_, SKIP_, FORM_)                                                           \
-    }
-#else
-#define NWE_PICK_SHAPE(W_, D_, SKIP_, FORM_)                \
-    if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {               \
-        launch = launch_one<W_, D_, SKIP_, FORM_>;          \
-        n_chunks = Shape<W_, D_>::n_chunks(FORM_);          \
-        NWE_PICK_TAIL(W_, D_, SKIP_, FORM_)                 \
-    }
-#endif
-    NWE_SHAPES(NWE_PICK_SHAPE)
-#undef NWE_PICK_SHAPE
-#undef NWE_PICK_TAIL
+    const ShapeRow* shape = find_shape(D, W, skip, form);
+    if (!shape) return false;
+    const RenderLauncher launch = shape->render[term ? kVariantTerm : share ? kVariantShare : kVariantPlain];
+    const RenderLauncher launch_tail = shape->render[kVariantTail];
     if (!launch) return false;
-    if (nc.n_chunks != n_chunks || (a.n_importance > 0 && nf.n_chunks != n_chunks)) return false;   // the kernel copies n_chunks bias rows
+    if (nc.n_chunks != shape->n_chunks || (a.n_importance > 0 && nf.n_chunks != shape->n_chunks)) return false;   // the kernel copies n_chunks bias rows
     int64_t full = 0;
     const int cus = device_cus();
     const int plan = plan_launch(a, decomposition, cus, &full);
@@ -222,28 +230,14 @@ int query_steps(int64_t packets, int forced) {
 }
 
 bool launch_query_mfma(const QueryArgs& a_in, const NetMfma& net, bool three_pass, int forced_steps, hipStream_t stream) {
-#ifdef NWE_ONLY_HEADLINE   // diagnostic builds hold no query kernels
-    return false;
-#else
-    const int D = net.D, W = net.W, skip = net.skip, form = net.form;
-    decltype(&launch_one_query<256, 8, 4, kFormFolded>) launch = nullptr;
-    int n_chunks = -1;
-#define NWE_PICK_QUERY(W_, D_, SKIP_, FORM_)                \
-    if (NWE_SHAPE_IS(W_, D_, SKIP_, FORM_)) {               \
-        launch = launch_one_query<W_, D_, SKIP_, FORM_>;    \
-        n_chunks = Shape<W_, D_>::n_chunks(FORM_);          \
-    }
-    NWE_SHAPES(NWE_PICK_QUERY)
-#undef NWE_PICK_QUERY
-    if (!launch || net.n_chunks != n_chunks) return false;   // the kernel copies n_chunks bias rows
+    const ShapeRow* shape = find_shape(net.D, net.W, net.skip, net.form);
+    if (!shape || !shape->query || net.n_chunks != shape->n_chunks) return false;   // the kernel copies n_chunks bias rows
     if (a_in.n_points <= 0) return true;
     QueryArgs a = a_in;
     const int64_t packets = ((int64_t)a.n_points + kQueryPacket - 1) / kQueryPacket;
     a.steps = query_steps(packets, forced_steps);
-    launch(a, net, three_pass, (unsigned)((packets + a.steps - 1) / a.steps), stream);
+    shape->query(a, net, three_pass, (unsigned)((packets + a.steps - 1) / a.steps), stream);
     return true;
-#endif
 }
 
 }  // namespace nwe
-#endif

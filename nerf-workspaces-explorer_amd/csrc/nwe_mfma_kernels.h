@@ -31,8 +31,10 @@
 //     stream; kFormNoViewDirs = trunk + _output_linear), LEAN (only rgb / depth / acc of pinhole views: every other pointer
 //     compile-time null, no register spills).
 // The templates live in nwe_mfma_config.h (shared types, tuning switches), nwe_mfma_epilogue.h, nwe_mfma_stream.h,
-// nwe_mfma_eval.h and nwe_mfma_render.h; nwe_mfma_inst_*.hip instantiate them for the shapes of nwe_mfma_shapes.h (in parallel),
-// nwe_kernel_mfma.hip plans the launches and dispatches.
+// nwe_mfma_eval.h and nwe_mfma_render.h (the render kernels, their variants and the one launcher) and nwe_mfma_query.h;
+// nwe_mfma_inst.hip instantiates them for the shapes of nwe_mfma_shapes.h, one translation unit per group of shapes and kernel
+// variant (in parallel; the Makefile generates the units), nwe_kernel_mfma.hip plans the launches and dispatches through one
+// table of the shapes.
 #pragma once
 #include "nwe_mfma_render.h"
 #include "nwe_mfma_shapes.h"

@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(256) query_mfma_kernel(QueryArgs a, NetMfma ne
 }
 
 // One query launch of a shape's kernel: `blocks` workgroups of a.steps packets each.  Explicitly instantiated per shape
-// (nwe_mfma_shapes.h, nwe_mfma_inst_query_*.hip), which instantiates the shape's two kernels (three-pass / single-pass).
+// (nwe_mfma_shapes.h, nwe_mfma_inst.hip), which instantiates the shape's two kernels (three-pass / single-pass).
 template <int W, int D, int SKIP, int FORM>
 void launch_one_query(QueryArgs a, const NetMfma& net, bool three_pass, unsigned blocks, hipStream_t stream) {
     if (blocks == 0) return;

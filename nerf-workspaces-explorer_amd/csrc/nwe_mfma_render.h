@@ -242,92 +242,69 @@ __global__ void __launch_bounds__(256) render_mfma_tail_kernel(RenderArgs a_in, 
 #undef NWE_PRIME_STREAM
 #undef NWE_EVAL_POINT
 
-// One launch of a shape's kernel for `rays` rays from ray_first on.  Explicitly instantiated per shape (nwe_mfma_shapes.h), which
-// instantiates the shape's eight kernels; the plan of a call's launches is nwe_kernel_mfma.hip's.
-template <int W, int D, int SKIP, int FORM>
-void launch_one(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_pass, bool split, int64_t ray_first, int64_t rays,
-                hipStream_t stream) {
-    if (rays <= 0) return;
-    a.ray_first = ray_first;
-    const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
-    const unsigned blocks = (unsigned)((rays + per_wg - 1) / per_wg);
-    // a queued launch (a.queue: a zeroed counter of this launch's own) deals its `blocks` work items to a larger grid
-    if (a.queue) a.queue_items = blocks;
-    const unsigned grid = a.queue ? queue_grid(blocks) : blocks;
-#define NWE_KERNEL(X3_, SPLIT_, LEAN_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, LEAN_>
-    void (*const kernels[8])(RenderArgs, NetMfma, NetMfma) = {   // index: 4 single-pass + 2 packets + 1 not lean
-        NWE_KERNEL(true, true, true),  NWE_KERNEL(true, true, false),  NWE_KERNEL(true, false, true),  NWE_KERNEL(true, false, false),
-        NWE_KERNEL(false, true, true), NWE_KERNEL(false, true, false), NWE_KERNEL(false, false, true), NWE_KERNEL(false, false, false)};
-#undef NWE_KERNEL
-    hipLaunchKernelGGL(kernels[(three_pass ? 0 : 4) + (split ? 0 : 2) + (is_lean(a) ? 0 : 1)], dim3(grid), dim3(256), 0, stream, a, nc, nf);
+// The kernel variants a shape is built in, beside its query kernels (nwe_mfma_query.h).  One instantiation unit holds one variant
+// of one group of shapes (nwe_mfma_inst.hip); the dispatcher's table has one launcher per shape and variant.
+//   plain: eight kernels (three-pass / single-pass, packets / sample split, lean / full)
+//   term:  four, early termination (TERM; lean)        share: four, shared coarse pass (SHARE; lean)
+//   tail:  two, render_mfma_tail_kernel (three-pass / single-pass, each holding both decompositions; lean)
+enum Variant { kVariantPlain, kVariantTerm, kVariantShare, kVariantTail, kVariants };
+
+// Whether a shape has a variant's kernels: the terminating and the sharing kernels exist for the product formulations,
+// kFormReference is a comparison path; every form has the plain kernels and, with them, the queue and the tail kernel.
+constexpr bool variant_built(int variant, int form) {
+    return variant == kVariantTerm || variant == kVariantShare ? form != kFormReference : true;
 }
-
-// Whether a shape has the terminating kernels (TERM): the product formulations do, kFormReference is a comparison path.
-constexpr bool term_built(int form) { return form != kFormReference; }
-
-// The same launch with early termination: the shape's four terminating kernels (three-pass / single-pass, packets / sample
-// split; lean only - the caller has checked is_lean(a), a.min_trans > 0 and a.evals).  Instantiated per shape in files of their
-// own (nwe_mfma_inst_term_*.hip); nothing for a shape that is not term_built.
-template <int W, int D, int SKIP, int FORM>
-void launch_one_term(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_pass, bool split, int64_t ray_first, int64_t rays,
-                     hipStream_t stream) {
-    if constexpr (term_built(FORM)) {
-        if (rays <= 0) return;
-        a.ray_first = ray_first;
-        const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
-        const unsigned blocks = (unsigned)((rays + per_wg - 1) / per_wg);
-#define NWE_KERNEL(X3_, SPLIT_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, true, true>
-        void (*const kernels[4])(RenderArgs, NetMfma, NetMfma) = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true),
-                                                                  NWE_KERNEL(false, false)};
-#undef NWE_KERNEL
-        hipLaunchKernelGGL(kernels[(three_pass ? 0 : 2) + (split ? 0 : 1)], dim3(blocks), dim3(256), 0, stream, a, nc, nf);
-    }
-}
-
-// Whether a shape has the sharing kernels (SHARE): as the terminating ones.
-constexpr bool share_built(int form) { return form != kFormReference; }
-
-// The same launch for the shared coarse pass (a.share: producer or consumer): the shape's four sharing kernels, lean only.
-// Instantiated per shape in files of their own (nwe_mfma_inst_share_*.hip); nothing for a shape that is not share_built.
-template <int W, int D, int SKIP, int FORM>
-void launch_one_share(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_pass, bool split, int64_t ray_first, int64_t rays,
-                      hipStream_t stream) {
-    if constexpr (share_built(FORM)) {
-        if (rays <= 0) return;
-        a.ray_first = ray_first;
-        const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
-        const unsigned blocks = (unsigned)((rays + per_wg - 1) / per_wg);
-#define NWE_KERNEL(X3_, SPLIT_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, true, false, true>
-        void (*const kernels[4])(RenderArgs, NetMfma, NetMfma) = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true),
-                                                                  NWE_KERNEL(false, false)};
-#undef NWE_KERNEL
-        hipLaunchKernelGGL(kernels[(three_pass ? 0 : 2) + (split ? 0 : 1)], dim3(blocks), dim3(256), 0, stream, a, nc, nf);
-    }
-}
-
-// Whether a shape has the tail kernel: every form that has the queue.
-constexpr bool tail_built(int) { return true; }
 #ifdef NWE_STAMPS   // a stamped launch is not lean (its stamp buffer), and stamps the tail path all the same
 constexpr bool kTailLean = false;
 #else
 constexpr bool kTailLean = true;
 #endif
 
-// The same launch through the shape's two tail kernels (three-pass / single-pass; the caller has checked the conditions of
-// launch_render_mfma and set a.tail and a.share).  `split` says which launch of the plan this is, and so the size of its items.
-// Instantiated per shape in files of their own (nwe_mfma_inst_tail_*.hip).
-template <int W, int D, int SKIP, int FORM>
-void launch_one_tail(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_pass, bool split, int64_t ray_first, int64_t rays,
-                     hipStream_t stream) {
-    if constexpr (tail_built(FORM)) {
+// workgroups (= work items) of a launch of `rays` rays (split: one packet per workgroup)
+inline unsigned mfma_workgroups(int64_t rays, bool split) {
+    const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
+    return (unsigned)((rays + per_wg - 1) / per_wg);
+}
+
+using RenderKernel = void (*)(RenderArgs, NetMfma, NetMfma);
+using RenderLauncher = void (*)(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);
+
+// One launch of a shape's kernels of one variant for `rays` rays from ray_first on; `split` says which decomposition, and so the
+// size of a work item.  Explicitly instantiated per shape and variant (nwe_mfma_shapes.h, nwe_mfma_inst.hip), which instantiates
+// the kernels; the plan of a call's launches, and the conditions under which a variant is taken, are nwe_kernel_mfma.hip's (term:
+// is_lean(a), a.min_trans > 0, a.evals; share: a.share, a.share_w; tail: a.tail, a.share).  Nothing for a shape that does not have
+// the variant, so that the instantiation exists all the same.
+template <int W, int D, int SKIP, int FORM, int VARIANT>
+void launch_one(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_pass, bool split, int64_t ray_first, int64_t rays,
+                hipStream_t stream) {
+    if constexpr (variant_built(VARIANT, FORM)) {
         if (rays <= 0) return;
         a.ray_first = ray_first;
-        const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
-        const unsigned blocks = (unsigned)((rays + per_wg - 1) / per_wg);
-        if (a.queue) a.queue_items = blocks;
-        const unsigned grid = a.queue ? queue_grid(blocks) : blocks;
-        if (three_pass) hipLaunchKernelGGL((render_mfma_tail_kernel<W, D, SKIP, true, FORM, kTailLean>), dim3(grid), dim3(256), 0, stream, a, nc, nf);
-        else hipLaunchKernelGGL((render_mfma_tail_kernel<W, D, SKIP, false, FORM, kTailLean>), dim3(grid), dim3(256), 0, stream, a, nc, nf);
+        const unsigned items = mfma_workgroups(rays, split);
+        // a queued launch (a.queue: a zeroed counter of this launch's own) deals its work items to a larger grid; the
+        // terminating and the sharing kernels take no tickets, so their launches are never queued
+        const bool queued = (VARIANT == kVariantPlain || VARIANT == kVariantTail) && a.queue;
+        if (queued) a.queue_items = items;
+        const unsigned grid = queued ? queue_grid(items) : items;
+        RenderKernel kernel;
+        if constexpr (VARIANT == kVariantPlain) {
+#define NWE_KERNEL(X3_, SPLIT_, LEAN_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, LEAN_>
+            const RenderKernel kernels[8] = {   // index: 4 single-pass + 2 packets + 1 not lean
+                NWE_KERNEL(true, true, true),  NWE_KERNEL(true, true, false),  NWE_KERNEL(true, false, true),  NWE_KERNEL(true, false, false),
+                NWE_KERNEL(false, true, true), NWE_KERNEL(false, true, false), NWE_KERNEL(false, false, true), NWE_KERNEL(false, false, false)};
+#undef NWE_KERNEL
+            kernel = kernels[(three_pass ? 0 : 4) + (split ? 0 : 2) + (is_lean(a) ? 0 : 1)];
+        } else if constexpr (VARIANT == kVariantTail) {
+            const RenderKernel kernels[2] = {render_mfma_tail_kernel<W, D, SKIP, true, FORM, kTailLean>,
+                                             render_mfma_tail_kernel<W, D, SKIP, false, FORM, kTailLean>};
+            kernel = kernels[three_pass ? 0 : 1];
+        } else {   // lean only: the caller has checked
+#define NWE_KERNEL(X3_, SPLIT_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, true, VARIANT == kVariantTerm, VARIANT == kVariantShare>
+            const RenderKernel kernels[4] = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true), NWE_KERNEL(false, false)};
+#undef NWE_KERNEL
+            kernel = kernels[(three_pass ? 0 : 2) + (split ? 0 : 1)];
+        }
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, a, nc, nf);
     }
 }
 
