@@ -300,6 +300,10 @@ int nwe_packed_copy(const nwe_ctx *ctx, int which, void *host_dst, int64_t bytes
 int64_t nwe_packed_bias_count(const nwe_ctx *ctx, int which);
 int nwe_packed_bias_copy(const nwe_ctx *ctx, int which, float *host_dst, int64_t count);
 float nwe_packed_scale(const nwe_ctx *ctx, int which);
+/* 1 if every value the colour layers of network `which` hold as packed for the MFMA kernels is finite (the folded view layer
+ * formed in fp64 with its view-direction columns, the rgb head, both biases), 0 if not or if the network is not packed folded,
+ * -1 if it has not been set.  Decided once per nwe_set_network; no device needed.  See nwe_debug_set_colour_skip. */
+int nwe_packed_colour_finite(const nwe_ctx *ctx, int which);
 
 /* Test hook: the NEXT nwe_render_rays call takes the fine-pass sample depths from z_dev (DEVICE [n_rays, S],
  * sorted per ray) instead of its own importance sampling; cleared after that call.  Lets a test feed the
@@ -522,6 +526,19 @@ int nwe_debug_last_tail(nwe_ctx *ctx, unsigned *stolen);
  * was not below the third counter's final value), 0 when the path was not taken.  stolen + rendered == the plan's split items
  * says that every item was rendered exactly once; with the path's condition (the surplus covers every item) rendered is 0. */
 int nwe_debug_last_tail_rest(nwe_ctx *ctx, unsigned *rendered);
+
+/* The hollow path of the lean MFMA kernels ("Samples without density"): in the pass that produces the
+ * outputs, a wave whose 32 rays all have sigma_raw <= 0 at a sample leaves out the colour layers of that evaluation - the
+ * sample weighs 0 on every one of them.  No bit of any output changes wherever the colour the full path computes there is not
+ * NaN; the one deliberate difference is named in DESIGN.md.
+ *   mode 0: off - every evaluation runs the colour layers
+ *   mode 1 (default): on for a network whose colour layers are finite as packed (nwe_packed_colour_finite) and for waves whose
+ *           rays all have finite view directions
+ *   mode 2: test hook - as 1 without the pack-time condition, so that a NaN planted in the colour head shows where the path ran
+ * NWE_COLOUR_SKIP=0 / 1 in the environment sets the mode a new context starts with.  Calls that are not lean, NWE_PREC_F32, the
+ * unfolded and the no-view-dirs formulations and nwe_query_points have no such path. */
+int nwe_debug_set_colour_skip(nwe_ctx *ctx, int mode);
+int nwe_debug_get_colour_skip(const nwe_ctx *ctx);              /* -1 for a null context */
 
 /* Diagnostic builds only (make -C csrc stamps): DEVICE buffer of 14 uint64 per wave that a -DNWE_STAMPS build of the MFMA
  * kernel fills with s_memtime cycle sums (tools/stamp_run.py); the product build never touches it.  NULL switches it off.

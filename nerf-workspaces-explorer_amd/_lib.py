@@ -27,7 +27,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_set_separate_passes", "nwe_get_separate_passes",
            "nwe_debug_set_work_queue", "nwe_debug_get_work_queue", "nwe_debug_get_work_queue_backfill", "nwe_debug_queue_grid", "nwe_debug_last_queue",
            "nwe_debug_get_work_queue_tail", "nwe_debug_last_tail", "nwe_debug_last_tail_rest",
-           "nwe_query_points", "nwe_last_query_ms", "nwe_debug_set_query_steps")
+           "nwe_query_points", "nwe_last_query_ms", "nwe_debug_set_query_steps",
+           "nwe_packed_colour_finite", "nwe_debug_set_colour_skip", "nwe_debug_get_colour_skip")
 
 
 class Outputs(C.Structure):
@@ -116,6 +117,9 @@ def load() -> C.CDLL:
         "nwe_query_points": (I, [P, I, P, I64, P, I64, I, C.POINTER(PointOutputs), P]),
         "nwe_last_query_ms": (F, [P]),
         "nwe_debug_set_query_steps": (I, [P, I]),
+        "nwe_packed_colour_finite": (I, [P, I]),
+        "nwe_debug_set_colour_skip": (I, [P, I]),
+        "nwe_debug_get_colour_skip": (I, [P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -129,6 +129,7 @@ struct nwe_ctx {
     int work_queue = -1;      // nwe_debug_set_work_queue; a new context takes NWE_WORK_QUEUE=0|1 from the environment
     bool backfill = true;     // the hybrid plan's second launch on the slot's own stream; NWE_WORK_QUEUE_BACKFILL=0: behind the first
     bool tail = true;         // the hybrid plan's split items in the packets launch's tail; NWE_WORK_QUEUE_TAIL=0: as without it
+    int colour_skip = 1;      // nwe_debug_set_colour_skip; NWE_COLOUR_SKIP=0: a new context starts with 0
     int last_plan = -1;       // nwe_debug_last_plan
     unsigned long long* stamps = nullptr;   // nwe_debug_set_stamps
     const float *trn_t = nullptr, *trn_nc = nullptr, *trn_nf = nullptr, *trn_u = nullptr;   // nwe_set_train_tables, one call
@@ -364,6 +365,13 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
     a.stamps = ctx->stamps;   // only read by -DNWE_STAMPS builds of the kernel (nwe_debug_set_stamps)
     if (a.n_rays <= 0) return NWE_OK;
     const NetState &nc = ctx->net[0], &nf = ctx->net[ctx->ni > 0 ? 1 : 0];
+    // the launch's own descriptors: whether its lean kernels may take the hollow path with this network (nwe_debug_set_colour_skip)
+    const auto with_skip = [&](const NetState& n) {
+        NetMfma m = n.mf;
+        m.colour_skip = ctx->colour_skip == 2 || (ctx->colour_skip == 1 && n.p.colour_finite) ? 1 : 0;
+        return m;
+    };
+    const NetMfma mf_c = with_skip(nc), mf_f = with_skip(nf);
     a.min_trans = ctx->min_trans;
     if (a.min_trans > 0.f) {   // the launch's waves add their ray evaluations to the slot's own word (its last reader: prepare_slot)
         HIPCHK(ctx, slot.evals.reserve(1));
@@ -439,7 +447,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         }
     }
     // the descriptors of the coarse and of the fine launch: (coarse, fine) for one fused kernel, its own network twice otherwise
-    const NetMfma &prod_f = separate ? nc.mf : nf.mf, &cons_c = separate ? nf.mf : nc.mf;
+    const NetMfma &prod_f = separate ? mf_c : mf_f, &cons_c = separate ? mf_f : mf_c;
     const int rc = record_launch(ctx, slot, stream, [&]() -> int {
         slot.has_mid = false; slot.rays_first = slot.rays_total = a.n_rays;
         slot.q_items[0] = slot.q_items[1] = slot.q_grid[0] = slot.q_grid[1] = 0; slot.side_used = false; slot.tail_items = 0;
@@ -450,7 +458,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         const char* shapes_differ = "coarse and fine networks must have the same shape for the MFMA kernel";
         if (coarse_launch) {
             if (precision == NWE_PREC_F32) launch_render_f32(prod, nc.f32, nf.f32, stream);
-            else if (!launch_render_mfma(prod, nc.mf, prod_f, precision == NWE_PREC_F16X3, ctx->decomposition, stream, nullptr))
+            else if (!launch_render_mfma(prod, mf_c, prod_f, precision == NWE_PREC_F16X3, ctx->decomposition, stream, nullptr))
                 return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
             if (full && prod.out.flags)
                 hipLaunchKernelGGL(or_masked_flags_kernel, dim3(1), dim3(1), 0, stream, prod.out.flags,
@@ -470,7 +478,7 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
             info.side = slot.side; info.fork = slot.ev_fork; info.join = slot.ev_join;
             info.tail = ctx->tail;
         }
-        if (!launch_render_mfma(a, cons_c, nf.mf, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info)) {
+        if (!launch_render_mfma(a, cons_c, mf_f, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info)) {
             if (!info.side_used) return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
             // the side launch is queued and the caller's stream could not be made to wait for it: nothing of this call may
             // still run when the call returns its error
@@ -677,6 +685,8 @@ int nwe_create(nwe_ctx** out, int device) {
         if (e[0] == '0' && !e[1]) c->backfill = false;
     if (const char* e = std::getenv("NWE_WORK_QUEUE_TAIL"))       // A/B timing of the tail path on one library
         if ((e[0] == '0' || e[0] == '1') && !e[1]) c->tail = e[0] == '1';
+    if (const char* e = std::getenv("NWE_COLOUR_SKIP"))           // A/B timing of the hollow path on one library
+        if ((e[0] == '0' || e[0] == '1') && !e[1]) c->colour_skip = e[0] - '0';
     if (!c->host_only) {
         const hipError_t e = hipSetDevice(device);
         if (e != hipSuccess) { delete c; return fail(nullptr, NWE_ERR_HIP, std::string("nwe_create: ") + hipGetErrorString(e)); }
@@ -946,6 +956,7 @@ int64_t nwe_flops_per_eval(const nwe_ctx* c, int which) { const NetState* n = se
 int64_t nwe_packed_bytes(const nwe_ctx* c, int which) { const NetState* n = set_net(c, which); return n ? (int64_t)n->p.stream.size() : 0; }
 int64_t nwe_packed_bias_count(const nwe_ctx* c, int which) { const NetState* n = set_net(c, which); return n ? (int64_t)n->p.bias_tab.size() : 0; }
 float nwe_packed_scale(const nwe_ctx* c, int which) { const NetState* n = set_net(c, which); return n ? n->p.w_scale : 0.f; }
+int nwe_packed_colour_finite(const nwe_ctx* c, int which) { const NetState* n = set_net(c, which); return n ? (n->p.colour_finite ? 1 : 0) : -1; }
 
 int nwe_packed_copy(const nwe_ctx* c, int which, void* host_dst, int64_t bytes) { const NetState* n = set_net(c, which); return copy_out(n ? &n->p.stream : nullptr, host_dst, bytes); }
 int nwe_packed_bias_copy(const nwe_ctx* c, int which, float* host_dst, int64_t count) { const NetState* n = set_net(c, which); return copy_out(n ? &n->p.bias_tab : nullptr, host_dst, count); }
@@ -957,6 +968,8 @@ int nwe_debug_set_fold(nwe_ctx* c, int on) { return set_on(c, [&] { c->fold = on
 int nwe_debug_set_decomposition(nwe_ctx* c, int mode) { return set_on(mode < -1 || mode > 2 ? nullptr : c, [&] { c->decomposition = mode; }); }
 int nwe_debug_set_work_queue(nwe_ctx* c, int mode) { return set_on(mode < -1 || mode > 1 ? nullptr : c, [&] { c->work_queue = mode; }); }
 int nwe_debug_get_work_queue(const nwe_ctx* c) { return c ? c->work_queue : -2; }
+int nwe_debug_set_colour_skip(nwe_ctx* c, int mode) { return set_on(mode < 0 || mode > 2 ? nullptr : c, [&] { c->colour_skip = mode; }); }
+int nwe_debug_get_colour_skip(const nwe_ctx* c) { return c ? c->colour_skip : -1; }
 int nwe_debug_get_work_queue_backfill(const nwe_ctx* c) { return c ? (c->backfill ? 1 : 0) : -1; }
 unsigned nwe_debug_queue_grid(unsigned items) { return queue_grid(items); }
 int nwe_debug_last_queue(nwe_ctx* c, unsigned* items2, unsigned* grid2, unsigned* taken2, int* side_stream) {

@@ -40,6 +40,9 @@ constexpr int kLongPieces = 8;
 #ifndef NWE_COARSE_DENSITY_ONLY
 #define NWE_COARSE_DENSITY_ONLY 1   // density-only coarse evaluations in lean frames (mlp_eval); 0 = every evaluation runs the view layer and rgb head
 #endif
+#ifndef NWE_COLOUR_SKIP
+#define NWE_COLOUR_SKIP 1   // the hollow path of lean evaluations whose ray packet has no density (mlp_eval); 0 = not built.  The run-time switch is nwe_debug_set_colour_skip
+#endif
 // Cache policy of the weight stream (NWE_GLDS_POLICY, timing experiments): 0 default, 1 sc1 (bypass the CU's vector L1, which
 // never sees a piece twice), 2 nt, 3 sc0 sc1, 4 sc1 nt.  It is spliced into an instruction string, so it stays a macro.
 #ifndef NWE_GLDS_POLICY
@@ -58,7 +61,7 @@ constexpr int kLongPieces = 8;
 #endif
 constexpr int kDmaStride = NWE_DMA_STRIDE;
 constexpr bool kSpreadBias = NWE_SPREAD_BIAS != 0, kOneWait = NWE_ONE_WAIT != 0, kSplitReads = NWE_SPLIT_READS != 0;
-constexpr bool kPeelSkip = NWE_PEEL_SKIP != 0, kCoarseDensityOnly = NWE_COARSE_DENSITY_ONLY != 0;
+constexpr bool kPeelSkip = NWE_PEEL_SKIP != 0, kCoarseDensityOnly = NWE_COARSE_DENSITY_ONLY != 0, kColourSkip = NWE_COLOUR_SKIP != 0;
 // -DNWE_STAMPS (`make stamps`): a DIAGNOSTIC build with in-kernel s_memtime stamps; NWE_STAMP(...) is its code, nothing otherwise.
 #ifdef NWE_STAMPS
 #define NWE_STAMP(...) __VA_ARGS__

@@ -1,5 +1,7 @@
 // One MLP evaluation for a wave's 32 points: network shape, the tile loop, layers, encodings (see nwe_mfma_kernels.h).
 #pragma once
+#include <cfloat>
+
 #include "nwe_mfma_epilogue.h"
 #include "nwe_mfma_stream.h"
 
@@ -231,6 +233,25 @@ __device__ __forceinline__ void tile_mma(WalkerT& wk, Frags& F, int lane, Pend& 
     wk.tile_done();
 }
 
+// tile_mma of a HOLLOW wave (mlp_eval: a wave whose 32 rays all have sigma <= 0 owes the workgroup nothing of a colour tile but
+// its quarter of the weight stream): no MFMA, no fragment read, no epilogue.  What it keeps is everything the other three waves
+// count on - the same LDS-DMA pieces of the same chunks in the same order on the same side of the tile's one barrier, begin() of
+// chunk T+2 behind it, tile_done() - for a tile without optional k-steps or extra pieces (the view tiles and the rgb head have
+// neither).  The wait in front of the barrier is the full one: this wave multiplies with nothing, so it keeps no read in flight.
+template <class C, class WalkerT>
+__device__ __forceinline__ void tile_pass(WalkerT& wk) {
+    constexpr int NQ = C::NKH + C::NKD, NB = C::NB, NA = C::NA;
+    static_assert(C::NKP == 0, "a hollow tile has no optional k-steps");
+    using DP = DmaPlan<NB, NA, NQ>;
+    static_for<0, DP::REST>([&](auto jc) __attribute__((always_inline)) { wk.piece(PD + decltype(jc)::value, NB >= kLongPieces ? NB - 2 : -1); });
+    wk.template sync<false>();
+    if constexpr (NA > 0) {
+        wk.begin(NA, wk.b, 2);
+        static_for<0, (NA < PD ? NA : PD)>([&](auto jc) __attribute__((always_inline)) { wk.piece(decltype(jc)::value); });
+    }
+    wk.tile_done();
+}
+
 // A full layer of NT tiles reading X (+ gamma k-steps) and writing Y.  Tile rt accumulates into P[rt&1] while the
 // epilogue of the tile before it runs: for rt = 0 that is the LAST tile of the previous layer (in P1, destined for
 // k-steps 2*NT-2, 2*NT-1 of X itself), for rt > 0 tile rt-1 of this layer (destined for Y).  On return P1 holds
@@ -327,13 +348,13 @@ struct ViewDma {
     using Plan0 = EpiPlan<X3, S::KH, S::KH + S::KD, true, DmaPlan<nb(0), na(0), S::KH + S::KD>::mask()>;
 };
 
-// View-layer tiles RT..NTV-1 (compile-time recursion: the DMA schedule and the ring phase depend on RT).  Each tile has
+// View-layer tiles RT..END-1 (END = NTV unless the caller runs tile 0 apart; compile-time recursion: the DMA schedule and the ring phase depend on RT).  Each tile has
 // KH + KD k-steps, which shifts the fragment ring by (KH+KD) mod (PD+1) per tile.
 // SIGMA_TILE (the unfolded formulation): tile 0 follows the alpha tile, which has no activation output to finish; tile RT
 // accumulates in P[(RT+1)&1].  !SIGMA_TILE (FOLD): tile 0 follows the last trunk tile directly (pending in P1) and runs its
 // epilogue - ReLU into the last two k-steps of X itself, and the last share of the alpha dot product (row NT-1 of dot_tab) -
 // so tile RT accumulates in P[RT&1].
-template <int RT, int W, int D, bool X3, bool SIGMA_TILE, class WalkerT>
+template <int RT, int W, int D, bool X3, bool SIGMA_TILE, int END = W / 64, class WalkerT>
 __device__ __forceinline__ void view_tiles(WalkerT& wk, Frags& F, int lane, h8* Ahi, h8* Alo, const h8* GDhi,
                                            const h8* GDlo, h8* Bhi, h8* Blo, Pend& P0, Pend& P1, float inv_scale,
                                            const float* dot_tab = nullptr, float* dot = nullptr) {
@@ -355,7 +376,16 @@ __device__ __forceinline__ void view_tiles(WalkerT& wk, Frags& F, int lane, h8* 
     } else {
         tile_mma<TileCfg<K, X3, CH, kPend>>(wk, F, lane, cur, prev, inv_scale, 0.f, Ahi, Alo, Bhi, Blo, 2 * RT - 2, GDhi, GDlo);
     }
-    if constexpr (RT + 1 < S::NTV) view_tiles<RT + 1, W, D, X3, SIGMA_TILE>(wk, F, lane, Ahi, Alo, GDhi, GDlo, Bhi, Blo, P0, P1, inv_scale);
+    if constexpr (RT + 1 < END) view_tiles<RT + 1, W, D, X3, SIGMA_TILE, END>(wk, F, lane, Ahi, Alo, GDhi, GDlo, Bhi, Blo, P0, P1, inv_scale);
+}
+
+// View tiles RT..NTV-1 of a hollow wave (tile_pass): the chunks and the DMA schedule of view_tiles.
+template <int RT, int W, int D, bool X3, class WalkerT>
+__device__ __forceinline__ void view_pass(WalkerT& wk) {
+    using S = Shape<W, D>;
+    using V = ViewDma<W, D, X3>;
+    tile_pass<TileCfg<KSteps<0, S::KH, S::KD>, X3, Chunks<V::nb(RT), V::na(RT)>, kNoEpi>>(wk);
+    if constexpr (RT + 1 < S::NTV) view_pass<RT + 1, W, D, X3>(wk);
 }
 
 // Whether mlp_eval has the density-only path for a shape: every folded shape except those whose gamma(x) skip input enters the
@@ -364,6 +394,15 @@ __device__ __forceinline__ void view_tiles(WalkerT& wk, Frags& F, int lane, h8* 
 template <int D, int SKIP>
 constexpr bool density_only_built(int form) {
     return kCoarseDensityOnly && form == kFormFolded && !(SKIP >= 0 && SKIP / 2 == D / 2 - 1);
+}
+
+// Whether the LEAN render kernels of a shape have the hollow path of mlp_eval (colour_skip): the folded shapes that have the
+// density-only path.  In their lean frames the evaluations that are not density-only are exactly those of the pass that produces
+// the outputs, so the one word per wave that allows the path (render kernel prologue) is that pass's.  The shapes without
+// (6-deep with skips (4,)) evaluate a coarse colour nobody reads and keep evaluating every colour.
+template <int D, int SKIP>
+constexpr bool colour_skip_built(int form) {
+    return kColourSkip && density_only_built<D, SKIP>(form);
 }
 
 // One MLP evaluation for the wave's 32 points.  nerf/models/nerf_model.py:45-83.
@@ -380,10 +419,14 @@ constexpr bool density_only_built(int form) {
 // (copies in rows 4..7 for the upper lane half; the reference ignores the fifth channel too: model_utils.py:62,71).
 // density_only (wave-uniform; honoured where density_only_built): sigma is all the caller reads, so the evaluation ends with
 // the trunk (see below) and returns o_r = o_g = o_b = 0.
+// CSKIP (the LEAN render kernels where colour_skip_built; skip_word = the wave's word in LDS, see the prologue of the render
+// kernel): an evaluation that is not density_only takes the hollow path below if the word is set and no ray of the wave has
+// density.
 // On entry chunks 0 and 1 of the stream are visible / in flight and F holds the first PD k-steps of chunk 0.
-template <int W, int D, int SKIP, bool X3, int FORM, class WalkerT>
+template <int W, int D, int SKIP, bool X3, int FORM, bool CSKIP = false, class WalkerT>
 __device__ __forceinline__ void mlp_eval(WalkerT& wk, Frags& F, int lane, float inv_scale, h8* Ghi, h8* Glo, const char* gd_lds,
-                                         const float* dot_tab, bool density_only, float& o_r, float& o_g, float& o_b, float& o_s) {
+                                         const float* dot_tab, bool density_only, float& o_r, float& o_g, float& o_b, float& o_s,
+                                         const int* skip_word = nullptr) {
     using S = Shape<W, D>;
     static_assert(D % 2 == 0, "trunk depth must be even");
     static_assert(SKIP < 0 || SKIP % 2 == 0, "skip layer index must be even");
@@ -493,7 +536,49 @@ __device__ __forceinline__ void mlp_eval(WalkerT& wk, Frags& F, int lane, float 
         GDhi[k] = *reinterpret_cast<const h8*>(gd_lds + (2 * k) * kTileBytes);
         if (X3) GDlo[k] = *reinterpret_cast<const h8*>(gd_lds + (2 * k + 1) * kTileBytes);
     }
-    if constexpr (FOLD) {
+    if constexpr (FOLD && CSKIP) {
+        static_assert(colour_skip_built<D, SKIP>(FORM), "the hollow path: shapes of colour_skip_built only");
+        // The hollow path.  A sample with sigma_raw <= 0 has alpha = 1 - exp(-max(sigma_raw, 0) dist) = 0 and weighs 0, so in
+        // r + w c its colour c adds +0 whatever finite value it has (Composite::shade, ::accumulate): nothing the view tiles 1..
+        // and the rgb head compute for it reaches an output of a lean frame.  sigma is complete once view tile 0 has run the
+        // last trunk tile's epilogue - the same FMAs into `sig` in the same order as ever, so sigma has the same bits - and if
+        // NONE of the wave's 32 rays has density there (and the launch allows it: the word), the wave leaves out the rest of the
+        // evaluation's arithmetic: NTV - 1 view tiles and the rgb head, 186 of 3120 MFMAs at 8x256, with their fragment reads and
+        // epilogues.  The colour it returns is 0 where the full path returns a finite value that is multiplied by a zero weight.
+        // -inf and NaN never pass the test: there the weight is NaN and so is every output, on either path.
+        // The word is set only where the full path's colour cannot be NaN for a finite sigma by way of its inputs: colour layers
+        // finite as packed (Packed::colour_finite) and a finite gamma(d) for every ray of the wave.  What is left is an
+        // activation above fp16's range under a finite sigma.
+        // The branch is wave-uniform, NOT workgroup-uniform: the other waves may run the full path, and they need this wave's
+        // quarter of every chunk and its arrival at every barrier.  tile_pass keeps both, tile for tile, so:
+        //   * every buffer release still rests on a barrier plus each wave's own waits in front of it.  A hollow wave only
+        //     arrives early at barriers it still takes part in; the pieces it issues behind barrier T are the ones tile_mma
+        //     issues there, into the buffer and tail slot that barrier released whatever the timing (Walker timeline).
+        //   * on entry the wave may still have the prefetched fragments of view tile 1 in flight (chunk T, which nothing writes
+        //     before barrier T + 1); its full wait in front of barrier T retires them.  From there on it has no read outstanding
+        //     anywhere, so the tail-slot argument - no write where a read of the old content can be pending - holds for it trivially.
+        //   * the end of the evaluation is the state the density-only comment describes: no DMA in flight (the rgb head streams
+        //     nothing behind it; the last piece was waited for at the last view tile's barrier), no read of a chunk buffer
+        //     pending in any wave behind the rgb head's barrier, the next evaluation's first pieces write buffers 0 and 1 only.
+        //   * the pieces of a group stay in order with no other group between them (M0, tools/check_m0.py): tile_pass issues
+        //     tile_mma's pieces in tile_mma's order, and the two paths join only at the end of the evaluation.
+        const int allow = *skip_word;   // with the gamma(d) fragments: long retired when view tile 0 ends
+        view_tiles<0, W, D, X3, false, 1>(wk, F, lane, Bhi, Blo, GDhi, GDlo, Ahi, Alo, P0, P1, inv_scale, dot_tab, &sig);
+        const float sigma = sigma_of();
+        o_s = sigma;
+        if (__all(allow != 0 && sigma <= 0.f && sigma >= -FLT_MAX)) {
+            view_pass<1, W, D, X3>(wk);
+            tile_pass<TileCfg<KSteps<0, S::KV>, X3, Chunks<0, 0, false>, kNoEpi>>(wk);
+            o_r = o_g = o_b = 0.f;
+            return;
+        }
+        view_tiles<1, W, D, X3, false>(wk, F, lane, Bhi, Blo, GDhi, GDlo, Ahi, Alo, P0, P1, inv_scale);
+        tile_mma<TileCfg<KSteps<0, S::KV>, X3, Chunks<0, 0, false>, kPend | kFeeds>>(wk, F, lane, P0, P1, inv_scale, 0.f, Ahi, Alo, Ahi, Alo, LV);
+        o_r = pend_value(P0, 0, inv_scale);
+        o_g = pend_value(P0, 1, inv_scale);
+        o_b = pend_value(P0, 2, inv_scale);
+        return;
+    } else if constexpr (FOLD) {
         // folded view layer: [h (B), gamma(d)] -> A[0..KV), ReLU (nerf_model.py:64-70 with W_v[:, :W] . W_f multiplied out).
         // Its first tile runs the epilogue of the last trunk tile (P1, NT even): ReLU into the last two k-steps of B itself and
         // the last share of the alpha dot product.  Tile RT accumulates in P[RT & 1], so the last one (NTV even) is in P1.

@@ -22,8 +22,9 @@ struct Smem {
     static constexpr int XOFF = TOFF + (2 * kMaxSamples + kMaxImportance) * 4;         // sample-split mode: shaded samples, 2 buffers
     static constexpr int LOFF = XOFF + (SPLIT ? 2 * kWaves * kRaysPerWave * 16 : 0);   // three tail slots of two tiles (Walker)
     static constexpr int GOFF = LOFF + 3 * 2 * kTileBytes;                           // gamma(d) fragments, (hi, lo) per k-step and wave
-    static constexpr int TOTAL = GOFF + kWaves * 2 * S::KD * kTileBytes;
-    static_assert(XOFF % 16 == 0 && LOFF % 16 == 0 && GOFF % 16 == 0 && TOTAL <= 160 * 1024, "LDS budget");
+    static constexpr int KOFF = GOFF + kWaves * 2 * S::KD * kTileBytes;                // one word per wave: the hollow path is allowed (colour_skip_built)
+    static constexpr int TOTAL = KOFF + kWaves * 4;
+    static_assert(XOFF % 16 == 0 && LOFF % 16 == 0 && GOFF % 16 == 0 && KOFF % 16 == 0 && TOTAL % 16 == 0 && TOTAL <= 160 * 1024, "LDS budget");
 };
 
 // Two work decompositions, same arithmetic in the same order (results are bit-identical):
@@ -85,7 +86,8 @@ __device__ __forceinline__ void read_raw(const float* raw_in, int64_t at, float&
         }                                                                                                                          \
         BEHIND_READS                                                                                                               \
         NWE_STAMP(const unsigned long long t2 = __builtin_amdgcn_s_memtime(); wk.st_t0 = t2; st_sync += t2 - t1;)                  \
-        mlp_eval<W, D, SKIP, X3, FORM>(wk, F, lane, net.inv_scale, Ghi, Glo, gd_lds, dot_tab, density_only, rr, rg, rb, rs);       \
+        mlp_eval<W, D, SKIP, X3, FORM, CSKIP>(wk, F, lane, net.inv_scale, Ghi, Glo, gd_lds, dot_tab, density_only, rr, rg, rb, rs, \
+                                              skip_word);                                                                          \
         NWE_STAMP(st_mlp += __builtin_amdgcn_s_memtime() - t2;)                                                                    \
     }
 

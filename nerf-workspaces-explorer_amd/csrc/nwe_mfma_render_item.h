@@ -66,6 +66,26 @@
         }
     }
 
+    // The hollow path of mlp_eval (colour_skip_built; lean kernels): one word per wave says whether the evaluations of the pass
+    // that produces the outputs may leave out the colour layers where no ray of the wave has density.  Set if the launch allows it
+    // for that pass's network (NetMfma::colour_skip) and gamma(d) as the view tiles multiply with it is finite for every ray of the
+    // wave: a zero or NaN rotation gives NaN there while the sample points, and so sigma, stay finite.  Written and read by the
+    // same wave, so it needs no barrier; it costs the sample loop no register (mlp_eval reads it with the gamma(d) fragments).
+    constexpr bool CSKIP = LEAN && colour_skip_built<D, SKIP>(FORM);
+    const int* skip_word = reinterpret_cast<const int*>(smem + SM::KOFF) + wave;
+    if constexpr (CSKIP) {
+        bool gd_ok = true;
+        const h8* gdh = reinterpret_cast<const h8*>(gd_lds);
+#pragma unroll
+        for (int k = 0; k < S::KD; ++k) {
+            const h8 g = gdh[(2 * k) * (kTileBytes / 16)];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) gd_ok = gd_ok && __builtin_fabsf((float)g[j]) <= 65504.f;   // lo = v - hi is finite where hi is
+        }
+        const int allow = (ni > 0 ? nf : nc).colour_skip != 0 && __all(gd_ok);
+        if (lane == 0) *reinterpret_cast<int*>(smem + SM::KOFF + wave * 4) = allow;
+    }
+
     FineSampler fs;
     // coarse weights, then the cdf: one buffer per wave (= per packet), or ONE for the workgroup's single packet (SPLIT), which
     // wave 0 alone writes - all four waves compute the same values - and everyone reads behind a workgroup barrier

@@ -125,6 +125,17 @@ void pack_mfma(Packed& p, const NetShape& n, int form, const float* const* w, co
     int e = 0;
     if (wmax > 0.0 && std::isfinite(wmax)) { e = 14 - (int)std::ceil(std::log2(wmax)); e = std::min(std::max(e, -14), 30); }
     p.w_scale = std::ldexp(1.f, e);
+    p.colour_finite = false;
+    if (folded) {
+        // what the kernel multiplies with: hi = fp16(v * scale) (lo = fp16(v * scale - hi) is finite whenever hi is), fp32 biases
+        bool ok = true;
+        const auto fits = [&](double v) { return std::isfinite(v) && std::fabs(v * (double)p.w_scale) < 65520.0; };
+        for (double v : wv) ok = ok && fits(v);
+        for (double v : bv) ok = ok && std::fabs(v) <= 3.4028234663852886e38;   // NaN compares false
+        for (int k = 0; k < 3 * (W / 2); ++k) ok = ok && fits((double)w[irgb][k]);
+        for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(b[irgb][k]);
+        p.colour_finite = ok;
+    }
     auto layer = [&](int li, int n_out, int ld, int n_tiles, int dup4, const std::vector<Segment>& segs) {
         RowMap rows{n_out, dup4};
         for (int rt = 0; rt < n_tiles; ++rt) put_chunk(p, w[li], b[li], ld, rows, rt, segs);

@@ -30,6 +30,8 @@ struct NetMfma {
     float inv_scale;        // weights are stored multiplied by 1/inv_scale (a power of two)
     int D, W, skip;
     int form;               // Form: which formulation of the network the stream holds
+    int colour_skip;        // set per launch, never packed (nwe_debug_set_colour_skip): the lean kernels may leave out the colour layers
+                            // of a wave's evaluation whose 32 rays all have sigma <= 0 (mlp_eval: the hollow path)
 };
 constexpr int kTileBytes = 1024;
 
@@ -57,6 +59,10 @@ struct Packed {
     std::vector<float> bias_tab;   // MFMA kernel: 32 floats per chunk, then (folded) the dot rows of _alpha_linear
     int n_chunks = 0;              // chunks of the stream = bias rows in front of the dot rows
     float w_scale = 1.f;           // power of two the packed weights are multiplied by
+    bool colour_finite = false;    // folded MFMA stream: every value the colour layers hold AS PACKED is finite - the folded view layer
+                                   // formed in fp64 with its gamma(d) columns and the rgb head, scaled and rounded to fp16, and both
+                                   // biases rounded to fp32.  Then a sample of zero weight contributes 0 x (finite colour) = 0 whatever
+                                   // its colour is, the condition of the hollow path (mlp_eval).  Not part of stream or bias table.
 };
 
 // w[i], b[i]: layer i as [out, in] and [out]; D trunk layers, then views, feature, alpha, rgb or (in_dir == 0) _output_linear

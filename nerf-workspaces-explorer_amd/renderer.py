@@ -325,6 +325,14 @@ class Renderer:
         self._check(self._lib.nwe_debug_last_tail_rest(self._ctx, C.byref(n)), "nwe_debug_last_tail_rest")
         return int(n.value)
 
+    def debug_set_colour_skip(self, mode: int) -> None:
+        """The hollow path of the lean MFMA kernels (include/nwe.h): 0 = off, 1 = on where the network's colour layers are finite as
+        packed (the default, or what NWE_COLOUR_SKIP set when the renderer was created), 2 = test hook without that condition."""
+        self._check(self._lib.nwe_debug_set_colour_skip(self._ctx, int(mode)), "nwe_debug_set_colour_skip")
+
+    def debug_get_colour_skip(self) -> int:
+        return int(self._lib.nwe_debug_get_colour_skip(self._ctx))
+
     def debug_get_work_queue_tail(self) -> bool:
         """Whether this renderer may take the tail path: fixed when it was created (NWE_WORK_QUEUE_TAIL=0 in the environment then)."""
         return bool(self._lib.nwe_debug_get_work_queue_tail(self._ctx))
@@ -497,6 +505,10 @@ class Renderer:
 
     def packed_scale(self, which: int) -> float:
         return float(self._lib.nwe_packed_scale(self._ctx, which))
+
+    def packed_colour_finite(self, which: int) -> bool:
+        """Whether the colour layers of network `which` are finite as packed (include/nwe.h: nwe_packed_colour_finite)."""
+        return int(self._lib.nwe_packed_colour_finite(self._ctx, which)) == 1
 
     def selftest(self):
         rep = (C.c_int32 * 8)()

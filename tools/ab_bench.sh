@@ -6,19 +6,21 @@
 #            static           the product library with NWE_WORK_QUEUE=0: the hardware's static dealing of workgroups
 #            nobackfill       the product library with NWE_WORK_QUEUE_BACKFILL=0: queued launches one after the other
 #            notail           the product library with NWE_WORK_QUEUE_TAIL=0: the split items in a launch of their own, beside the packets
+#            noskip           the product library with NWE_COLOUR_SKIP=0: every evaluation runs its colour layers
 # Usage (on the GPU box): bash tools/ab_bench.sh arm1 [arm2 ...] -> one line per run on stdout, and in the file $AB_OUT if that is set
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=${AB_OUT:-/dev/null}
 : > $OUT
 for rep in 1 2 3; do
   for v in product "$@"; do
-    unset NWE_LIB NWE_WORK_QUEUE NWE_WORK_QUEUE_BACKFILL NWE_WORK_QUEUE_TAIL
+    unset NWE_LIB NWE_WORK_QUEUE NWE_WORK_QUEUE_BACKFILL NWE_WORK_QUEUE_TAIL NWE_COLOUR_SKIP
     TREE=$ROOT
     case "$v" in
       product) ;;
       static) export NWE_WORK_QUEUE=0 ;;
       nobackfill) export NWE_WORK_QUEUE_BACKFILL=0 ;;
       notail) export NWE_WORK_QUEUE_TAIL=0 ;;
+      noskip) export NWE_COLOUR_SKIP=0 ;;
       *=*) if [ -d "${v#*=}" ]; then TREE=${v#*=}; else export NWE_LIB=${v#*=}; fi ;;
       *) export NWE_LIB=$ROOT/nerf-workspaces-explorer_amd/csrc/exp/libnwe_$v.so ;;
     esac
