@@ -514,6 +514,49 @@ int nwe_debug_get_work_queue(const nwe_ctx *ctx);               /* -2 for a null
 int nwe_debug_get_work_queue_backfill(const nwe_ctx *ctx);      /* 1, or 0 under NWE_WORK_QUEUE_BACKFILL=0; -1 for a null context */
 /* The grid of a queued launch of `items` work items: items plus a quarter, rounded up to a multiple of 8.  No device needed. */
 unsigned nwe_debug_queue_grid(unsigned items);
+/* The plan of a render call without the call: what nwe_render (n_rays < 0: the camera's n_poses, H, W and rows
+ * [row_begin, row_end)) or nwe_render_rays (n_rays >= 0; the camera arguments are not read) would decide for this context
+ * on a device of `cus` compute units.  The context may be host-only; its state is read as it is: networks, sampling, early
+ * termination, shared coarse pass, separate passes, decomposition, work-queue mode, backfill and tail.  Of `out` only null /
+ * non-null is read; `hooks` says which one-shot hooks of nwe_render_rays count as armed (the context's own stay as they are).
+ * Returns the refusal the real call would return for these arguments, with its text (nwe_last_error), a host-only context's
+ * own refusal aside; else fills *report, whose struct_bytes the caller has set.  Touches no device, launches nothing, moves
+ * no ring.  A call of no rays plans nothing: the report is zero. */
+#define NWE_PLAN_HOOK_COARSE_WEIGHTS 1u /* nwe_debug_set_coarse_weights */
+#define NWE_PLAN_HOOK_OTHER 2u          /* any of nwe_debug_set_fine_depths / _raw, nwe_set_train_tables */
+/* One stage of the call - the coarse launch of a shared coarse pass or of separate passes, or the main stage every call has -
+ * and, for the MFMA precisions, the plan of its launches. */
+typedef struct nwe_plan_stage {
+    int32_t active;       /* 0: the call has no such stage, and the rest is zero */
+    int32_t role;         /* 0 one fused kernel, 1 producer (coarse pass alone), 2 consumer (fine pass alone) */
+    int64_t n_rays;       /* the stage's rays: the producer's are the representatives */
+    int32_t n_importance;
+    int32_t net;          /* the network (0 coarse, 1 fine) in both descriptor slots, -1: (coarse, fine) */
+    int32_t variant;      /* the kernels: 0 plain, 1 terminating, 2 sharing */
+    int32_t plan;         /* nwe_debug_last_plan: 0 packets, 1 sample split, 2 packets + split rest */
+    int32_t n_launches;   /* 1, or 2 under plan 2 */
+    int32_t fork;         /* 0 the second launch follows the first on the caller's stream; it goes to the side stream, which forks
+                             1 in front of the first launch (backfill), 2 behind it (tail path) */
+    int64_t ray_first[2], rays[2];   /* per launch: its rays, */
+    int32_t split[2];                /* 1 = one packet per work item, 0 = four, */
+    uint32_t items[2], grid[2];      /* its work items, and its grid if it is queued (0: dealt by the hardware) */
+    int32_t tail;         /* 1: the tail path is taken */
+    uint32_t tail_items;  /* ... and the split items it renders in the packets launch */
+} nwe_plan_stage;
+typedef struct nwe_plan_report {
+    uint64_t struct_bytes;
+    int32_t separate, share, full;      /* two launches with each network's own kernels; through the sharing kernels; the full ones */
+    int32_t coarse_launch;              /* the call has a coarse stage */
+    int32_t may_queue, need_side;       /* a launch is queued: the slot's counters are zeroed; the side streams exist */
+    int32_t need_evals, coarse_flags;   /* the slot's evaluation counter is zeroed; the coarse launch has a flag word of its own */
+    int32_t share_k, reserved;
+    int64_t table_elems;                /* floats of the slot's weight table between the two stages */
+    int64_t evals_full, evals_run;      /* nwe_last_ray_evaluations [1] and, without early termination, [0] */
+    int64_t share_rays;                 /* nwe_last_coarse_launch */
+    nwe_plan_stage coarse, main;
+} nwe_plan_report;
+int nwe_debug_plan(nwe_ctx *ctx, int n_poses, int H, int W, int row_begin, int row_end, int64_t n_rays, const nwe_outputs *out,
+                   unsigned hooks, int precision, int cus, nwe_plan_report *report);
 /* The most recent recorded render launch of this context, per launch of its plan: its work items, its grid and the final value
  * of its ticket counter (= grid when every workgroup took one); zeros = not queued.  *side_stream (may be NULL): 1 if the
  * second launch ran on the context's low-priority stream.  Waits for the launch, like the timing calls. */

@@ -28,7 +28,7 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_debug_set_work_queue", "nwe_debug_get_work_queue", "nwe_debug_get_work_queue_backfill", "nwe_debug_queue_grid", "nwe_debug_last_queue",
            "nwe_debug_get_work_queue_tail", "nwe_debug_last_tail", "nwe_debug_last_tail_rest",
            "nwe_query_points", "nwe_last_query_ms", "nwe_debug_set_query_steps",
-           "nwe_packed_colour_finite", "nwe_debug_set_colour_skip", "nwe_debug_get_colour_skip")
+           "nwe_packed_colour_finite", "nwe_debug_set_colour_skip", "nwe_debug_get_colour_skip", "nwe_debug_plan")
 
 
 class Outputs(C.Structure):
@@ -48,6 +48,27 @@ class PointOutputs(C.Structure):
 
     def __init__(self, **kw):
         super().__init__(struct_bytes=C.sizeof(PointOutputs), **kw)
+
+
+PLAN_HOOK_COARSE_WEIGHTS, PLAN_HOOK_OTHER = 1, 2
+
+
+class PlanStage(C.Structure):
+    """nwe_plan_stage of nwe_debug_plan."""
+    _fields_ = [("active", C.c_int32), ("role", C.c_int32), ("n_rays", C.c_int64), ("n_importance", C.c_int32), ("net", C.c_int32),
+                ("variant", C.c_int32), ("plan", C.c_int32), ("n_launches", C.c_int32), ("fork", C.c_int32),
+                ("ray_first", C.c_int64 * 2), ("rays", C.c_int64 * 2), ("split", C.c_int32 * 2), ("items", C.c_uint32 * 2),
+                ("grid", C.c_uint32 * 2), ("tail", C.c_int32), ("tail_items", C.c_uint32)]
+
+
+class PlanReport(C.Structure):
+    """nwe_plan_report of nwe_debug_plan."""
+    _fields_ = [("struct_bytes", C.c_uint64)] + [(name, C.c_int32) for name in (
+        "separate", "share", "full", "coarse_launch", "may_queue", "need_side", "need_evals", "coarse_flags", "share_k", "reserved")] + [
+        (name, C.c_int64) for name in ("table_elems", "evals_full", "evals_run", "share_rays")] + [("coarse", PlanStage), ("main", PlanStage)]
+
+    def __init__(self):
+        super().__init__(struct_bytes=C.sizeof(PlanReport))
 
 
 _lib = None
@@ -120,6 +141,7 @@ def load() -> C.CDLL:
         "nwe_packed_colour_finite": (I, [P, I]),
         "nwe_debug_set_colour_skip": (I, [P, I]),
         "nwe_debug_get_colour_skip": (I, [P]),
+        "nwe_debug_plan": (I, [P, I, I, I, I, I, I64, C.POINTER(Outputs), C.c_uint, I, I, C.POINTER(PlanReport)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -54,12 +54,18 @@ struct NetState : NetShape {
 };
 
 // One slot per launch in flight: the pose table a kernel reads and the events around it.  A slot is reused only
-// after its own launch has finished (its `done` event), so renders of one context queued on different streams never
-// share a pose buffer.
+// after its own launch has finished (its `done` event), so launches of one context queued on different streams never
+// share a pose buffer.  This much every launch has: nwe_create_rays and the query ring take it as it is.
 struct Slot {
     DevBuf<float> poses;
-    Event ev0, ev1, ev_mid;   // ev_mid: between the two launches of the hybrid plan
-    bool used = false, has_mid = false;
+    Event ev0, ev1;
+    bool used = false;
+};
+
+// A slot of the render ring: what its launch reports and the device resources its plan asks for (CallPlan, nwe_plan.h).
+struct RenderSlot : Slot {
+    Event ev_mid;   // between the two launches of the hybrid plan
+    bool has_mid = false;
     int64_t rays_first = 0, rays_total = 0;
     // nwe_last_ray_evaluations: the full count of the launch and, if it terminated rays early, the word its waves added to
     DevBuf<unsigned long long> evals;
@@ -69,13 +75,13 @@ struct Slot {
     // fills and the consumer launch behind it reads (last reader: prepare_slot), the event between the two
     // (nwe_last_coarse_launch), the representatives and the evaluations the two launches ran
     // separate passes (nwe_set_separate_passes): the same table between the coarse and the fine launch, [n_rays][n_samples] when
-    // the two are full kernels, and the word the coarse launch's flags go through (queue_coarse_flags)
+    // the two are full kernels, and the word the coarse launch's flags go through (or_masked_flags_kernel)
     DevBuf<float> share_w;
     DevBuf<uint32_t> coarse_flags;
     Event ev_share;
     bool has_share = false;
     int64_t share_rays = 0, evals_run = 0;
-    // work queue (nwe_debug_set_work_queue): the two ticket counters of the call, one per launch of its plan, zeroed on the
+    // work queue (nwe_debug_set_work_queue): the ticket counters of the call (LaunchResources::counters), zeroed on the
     // caller's stream in front of the launches (last reader: prepare_slot); the low-priority stream the second launch of the
     // hybrid plan backfills the first from, and the events of its fork and join; what nwe_debug_last_queue reports
     DevBuf<unsigned> queue;
@@ -94,11 +100,12 @@ thread_local std::string g_create_error;
 struct nwe_ctx {
     int device = -1;
     bool host_only = false;
+    int cus = 256;            // the device's compute units, asked once by nwe_create: what the launch plans and the query's steps count rounds in
     NetState net[2];
     DevBuf<float> d_t;        // t_vals | one_minus_t | u, at 0, kMaxSamples and 2 kMaxSamples
     int ns = 0, ni = 0;
     static constexpr int kSlots = 4;
-    Slot slots[kSlots];
+    RenderSlot slots[kSlots];
     Slot rays_slot;                      // nwe_create_rays: a pose table and events of its own, outside the timing ring
     // next_slot: the slot the next render takes.  last_slot: the most recent render launch that was RECORDED
     // (nwe_last_kernel_ms); both move only when launch() has succeeded, so a refused launch leaves the timing calls alone.
@@ -195,10 +202,16 @@ __global__ void create_rays_kernel(RenderArgs a, float* __restrict__ out) {
 // ago, normally long finished).  From here on the slot's events describe no launch until a new one has been recorded.
 int prepare_slot(nwe_ctx* c, Slot& s) {
     if (!s.ev0)
-        for (Event* e : {&s.ev0, &s.ev1, &s.ev_mid, &s.ev_share}) HIPCHK(c, hipEventCreate(&e->h));
+        for (Event* e : {&s.ev0, &s.ev1}) HIPCHK(c, hipEventCreate(&e->h));
     if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
-    s.used = s.has_mid = s.has_share = false;
+    s.used = false;
     return NWE_OK;
+}
+int prepare_slot(nwe_ctx* c, RenderSlot& s) {
+    if (!s.ev_mid)
+        for (Event* e : {&s.ev_mid, &s.ev_share}) HIPCHK(c, hipEventCreate(&e->h));
+    s.has_mid = s.has_share = false;
+    return prepare_slot(c, static_cast<Slot&>(s));
 }
 
 // ev0, what `queue` launches, ev1: from then on the slot describes this launch.  `queue` returns NWE_OK or refuses (then
@@ -217,7 +230,7 @@ int record_launch(nwe_ctx* c, Slot& s, hipStream_t stream, Queue&& queue) {
 // into LDS by every workgroup as it starts, the weights are streamed throughout): wait for this context's own launches,
 // on whatever streams they are.  Costs nothing when nothing is in flight.
 int wait_for_launches(nwe_ctx* c) {
-    for (Slot& s : c->slots)
+    for (RenderSlot& s : c->slots)
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     if (c->rays_slot.used) HIPCHK(c, hipEventSynchronize(c->rays_slot.ev1));
     for (Slot& s : c->query_slots)   // a query streams the weights of its network throughout
@@ -268,13 +281,35 @@ RenderArgs camera_args(const Camera& m, const float* poses_dev) {
     return a;
 }
 
+// The refusals early termination and the shared coarse pass share: both render lean pinhole calls only, through kernels of
+// their own.  `on` / `off` open and close the mode's texts, `no_rays` is its word for nwe_render_rays, `kind` names its kernels.
+int check_lean_mode(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole, const std::string& on, const char* off,
+                    const char* no_rays, const std::string& kind, int variant) {
+    // what only a ray's own full passes can give is refused by name rather than changed in silence
+    if (!pinhole) return fail(ctx, NWE_ERR_UNSUPPORTED, on + no_rays + off);
+    nwe_outputs rest = *out;
+    rest.struct_bytes = 0; rest.rgb = rest.depth = rest.acc = nullptr; rest.flags = nullptr;
+    const nwe_outputs none = {};
+    if (std::memcmp(&rest, &none, sizeof(none)) != 0)
+        return fail(ctx, NWE_ERR_UNSUPPORTED, on + "only rgb / depth / acc / flags can be requested" + off);
+    if (precision == NWE_PREC_F32) return NWE_OK;
+    for (int i = 0; i < (ctx->ni > 0 ? 2 : 1); ++i) {
+        const NetState& n = ctx->net[i];
+        if (mfma_variant_built(n.D, n.W, n.skip, n.form, variant)) continue;
+        return fail(ctx, NWE_ERR_UNSUPPORTED,
+                    on + (n.form == kFormReference ? "a network packed unfolded (nwe_debug_set_fold(0)) has no " + kind + " MFMA kernel"
+                                                   : "no " + kind + " MFMA kernel was built for this network shape") + "; use NWE_PREC_F32" + off);
+    }
+    return NWE_OK;
+}
+
 // pinhole: nwe_render / a tile of nwe_render_tiled (false: nwe_render_rays).  The refusals of early termination and of the
-// shared coarse pass come last, and those of separate passes behind them.
-int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole) {
+// shared coarse pass come last, and those of separate passes behind them.  planning: nwe_debug_plan, which a host-only context serves.
+int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole, bool planning = false) {
     if (!ctx || !out) return fail(ctx, NWE_ERR_INVALID, "null context or outputs");
     if (out->struct_bytes != sizeof(nwe_outputs))
         return fail(ctx, NWE_ERR_INVALID, "nwe_outputs.struct_bytes != sizeof(nwe_outputs): the caller was built against another version of include/nwe.h");
-    if (ctx->host_only) return fail(ctx, NWE_ERR_STATE, "host-only context cannot render");
+    if (ctx->host_only && !planning) return fail(ctx, NWE_ERR_STATE, "host-only context cannot render");
     if (ctx->ns <= 0) return fail(ctx, NWE_ERR_STATE, "nwe_set_sampling has not been called");
     if (!ctx->net[0].set) return fail(ctx, NWE_ERR_STATE, "coarse network not set");
     if (ctx->ni > 0 && !ctx->net[1].set) return fail(ctx, NWE_ERR_STATE, "fine network not set but n_importance > 0");
@@ -302,48 +337,17 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhol
             return fail(ctx, NWE_ERR_UNSUPPORTED, "the MFMA kernel supports n_samples <= 128; use NWE_PREC_F32");
     }
     const std::string sharing = "the shared coarse pass is on (nwe_set_shared_coarse, k = " + std::to_string(ctx->share_k) + "): ";
-    const char* share_off = "; set shared_coarse to 1 for this call";
     if (ctx->share_k > 1 && ctx->min_trans > 0.f)
         return fail(ctx, NWE_ERR_UNSUPPORTED, sharing + "it is not built together with early termination (nwe_set_early_termination, min_transmittance = " +
                                                   std::to_string(ctx->min_trans) + "); switch one of them off");
-    if (ctx->share_k > 1) {
-        // a block's pixels share one coarse pass: what only a ray's own coarse pass can give is refused by name
-        if (!pinhole) return fail(ctx, NWE_ERR_UNSUPPORTED, sharing + "nwe_render_rays has no pixel grid to share over" + share_off);
-        nwe_outputs rest = *out;
-        rest.struct_bytes = 0; rest.rgb = rest.depth = rest.acc = nullptr; rest.flags = nullptr;
-        const nwe_outputs none = {};
-        if (std::memcmp(&rest, &none, sizeof(none)) != 0)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, sharing + "only rgb / depth / acc / flags can be requested" + share_off);
-        if (precision != NWE_PREC_F32) {
-            for (int i = 0; i < (ctx->ni > 0 ? 2 : 1); ++i) {
-                const NetState& n = ctx->net[i];
-                if (mfma_share_supported(n.D, n.W, n.skip, n.form)) continue;
-                return fail(ctx, NWE_ERR_UNSUPPORTED,
-                            sharing + (n.form == kFormReference ? "a network packed unfolded (nwe_debug_set_fold(0)) has no sharing MFMA kernel"
-                                                                : "no sharing MFMA kernel was built for this network shape") + "; use NWE_PREC_F32" + share_off);
-            }
-        }
-    }
-    if (ctx->min_trans > 0.f) {
-        // what a terminated call cannot give has no meaning past a stop: refused by name rather than changed in silence
-        const std::string on = "early termination is on (nwe_set_early_termination, min_transmittance = " + std::to_string(ctx->min_trans) + "): ";
-        const char* off = "; set min_transmittance to 0 for this call";
-        if (!pinhole) return fail(ctx, NWE_ERR_UNSUPPORTED, on + "nwe_render_rays, its hooks and its training tables are not terminated" + off);
-        nwe_outputs rest = *out;
-        rest.struct_bytes = 0; rest.rgb = rest.depth = rest.acc = nullptr; rest.flags = nullptr;
-        const nwe_outputs none = {};
-        if (std::memcmp(&rest, &none, sizeof(none)) != 0)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, on + "only rgb / depth / acc / flags can be requested" + off);
-        if (precision != NWE_PREC_F32) {
-            for (int i = 0; i < (ctx->ni > 0 ? 2 : 1); ++i) {
-                const NetState& n = ctx->net[i];
-                if (mfma_term_supported(n.D, n.W, n.skip, n.form)) continue;
-                return fail(ctx, NWE_ERR_UNSUPPORTED,
-                            on + (n.form == kFormReference ? "a network packed unfolded (nwe_debug_set_fold(0)) has no terminating MFMA kernel"
-                                                           : "no terminating MFMA kernel was built for this network shape") + "; use NWE_PREC_F32" + off);
-            }
-        }
-    }
+    if (ctx->share_k > 1)
+        TRY(check_lean_mode(ctx, out, precision, pinhole, sharing, "; set shared_coarse to 1 for this call",
+                            "nwe_render_rays has no pixel grid to share over", "sharing", kVariantShare));
+    if (ctx->min_trans > 0.f)
+        TRY(check_lean_mode(ctx, out, precision, pinhole,
+                            "early termination is on (nwe_set_early_termination, min_transmittance = " + std::to_string(ctx->min_trans) + "): ",
+                            "; set min_transmittance to 0 for this call", "nwe_render_rays, its hooks and its training tables are not terminated",
+                            "terminating", kVariantTerm));
     if (ctx->separate && precision != NWE_PREC_F32) {
         const std::string separate = "separate passes are on (nwe_set_separate_passes): ";
         const char* separate_off = "; set separate_passes to 0 for this call";
@@ -356,14 +360,114 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhol
     return NWE_OK;
 }
 
-// A render launch on the ring slot prepare_slot() made ready (ctx->slots[ctx->next_slot]).  The ring moves on here, once the
-// launch has been recorded.
-int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t stream) {
+#ifdef NWE_STAMPS
+constexpr bool kStampedBuild = true;
+#else
+constexpr bool kStampedBuild = false;
+#endif
+
+// What the context holds for every render call: background, sampling tables and counts, the modes' kernel arguments.
+void context_args(const nwe_ctx* ctx, RenderArgs& a) {
     a.white_bkgd = ctx->white_bkgd;
-    a.t_vals = ctx->d_t.get(); a.omt_vals = a.t_vals + kMaxSamples; a.u_vals = a.omt_vals + kMaxSamples;
+    a.t_vals = ctx->d_t.get();   // null on a host-only context, which plans and never launches
+    if (a.t_vals) { a.omt_vals = a.t_vals + kMaxSamples; a.u_vals = a.omt_vals + kMaxSamples; }
     a.n_samples = ctx->ns; a.n_importance = ctx->ni;
     a.stamps = ctx->stamps;   // only read by -DNWE_STAMPS builds of the kernel (nwe_debug_set_stamps)
+    a.min_trans = ctx->min_trans;
+}
+
+// The call as the planner sees it (nwe_plan.h): `a` as the entry point and context_args() filled it, the context's modes.
+CallDesc describe_call(const nwe_ctx* ctx, const RenderArgs& a, int precision) {
+    CallDesc d;
+    d.n_rays = a.n_rays;
+    RenderArgs consumer = a;
+    consumer.share = kShareConsumer | ctx->share_k << 8;
+    d.n_rep = share_n_rep(consumer, share_grid(consumer));   // at most n_rays
+    d.n_samples = a.n_samples; d.n_importance = a.n_importance;
+    d.mfma = precision != NWE_PREC_F32;
+    d.term = a.min_trans > 0.f;
+    d.share_k = ctx->share_k; d.separate = ctx->separate != 0;
+    RenderArgs unstamped = a;
+    unstamped.stamps = nullptr;
+    d.lean = mfma_is_lean(unstamped); d.stamps = a.stamps != nullptr; d.stamped_build = kStampedBuild;
+    d.w_in = a.w_in != nullptr;
+    d.want_weights_coarse = a.out.weights_coarse != nullptr; d.want_flags = a.out.flags != nullptr;
+    for (int i = 0; i < 2; ++i)
+        for (int v = 0; v < kVariants; ++v) {
+            const NetState& n = ctx->net[i];
+            d.built[i][v] = n.set && n.mfma_ok && mfma_variant_built(n.D, n.W, n.skip, n.form, v);
+        }
+    d.decomposition = ctx->decomposition; d.queue_mode = ctx->work_queue;
+    d.backfill = ctx->backfill; d.tail = ctx->tail;
+    return d;
+}
+
+// What the plan asks of the slot, reserved and - on the caller's stream - zeroed (the last reader of each has finished: prepare_slot).
+int provide(nwe_ctx* ctx, RenderSlot& slot, const CallPlan& p, hipStream_t stream) {
+    if (p.need_evals) {   // the launch's waves add their ray evaluations to the slot's own word
+        HIPCHK(ctx, slot.evals.reserve(1));
+        HIPCHK(ctx, hipMemsetAsync(slot.evals.get(), 0, sizeof(unsigned long long), stream));
+    }
+    HIPCHK(ctx, slot.share_w.reserve((size_t)p.table_elems));
+    if (p.coarse_flags) {
+        HIPCHK(ctx, slot.coarse_flags.reserve(1));
+        HIPCHK(ctx, hipMemsetAsync(slot.coarse_flags.get(), 0, sizeof(uint32_t), stream));
+    }
+    if (p.may_queue) HIPCHK(ctx, slot.queue.reserve(4));   // LaunchResources::counters, zeroed in front of the main stage
+    // every slot's stream with the first call that queues a launch, not one with each of the ring's first four: creating a stream takes
+    // milliseconds, which belong to a context's first frame and to no later one.  The lowest priority there is, so that the
+    // quarter-size work items wait behind the packets until those run out.
+    for (RenderSlot& s : ctx->slots) {
+        if (!p.need_side || s.side) continue;
+        int least = 0, greatest = 0;
+        HIPCHK(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(ctx, hipStreamCreateWithPriority(&s.side.h, hipStreamNonBlocking, least));
+        for (Event* e : {&s.ev_fork, &s.ev_join}) HIPCHK(ctx, hipEventCreateWithFlags(&e->h, hipEventDisableTiming));
+    }
+    return NWE_OK;
+}
+
+// The stages' kernel arguments from the call's: `a` becomes the main stage's; returns the coarse stage's (unused without one).
+RenderArgs stage_args(const CallPlan& p, const RenderSlot& slot, RenderArgs& a) {
+    RenderArgs prod = {};
+    if (p.need_evals) a.evals = slot.evals.get();
+    if (p.main.role != kShareOff) a.share = p.main.role | p.share_k << 8;   // the full kernels do not read it: it costs the launch by its role
+    if (p.share) a.share_w = slot.share_w.get();
+    if (p.coarse.active) {
+        prod = a;
+        prod.share = p.coarse.role | p.share_k << 8; prod.n_rays = p.coarse.n_rays; prod.n_importance = p.coarse.n_importance;
+        prod.out = {};
+        if (p.share) {
+            // k = 1 (separate passes): every ray runs its own coarse pass, whose flag bits are the fused kernel's; a representative's
+            // coarse pass (k > 1) describes no ray of the call
+            if (p.share_k == 1) prod.out.flags = a.out.flags;
+        } else {   // the single-pass render of the full kernels, whose weights_coarse output is the table: the caller's own if it asked for one
+            float* table = a.out.weights_coarse ? a.out.weights_coarse : slot.share_w.get();
+            prod.z_fine_in = prod.raw_in_f = prod.noise_f = prod.u_rand = nullptr;
+            prod.out.struct_bytes = a.out.struct_bytes;
+            prod.out.raw_coarse = a.out.raw_coarse; prod.out.weights_coarse = table;
+            prod.out.rgb_coarse = a.out.rgb_coarse; prod.out.depth_coarse = a.out.depth_coarse;
+            prod.out.acc_coarse = a.out.acc_coarse; prod.out.disp_coarse = a.out.disp_coarse;
+            if (p.coarse_flags) prod.out.flags = slot.coarse_flags.get();
+            a.w_in = table;   // read through the coarse-weights hook, which takes the place of pass 0
+        }
+    }
+    if (p.full) {
+        a.raw_in_c = a.noise_c = nullptr;   // the coarse launch's
+        a.out.raw_coarse = a.out.weights_coarse = a.out.rgb_coarse = a.out.depth_coarse = a.out.acc_coarse = a.out.disp_coarse = nullptr;
+    }
+    return prod;
+}
+
+// A render launch on the ring slot prepare_slot() made ready (ctx->slots[ctx->next_slot]): describe the call, plan it, carry
+// the plan out.  The ring moves on here, once the launch has been recorded.
+int launch(nwe_ctx* ctx, RenderSlot& slot, RenderArgs& a, int precision, hipStream_t stream) {
+    context_args(ctx, a);
     if (a.n_rays <= 0) return NWE_OK;
+    const CallPlan p = plan_call(describe_call(ctx, a, precision), ctx->cus);
+    const bool mfma = precision != NWE_PREC_F32, three_pass = precision == NWE_PREC_F16X3;
+    TRY(provide(ctx, slot, p, stream));
+    const RenderArgs prod = stage_args(p, slot, a);
     const NetState &nc = ctx->net[0], &nf = ctx->net[ctx->ni > 0 ? 1 : 0];
     // the launch's own descriptors: whether its lean kernels may take the hollow path with this network (nwe_debug_set_colour_skip)
     const auto with_skip = [&](const NetState& n) {
@@ -371,124 +475,47 @@ int launch(nwe_ctx* ctx, Slot& slot, RenderArgs& a, int precision, hipStream_t s
         m.colour_skip = ctx->colour_skip == 2 || (ctx->colour_skip == 1 && n.p.colour_finite) ? 1 : 0;
         return m;
     };
-    const NetMfma mf_c = with_skip(nc), mf_f = with_skip(nf);
-    a.min_trans = ctx->min_trans;
-    if (a.min_trans > 0.f) {   // the launch's waves add their ray evaluations to the slot's own word (its last reader: prepare_slot)
-        HIPCHK(ctx, slot.evals.reserve(1));
-        HIPCHK(ctx, hipMemsetAsync(slot.evals.get(), 0, sizeof(unsigned long long), stream));
-        a.evals = slot.evals.get();
-    }
-    // Shared coarse pass: with importance samples the call is two launches, the producer over the representatives of the blocks
-    // its rows touch (check_ready has refused everything but lean pinhole calls), then the consumer over its rays.
-    // Separate passes (MFMA precisions): the same two launches for every call with importance samples, each with the kernel of
-    // its own network's shape and with that network in both descriptor slots, so that a kernel copies bias tables of its own
-    // shape only.  A lean call takes the sharing kernels, at k = 1 every pixel its own representative; every other call the
-    // full kernels: the coarse launch is their single-pass render (n_importance = 0) whose weights_coarse output is the table,
-    // the fine launch reads the table through the coarse-weights hook (w_in), which takes the place of pass 0.
-    const bool separate = ctx->separate && precision != NWE_PREC_F32 && a.n_importance > 0;
-    const auto has_share_kernels = [](const NetState& n) { return mfma_share_supported(n.D, n.W, n.skip, n.form); };
-    const bool share = a.n_importance > 0 && (ctx->share_k > 1 || (separate && mfma_is_lean(a) && has_share_kernels(nc) && has_share_kernels(nf)));
-    const bool full = separate && !share;           // separate passes through the full kernels
-    const bool coarse_launch = share || (full && !a.w_in);   // with the coarse-weights hook armed there is no coarse pass
-    RenderArgs prod = {};
-    if (share) {
-        a.share = kShareConsumer | ctx->share_k << 8;
-        const int64_t n_rep = share_n_rep(a, share_grid(a));   // at most n_rays
-        HIPCHK(ctx, slot.share_w.reserve((size_t)n_rep * a.n_samples));
-        a.share_w = slot.share_w.get();
-        prod = a;
-        prod.share = kShareProducer | ctx->share_k << 8; prod.n_rays = n_rep; prod.out = {};
-        // k = 1 (separate passes): every ray runs its own coarse pass, whose flag bits are the fused kernel's; a representative's
-        // coarse pass (k > 1) describes no ray of the call
-        if (ctx->share_k == 1) prod.out.flags = a.out.flags;
-    }
-    if (full) {
-        a.share = kShareConsumer | 1 << 8;   // the full kernels do not read it: plan_launch costs the launch by its role
-        if (coarse_launch) {
-            float* table = a.out.weights_coarse;   // the caller's own table [n_rays][n_samples] if it asked for one
-            if (!table) {
-                HIPCHK(ctx, slot.share_w.reserve((size_t)a.n_rays * a.n_samples));
-                table = slot.share_w.get();
-            }
-            prod = a;
-            prod.share = kShareProducer | 1 << 8; prod.n_importance = 0;
-            prod.z_fine_in = prod.raw_in_f = prod.noise_f = prod.u_rand = nullptr;
-            prod.out = {};
-            prod.out.struct_bytes = a.out.struct_bytes;
-            prod.out.raw_coarse = a.out.raw_coarse; prod.out.weights_coarse = table;
-            prod.out.rgb_coarse = a.out.rgb_coarse; prod.out.depth_coarse = a.out.depth_coarse;
-            prod.out.acc_coarse = a.out.acc_coarse; prod.out.disp_coarse = a.out.disp_coarse;
-            if (a.out.flags) {
-                HIPCHK(ctx, slot.coarse_flags.reserve(1));
-                HIPCHK(ctx, hipMemsetAsync(slot.coarse_flags.get(), 0, sizeof(uint32_t), stream));
-                prod.out.flags = slot.coarse_flags.get();
-            }
-            a.w_in = table;
-        }
-        a.raw_in_c = a.noise_c = nullptr;   // the coarse launch's
-        a.out.raw_coarse = a.out.weights_coarse = a.out.rgb_coarse = a.out.depth_coarse = a.out.acc_coarse = a.out.disp_coarse = nullptr;
-    }
-    // Work queue: a call that is one fused plain MFMA kernel (early termination, the shared coarse pass and separate passes keep
-    // their launches as they are) may deal its workgroups from the slot's counters, and its hybrid plan's second launch may
-    // backfill the first from the slot's own stream: created on first use with the lowest priority there is, so that the
-    // quarter-size work items wait behind the packets until those run out.
-    const bool may_queue = ctx->work_queue != 0 && precision != NWE_PREC_F32 && !separate && !share && !(a.min_trans > 0.f) &&
-                           mfma_queues(a, ctx->decomposition, ctx->work_queue);   // a call that queues nothing pays nothing
-    if (may_queue) {
-        HIPCHK(ctx, slot.queue.reserve(4));   // the two launches' tickets, the tail path's, the items its second launch rendered
-        // every slot's stream with the first call that queues a launch, not one with each of the ring's first four: creating a stream takes
-        // milliseconds, which belong to a context's first frame and to no later one
-        for (Slot& s : ctx->slots) {
-            if (!ctx->backfill || s.side) continue;
-            int least = 0, greatest = 0;
-            HIPCHK(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIPCHK(ctx, hipStreamCreateWithPriority(&s.side.h, hipStreamNonBlocking, least));
-            for (Event* e : {&s.ev_fork, &s.ev_join}) HIPCHK(ctx, hipEventCreateWithFlags(&e->h, hipEventDisableTiming));
-        }
-    }
-    // the descriptors of the coarse and of the fine launch: (coarse, fine) for one fused kernel, its own network twice otherwise
-    const NetMfma &prod_f = separate ? mf_c : mf_f, &cons_c = separate ? mf_f : mf_c;
+    const NetMfma mf[2] = {with_skip(nc), with_skip(nf)};
+    // one stage: (coarse, fine) in the descriptor slots of one fused kernel, the stage's own network twice under separate passes
+    const auto run = [&](const StagePlan& s, const RenderArgs& args, const LaunchResources& res, LaunchReport* report) {
+        if (!mfma) { launch_render_f32(args, nc.f32, nf.f32, stream); return true; }
+        return launch_render_mfma(args, mf[s.net < 0 ? 0 : s.net], mf[s.net < 0 ? 1 : s.net], three_pass, s.pass, res, stream, report);
+    };
     const int rc = record_launch(ctx, slot, stream, [&]() -> int {
-        slot.has_mid = false; slot.rays_first = slot.rays_total = a.n_rays;
-        slot.q_items[0] = slot.q_items[1] = slot.q_grid[0] = slot.q_grid[1] = 0; slot.side_used = false; slot.tail_items = 0;
-        slot.term = a.min_trans > 0.f;
-        slot.evals_full = a.n_rays * (int64_t)(a.n_samples + (a.n_importance > 0 ? a.n_samples + a.n_importance : 0));
-        slot.evals_run = coarse_launch ? prod.n_rays * a.n_samples + a.n_rays * (int64_t)(a.n_samples + a.n_importance) : slot.evals_full;
-        slot.share_rays = coarse_launch ? prod.n_rays : 0;
+        const PassPlan& pass = p.main.pass;
+        slot.has_mid = false; slot.rays_total = a.n_rays;
+        slot.rays_first = mfma ? pass.launch[0].rays : a.n_rays;
+        for (int i = 0; i < 2; ++i) { slot.q_grid[i] = pass.launch[i].grid; slot.q_items[i] = pass.launch[i].grid ? pass.launch[i].items : 0; }
+        slot.side_used = false; slot.tail_items = pass.tail_items;
+        slot.term = p.need_evals;
+        slot.evals_full = p.evals_full; slot.evals_run = p.evals_run; slot.share_rays = p.share_rays;
         const char* shapes_differ = "coarse and fine networks must have the same shape for the MFMA kernel";
-        if (coarse_launch) {
-            if (precision == NWE_PREC_F32) launch_render_f32(prod, nc.f32, nf.f32, stream);
-            else if (!launch_render_mfma(prod, mf_c, prod_f, precision == NWE_PREC_F16X3, ctx->decomposition, stream, nullptr))
-                return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
-            if (full && prod.out.flags)
+        LaunchReport report;
+        if (p.coarse.active) {
+            if (!run(p.coarse, prod, LaunchResources{}, &report)) return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
+            if (p.full && prod.out.flags)
                 hipLaunchKernelGGL(or_masked_flags_kernel, dim3(1), dim3(1), 0, stream, prod.out.flags,
                                    ~(uint32_t)(NWE_FLAG_RGB | NWE_FLAG_DEPTH | NWE_FLAG_ACC | NWE_FLAG_DISP), a.out.flags);
             HIPCHK(ctx, hipEventRecord(slot.ev_share, stream));
             slot.has_share = true;
         }
-        if (precision == NWE_PREC_F32) {
-            launch_render_f32(a, nc.f32, nf.f32, stream);
-            return NWE_OK;
-        }
-        LaunchInfo info;
-        info.mid = slot.ev_mid;
-        if (may_queue) {
+        LaunchResources res;
+        res.mid = slot.ev_mid;
+        if (p.may_queue) {
             HIPCHK(ctx, hipMemsetAsync(slot.queue.get(), 0, 4 * sizeof(unsigned), stream));
-            info.queue = slot.queue.get(); info.queue_mode = ctx->work_queue;
-            info.side = slot.side; info.fork = slot.ev_fork; info.join = slot.ev_join;
-            info.tail = ctx->tail;
+            res.counters = slot.queue.get();
+            res.side = slot.side; res.fork = slot.ev_fork; res.join = slot.ev_join;
         }
-        if (!launch_render_mfma(a, cons_c, mf_f, precision == NWE_PREC_F16X3, ctx->decomposition, stream, &info)) {
-            if (!info.side_used) return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
+        report = {};
+        if (!run(p.main, a, res, &report)) {
+            if (!report.side_used) return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
             // the side launch is queued and the caller's stream could not be made to wait for it: nothing of this call may
             // still run when the call returns its error
             (void)hipStreamSynchronize(slot.side);
             return fail(ctx, NWE_ERR_HIP, std::string("work queue: joining the side stream: ") + hipGetErrorString(hipGetLastError()));
         }
-        ctx->last_plan = info.plan;
-        for (int i = 0; i < 2; ++i) { slot.q_items[i] = info.items[i]; slot.q_grid[i] = info.grid[i]; }
-        slot.side_used = info.side_used; slot.tail_items = info.tail_items;
-        slot.has_mid = info.mid_recorded; slot.rays_first = info.rays_first;
+        if (mfma) ctx->last_plan = pass.plan;
+        slot.side_used = report.side_used; slot.has_mid = report.mid_recorded;
         return NWE_OK;
     });
     if (rc) return rc;
@@ -502,7 +529,7 @@ int render_rows(nwe_ctx* c, const Camera& m, int precision, const nwe_outputs* o
     TRY(check_ready(c, out, precision, true));
     TRY(check_camera(c, m));
     ON_DEVICE(c);
-    Slot& slot = c->slots[c->next_slot];
+    RenderSlot& slot = c->slots[c->next_slot];
     TRY(prepare_slot(c, slot));
     TRY(upload_poses(c, slot, m.c2w, m.n_poses, stream));
     RenderArgs a = camera_args(m, slot.poses.get());
@@ -668,7 +695,7 @@ int set_on(nwe_ctx* c, Set&& set) { if (!c) return NWE_ERR_INVALID; set(); retur
 constexpr float kMinPartMs = 1e-5f;
 
 // The most recent recorded render launch (nwe_last_kernel_ms, nwe_last_launch_parts), or null
-const Slot* last_render(const nwe_ctx* c) { return c->host_only || c->last_slot < 0 || !c->slots[c->last_slot].used ? nullptr : &c->slots[c->last_slot]; }
+const RenderSlot* last_render(const nwe_ctx* c) { return c->host_only || c->last_slot < 0 || !c->slots[c->last_slot].used ? nullptr : &c->slots[c->last_slot]; }
 
 }  // namespace
 
@@ -690,6 +717,9 @@ int nwe_create(nwe_ctx** out, int device) {
     if (!c->host_only) {
         const hipError_t e = hipSetDevice(device);
         if (e != hipSuccess) { delete c; return fail(nullptr, NWE_ERR_HIP, std::string("nwe_create: ") + hipGetErrorString(e)); }
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->cus = cus;
+        else (void)hipGetLastError();
     }
     *out = c;
     return NWE_OK;
@@ -839,8 +869,8 @@ int nwe_query_points(nwe_ctx* c, int which, const float* points_dev, int64_t n_p
     a.points_per_dir = (int)std::min(points_per_dir, n_points);   // one direction for all of them from there on
     a.density_only = out->raw ? 0 : 1;
     TRY(record_launch(c, slot, stream, [&]() -> int {
-        if (precision == NWE_PREC_F32) launch_query_f32(a, net.f32, c->query_steps, stream);
-        else if (!launch_query_mfma(a, net.mf, precision == NWE_PREC_F16X3, c->query_steps, stream))
+        if (precision == NWE_PREC_F32) launch_query_f32(a, net.f32, c->query_steps, c->cus, stream);
+        else if (!launch_query_mfma(a, net.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
             return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
         return NWE_OK;
     }));
@@ -869,7 +899,7 @@ int nwe_render_rays(nwe_ctx* c, const float* rays_dev, int64_t n_rays, int preci
     if (n_rays < 0 || n_rays > INT32_MAX || (!rays_dev && n_rays > 0)) return fail(c, NWE_ERR_INVALID, "bad rays (null, or more than 2^31 - 1)");
     if (n_rays == 0) return NWE_OK;
     ON_DEVICE(c);
-    Slot& slot = c->slots[c->next_slot];
+    RenderSlot& slot = c->slots[c->next_slot];
     TRY(prepare_slot(c, slot));
     RenderArgs a = {};
     a.rays = rays_dev; a.n_rays = n_rays; a.W = 1; a.rows = 1;
@@ -890,7 +920,7 @@ int nwe_to8b(nwe_ctx* c, const float* rgb_dev, uint8_t* out_dev, int64_t n, void
 }
 
 float nwe_last_kernel_ms(nwe_ctx* c) {
-    const Slot* s = c ? last_render(c) : nullptr;
+    const RenderSlot* s = c ? last_render(c) : nullptr;
     if (!s) return -1.f;
     DeviceGuard guard;
     hipError_t e = hipSetDevice(c->device);
@@ -904,7 +934,7 @@ float nwe_last_kernel_ms(nwe_ctx* c) {
 int nwe_last_launch_parts(nwe_ctx* c, float* ms2, int64_t* rays2) {
     if (!c || !ms2 || !rays2) return NWE_ERR_INVALID;
     ms2[0] = ms2[1] = -1.f; rays2[0] = rays2[1] = 0;
-    const Slot* s = last_render(c);
+    const RenderSlot* s = last_render(c);
     if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
     ON_DEVICE(c);
     HIPCHK(c, hipEventSynchronize(s->ev1));
@@ -926,7 +956,7 @@ int nwe_last_launch_parts(nwe_ctx* c, float* ms2, int64_t* rays2) {
 int nwe_last_coarse_launch(nwe_ctx* c, float* ms, int64_t* rays) {
     if (!c || !ms || !rays) return NWE_ERR_INVALID;
     *ms = -1.f; *rays = 0;
-    const Slot* s = last_render(c);
+    const RenderSlot* s = last_render(c);
     if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
     if (!s->has_share) return NWE_OK;
     ON_DEVICE(c);
@@ -939,7 +969,7 @@ int nwe_last_coarse_launch(nwe_ctx* c, float* ms, int64_t* rays) {
 int nwe_last_ray_evaluations(nwe_ctx* c, int64_t* out2) {
     if (!c || !out2) return NWE_ERR_INVALID;
     out2[0] = out2[1] = 0;
-    const Slot* s = last_render(c);
+    const RenderSlot* s = last_render(c);
     if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
     ON_DEVICE(c);
     HIPCHK(c, hipEventSynchronize(s->ev1));
@@ -972,11 +1002,62 @@ int nwe_debug_set_colour_skip(nwe_ctx* c, int mode) { return set_on(mode < 0 || 
 int nwe_debug_get_colour_skip(const nwe_ctx* c) { return c ? c->colour_skip : -1; }
 int nwe_debug_get_work_queue_backfill(const nwe_ctx* c) { return c ? (c->backfill ? 1 : 0) : -1; }
 unsigned nwe_debug_queue_grid(unsigned items) { return queue_grid(items); }
+// The plan of a call without the call: check_ready's refusals, the entry point's own, then plan_call at the given CU count.
+int nwe_debug_plan(nwe_ctx* c, int n_poses, int H, int W, int row_begin, int row_end, int64_t n_rays, const nwe_outputs* out,
+                   unsigned hooks, int precision, int cus, nwe_plan_report* report) {
+    const bool pinhole = n_rays < 0;
+    TRY(check_ready(c, out, precision, pinhole, true));
+    if (!report || report->struct_bytes != sizeof(nwe_plan_report))
+        return fail(c, NWE_ERR_INVALID, "nwe_plan_report.struct_bytes != sizeof(nwe_plan_report): the caller was built against another version of include/nwe.h");
+    if (cus < 1) return fail(c, NWE_ERR_INVALID, "cus must be at least 1");
+    *report = {};
+    report->struct_bytes = sizeof(nwe_plan_report);
+    static const float somewhere = 0.f;   // an armed hook, a pose table: only null / non-null is read
+    RenderArgs a = {};
+    if (pinhole) {
+        const Camera m{&somewhere, n_poses, H, W, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f, row_begin, row_end};
+        TRY(check_camera(c, m));
+        a = camera_args(m, &somewhere);
+        if (a.n_rays > INT32_MAX) return fail(c, NWE_ERR_INVALID, "more than 2^31 - 1 rays in one call");
+    } else {
+        if (n_rays > INT32_MAX) return fail(c, NWE_ERR_INVALID, "bad rays (null, or more than 2^31 - 1)");
+        a.rays = &somewhere; a.n_rays = n_rays; a.W = 1; a.rows = 1;
+        if (hooks & NWE_PLAN_HOOK_COARSE_WEIGHTS) a.w_in = &somewhere;
+        if (hooks & NWE_PLAN_HOOK_OTHER) a.z_fine_in = &somewhere;
+    }
+    a.out = *out;
+    context_args(c, a);
+    if (a.n_rays <= 0) return NWE_OK;   // the call launches nothing
+    const CallPlan p = plan_call(describe_call(c, a, precision), cus);
+    report->separate = p.separate; report->share = p.share; report->full = p.full; report->coarse_launch = p.coarse_launch;
+    report->may_queue = p.may_queue; report->need_side = p.need_side; report->need_evals = p.need_evals;
+    report->coarse_flags = p.coarse_flags; report->share_k = p.share_k;
+    report->table_elems = p.table_elems; report->evals_full = p.evals_full; report->evals_run = p.evals_run; report->share_rays = p.share_rays;
+    const StagePlan* stages[2] = {&p.coarse, &p.main};
+    for (int i = 0; i < 2; ++i) {
+        const StagePlan& s = *stages[i];
+        nwe_plan_stage& r = i == 0 ? report->coarse : report->main;
+        if (!s.active) continue;
+        r.active = 1; r.role = s.role; r.n_rays = s.n_rays; r.n_importance = s.n_importance; r.net = s.net;
+        if (precision == NWE_PREC_F32) continue;   // the fp32 launcher has no plan
+        // what launch_render_mfma refuses: no kernel for the stage, or one fused kernel over two networks of different shapes
+        const NetState &nc = c->net[0], &nf = c->net[1];
+        if (!s.pass.ok || (s.net < 0 && s.n_importance > 0 && (nf.D != nc.D || nf.W != nc.W || nf.skip != nc.skip || nf.form != nc.form)))
+            return fail(c, NWE_ERR_UNSUPPORTED, "coarse and fine networks must have the same shape for the MFMA kernel");
+        r.variant = s.pass.variant; r.plan = s.pass.plan; r.n_launches = s.pass.n_launches;
+        for (int l = 0; l < 2; ++l) {
+            const LaunchPlan& q = s.pass.launch[l];
+            r.ray_first[l] = q.ray_first; r.rays[l] = q.rays; r.split[l] = q.split; r.items[l] = q.items; r.grid[l] = q.grid;
+        }
+        r.fork = s.pass.fork; r.tail = s.pass.tail; r.tail_items = s.pass.tail_items;
+    }
+    return NWE_OK;
+}
 int nwe_debug_last_queue(nwe_ctx* c, unsigned* items2, unsigned* grid2, unsigned* taken2, int* side_stream) {
     if (!c || !items2 || !grid2 || !taken2) return NWE_ERR_INVALID;
     for (int i = 0; i < 2; ++i) items2[i] = grid2[i] = taken2[i] = 0;
     if (side_stream) *side_stream = 0;
-    const Slot* s = last_render(c);
+    const RenderSlot* s = last_render(c);
     if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
     ON_DEVICE(c);
     HIPCHK(c, hipEventSynchronize(s->ev1));
@@ -991,7 +1072,7 @@ int nwe_debug_get_work_queue_tail(const nwe_ctx* c) { return c ? (c->tail ? 1 : 
 static int last_tail(nwe_ctx* c, unsigned* out, int which) {
     if (!c || !out) return NWE_ERR_INVALID;
     *out = 0;
-    const Slot* s = last_render(c);
+    const RenderSlot* s = last_render(c);
     if (!s) return fail(c, NWE_ERR_STATE, "nothing has been launched");
     if (!s->tail_items) return NWE_OK;
     ON_DEVICE(c);

@@ -12,11 +12,9 @@
 #include <stdint.h>
 
 #include "../../include/nwe.h"
+#include "nwe_plan.h"   // kMaxSamples, kMaxImportance, the share roles: shared with the HIP-free planner
 
 namespace nwe {
-
-constexpr int kMaxSamples = 128;     // n_samples upper bound (LDS tables)
-constexpr int kMaxImportance = 256;  // n_importance upper bound
 
 // Kernel arguments common to both kernels (passed by value).
 struct RenderArgs {
@@ -76,7 +74,6 @@ static_assert(sizeof(RenderArgs) == 360, "RenderArgs must not grow: every kernel
 // Diagnostic builds (-DNWE_STAMPS): uint64 words of a wave's stamp row (include/nwe.h, nwe_debug_set_stamps).
 constexpr int kStampWords = 14;
 
-constexpr int kShareOff = 0, kShareProducer = 1, kShareConsumer = 2;
 __host__ __device__ inline int share_role(const RenderArgs& a) { return a.share & 0xff; }
 
 // The blocks a call's rows touch, from the camera fields both launches of a shared call carry: k, the first block row, the

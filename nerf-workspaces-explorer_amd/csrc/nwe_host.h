@@ -5,6 +5,7 @@
 
 #include "nwe_device.h"
 #include "nwe_pack.h"   // LayerF32, NetF32, NetMfma, Form, kTileBytes, kMaxDepth: shared with the HIP-free packers
+#include "nwe_plan.h"   // PassPlan and the constants of planning: shared with the HIP-free planner
 
 namespace nwe {
 
@@ -14,48 +15,30 @@ void launch_render_f32(const RenderArgs& a, const NetF32& nc, const NetF32& nf, 
 
 // true if a kernel instantiation exists for this shape (in_dir == 0 exactly for kFormNoViewDirs)
 bool mfma_supported(int D, int W, int in_xyz, int in_dir, int skip, int form);
-// returns false if the shape has no instantiation.  decomposition: -1 = pick by frame size, 0 = four ray packets per
-// workgroup, 1 = one packet per workgroup with its samples dealt to the four waves, 2 = full rounds as 0 and the ragged
-// last round as 1 in a second launch (bit-identical results)
-// *info (may be null): in, `mid` = an event to record between the two launches of plan 2 (or null); out, the plan taken
-// (0 / 1 / 2 as above) and the rays the first launch got (all of them unless plan 2)
-// Work queue (nwe_debug_set_work_queue; plain kernels only, a terminating or sharing launch stays static): in, `queue` = two
-// zeroed device counters, one per launch of the plan, or null, and queue_mode: -1 = queue a launch with more workgroups than the
-// device has CUs, 1 = every launch; out, per launch its work items and its grid (0, 0 = not queued).  With a queue the second
-// launch of plan 2 goes to `side` (in: a low-priority stream, with `fork` and `join` events of the caller's; all three or
-// none), which starts behind `fork` on the caller's stream in front of the first launch and which the caller's stream joins
-// behind the second; out, side_used.  false with a side launch queued: the join could not be queued, *info says side_used.
-// Tail path (render_mfma_tail_kernel): `queue` then has a third zeroed counter; in, `tail` = the caller allows it; out, tail_items =
-// the plan's split items if the path was taken - lean call, queued first launch whose surplus workgroups cover them all, tail
-// kernel built, side stream given - and 0 otherwise.  The side stream then forks behind the first launch, not in front of it.
-struct LaunchInfo {
-    hipEvent_t mid = nullptr;
-    int plan = -1;
-    int64_t rays_first = 0;
-    bool mid_recorded = false;
-    unsigned* queue = nullptr;
-    int queue_mode = -1;
-    hipStream_t side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    unsigned items[2] = {0, 0}, grid[2] = {0, 0};
-    bool side_used = false;
-    bool tail = false;
-    unsigned tail_items = 0;
+// Carries out the plan of one launch group (plan_pass, nwe_plan.h): looks up the shape's launcher of the plan's variant and issues
+// the launches, events and stream waits the plan names.  false: the plan is not ok, or the descriptors do not fit the shape's
+// kernels (nothing was launched) - or, with out->side_used, the join of the side launch could not be queued.
+struct LaunchResources {
+    hipEvent_t mid = nullptr;        // recorded between the two launches of plan 2 (or null)
+    unsigned* counters = nullptr;    // a plan with a queued launch: four zeroed words - one ticket counter per launch, the tail
+                                     // path's, and the items its second launch rendered
+    hipStream_t side = nullptr;      // a plan that forks: the low-priority stream of the second launch, and the events of its
+    hipEvent_t fork = nullptr, join = nullptr;   // fork from and join into the caller's stream
 };
-// true if a plain launch of `a` under this decomposition and queue mode deals at least one launch of its plan from a queue: the
-// same plan and the same size test as launch_render_mfma's, for the caller that has to provide the counters and the stream
-bool mfma_queues(const RenderArgs& a, int decomposition, int queue_mode);
-bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& nf, bool three_pass, int decomposition, hipStream_t stream,
-                        LaunchInfo* info);
+// What execution reports back.  The side stream is used only if the fork could be recorded and waited on; otherwise the
+// second launch follows the first on the caller's stream.
+struct LaunchReport {
+    bool mid_recorded = false, side_used = false;
+};
+bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& nf, bool three_pass, const PassPlan& plan,
+                        const LaunchResources& res, hipStream_t stream, LaunchReport* out);
 
-// true if the shape's terminating kernels (early ray termination) were built: every supported shape but kFormReference
-bool mfma_term_supported(int D, int W, int skip, int form);
-
-// true if the shape's sharing kernels (shared coarse pass) were built: the same shapes
-bool mfma_share_supported(int D, int W, int skip, int form);
+// true if the shape's kernels of this variant (nwe_plan.h: Variant) are in this library; the terminating and the sharing kernels
+// exist for every supported shape but kFormReference
+bool mfma_variant_built(int D, int W, int skip, int form, int variant);
 
 // true if the MFMA launch of `a` takes the lean instantiations: no output beyond rgb / depth / acc / flags, no hook, no table, no
-// precomputed rays (is_lean, nwe_mfma_render.h)
+// precomputed rays, no stamps (is_lean, nwe_mfma_render.h)
 bool mfma_is_lean(const RenderArgs& a);
 
 int mfma_max_samples();      // n_samples the MFMA kernel's per-wave LDS buffers are sized for
@@ -85,10 +68,10 @@ constexpr int kQueryMaxSteps = 256;    // steps per workgroup at the most: one p
 // most - and as many steps per workgroup as that leaves, up to kQueryMaxSteps: steps = clamp(packets / (8 CUs), 1, 256).
 // The prologue a workgroup amortises over its steps is small (one bias table, ~10 KB from L2, and a barrier: a few per cent
 // of ONE step), so a query of up to 8 CUs packets runs one step per workgroup and spreads as widely as it can.
-int query_steps(int64_t packets, int forced);
-void launch_query_f32(const QueryArgs& a, const NetF32& net, int forced_steps, hipStream_t stream);
+int query_steps(int64_t packets, int forced, int cus);
+void launch_query_f32(const QueryArgs& a, const NetF32& net, int forced_steps, int cus, hipStream_t stream);
 // false: no query kernel for the network's shape (the shapes of mfma_supported), or its stream does not fit the instantiation
-bool launch_query_mfma(const QueryArgs& a, const NetMfma& net, bool three_pass, int forced_steps, hipStream_t stream);
+bool launch_query_mfma(const QueryArgs& a, const NetMfma& net, bool three_pass, int forced_steps, int cus, hipStream_t stream);
 
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);

@@ -351,11 +351,11 @@ __global__ void __launch_bounds__(256) query_f32_kernel(QueryArgs a, NetF32 net)
     if (flags && a.flags) atomicOr(a.flags, flags);
 }
 
-void launch_query_f32(const QueryArgs& a_in, const NetF32& net, int forced_steps, hipStream_t stream) {
+void launch_query_f32(const QueryArgs& a_in, const NetF32& net, int forced_steps, int cus, hipStream_t stream) {
     if (a_in.n_points <= 0) return;
     QueryArgs a = a_in;
     const int64_t packets = ((int64_t)a.n_points + kRP - 1) / kRP;
-    a.steps = query_steps(packets, forced_steps);
+    a.steps = query_steps(packets, forced_steps, cus);
     const dim3 grid((unsigned)((packets + a.steps - 1) / a.steps));
     if (net.in_dir != 0) hipLaunchKernelGGL(query_f32_kernel<true>, grid, dim3(256), 0, stream, a, net);
     else hipLaunchKernelGGL(query_f32_kernel<false>, grid, dim3(256), 0, stream, a, net);

@@ -11,9 +11,6 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 #define LDS_AS __attribute__((address_space(3)))
 
-constexpr int kWaves = 4;
-constexpr int kRaysPerWave = 32;
-
 constexpr int PD = 3;   // A fragments are read PD k-steps ahead of their MFMAs
 // A LONG chunk (>= 16 k-steps, three-pass mode) has at least this many pieces per wave; it keeps the (hi, lo) tiles of its last
 // k-step in a rotating tail slot instead of the chunk buffer, see Walker.

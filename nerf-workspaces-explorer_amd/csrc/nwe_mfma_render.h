@@ -4,12 +4,6 @@
 
 namespace nwe {
 
-// Coarse samples the LDS weight / cdf buffer holds: four packets per workgroup keep one buffer per wave (64 samples); the
-// sample-split decomposition has ONE packet per workgroup and one shared buffer, which holds the ABI's full 128 samples
-// in half the space - so more than 64 coarse samples always take that decomposition (plan_launch, nwe_kernel_mfma.hip).
-constexpr int kPacketMaxSamples = 64;
-constexpr int kSplitMaxSamples = kMaxSamples;
-
 template <int W, int D, bool SPLIT>
 struct Smem {
     using S = Shape<W, D>;
@@ -244,29 +238,11 @@ __global__ void __launch_bounds__(256) render_mfma_tail_kernel(RenderArgs a_in, 
 #undef NWE_PRIME_STREAM
 #undef NWE_EVAL_POINT
 
-// The kernel variants a shape is built in, beside its query kernels (nwe_mfma_query.h).  One instantiation unit holds one variant
-// of one group of shapes (nwe_mfma_inst.hip); the dispatcher's table has one launcher per shape and variant.
-//   plain: eight kernels (three-pass / single-pass, packets / sample split, lean / full)
-//   term:  four, early termination (TERM; lean)        share: four, shared coarse pass (SHARE; lean)
-//   tail:  two, render_mfma_tail_kernel (three-pass / single-pass, each holding both decompositions; lean)
-enum Variant { kVariantPlain, kVariantTerm, kVariantShare, kVariantTail, kVariants };
-
-// Whether a shape has a variant's kernels: the terminating and the sharing kernels exist for the product formulations,
-// kFormReference is a comparison path; every form has the plain kernels and, with them, the queue and the tail kernel.
-constexpr bool variant_built(int variant, int form) {
-    return variant == kVariantTerm || variant == kVariantShare ? form != kFormReference : true;
-}
 #ifdef NWE_STAMPS   // a stamped launch is not lean (its stamp buffer), and stamps the tail path all the same
 constexpr bool kTailLean = false;
 #else
 constexpr bool kTailLean = true;
 #endif
-
-// workgroups (= work items) of a launch of `rays` rays (split: one packet per workgroup)
-inline unsigned mfma_workgroups(int64_t rays, bool split) {
-    const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
-    return (unsigned)((rays + per_wg - 1) / per_wg);
-}
 
 using RenderKernel = void (*)(RenderArgs, NetMfma, NetMfma);
 using RenderLauncher = void (*)(RenderArgs, const NetMfma&, const NetMfma&, bool, bool, int64_t, int64_t, hipStream_t);

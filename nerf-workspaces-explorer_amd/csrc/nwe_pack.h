@@ -42,11 +42,6 @@ enum Form {
     kFormNoViewDirs = 2     // use_view_dirs=False (nerf_model.py:41-43,78-79): trunk, then the rows rgb_raw(3), sigma_raw of _output_linear
 };
 
-// The grid of a queued MFMA launch of n work items (nwe_debug_set_work_queue): n plus a quarter, rounded up to a multiple of 8.
-// The hardware deals a grid's workgroups to the 8 XCDs in turn, an eighth each; with a quarter more workgroups than items an
-// XCD up to 25 % faster than the mean still finds workgroups in its eighth to take tickets with.
-inline unsigned queue_grid(unsigned n) { return (unsigned)(((uint64_t)n + (n + 3) / 4 + 7) / 8 * 8); }
-
 struct NetShape {
     int D = 0, W = 0, in_xyz = 0, in_dir = 0, skip = -1, out_ch = 0;   // out_ch: use_view_dirs=False (in_dir == 0), rows of _output_linear
 };

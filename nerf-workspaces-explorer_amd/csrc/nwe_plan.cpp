@@ -1,0 +1,145 @@
+// Launch planning (nwe_plan.h): plain C++ without HIP.
+#include "nwe_plan.h"
+
+namespace nwe {
+
+// The plan of a launch group: 0 = all packets, 1 = all sample-split, 2 = hybrid; *full_out = the rays of the hybrid plan's first launch.
+static int plan_launch(const PassDesc& a, int cus, int64_t* full_out) {
+    // One workgroup per CU at a time, so a launch costs (rounds of workgroups) x (sample iterations per workgroup).  Three
+    // plans, same arithmetic: all packets; all sample-split (finer units, ~6 % overhead: redundant sequential part and
+    // exchange); or the full rounds as packets and the ragged last round sample-split in a second launch behind it.
+    const int64_t rays_wg = kWaves * kRaysPerWave;
+    // the sample iterations this launch runs: both passes, or - shared coarse pass - the producer's coarse pass alone, the
+    // consumer's fine pass alone
+    const int s_coarse = a.role == kShareConsumer ? 0 : a.n_samples;
+    const int s_fine = a.role == kShareProducer || a.n_importance <= 0 ? 0 : a.n_samples + a.n_importance;
+    const double its = (double)(s_coarse + s_fine);
+    const double its_split = 1.06 * (double)((s_coarse + 3) / 4 + (s_fine + 3) / 4);
+    const auto rounds = [&](int64_t rays, int64_t per_wg) { return (double)(((rays + per_wg - 1) / per_wg + cus - 1) / cus); };
+    const int64_t full = (a.n_rays / rays_wg / cus) * cus * rays_wg;            // rays in complete rounds of packet workgroups
+    const double t_packet = rounds(a.n_rays, rays_wg) * its;
+    const double t_split = rounds(a.n_rays, kRaysPerWave) * its_split;
+    const double t_hybrid = full > 0 && full < a.n_rays ? (double)(full / rays_wg / cus) * its + rounds(a.n_rays - full, kRaysPerWave) * its_split : 1e300;
+    // two launches when the model promises at least 0.8 %: the 800x800 frame (19 full rounds + 136 workgroups) is 1.0 % by the
+    // model and measures -0.4 % (368.4 vs 370.0 ms, alternating, tools/plan_ab.py); a second launch costs a few microseconds
+    const double t_single = t_packet <= t_split ? t_packet : t_split;
+    int plan = t_hybrid < 0.992 * t_single ? 2 : (t_packet <= t_split ? 0 : 1);
+    if (a.decomposition >= 0) plan = a.decomposition;   // nwe_debug_set_decomposition: tests force one
+    if (a.n_samples > kPacketMaxSamples) plan = 1;      // only the single-packet workgroup has LDS for that many coarse weights
+    *full_out = full;
+    return plan;
+}
+
+PassPlan plan_pass(const PassDesc& d, int cus) {
+    PassPlan p;
+    if (d.variant < 0) return p;
+    p.ok = true;
+    p.variant = d.variant;
+    int64_t full = 0;
+    p.plan = plan_launch(d, cus, &full);
+    // Dealing: the hardware hands workgroup b of a launch to XCD (b + c) mod 8, an eighth of the launch each
+    // whatever pace an XCD runs at.  A queued launch deals tickets instead (render_mfma_kernel), from a counter of its own.
+    const auto deal = [&](LaunchPlan& l, int64_t ray_first, int64_t rays, bool split) {
+        l.ray_first = ray_first; l.rays = rays; l.split = split;
+        l.items = mfma_workgroups(rays, split);
+        if (d.may_queue && rays > 0 && (d.queue_mode == 1 || l.items > (unsigned)cus)) l.grid = queue_grid(l.items);
+    };
+    if (p.plan != 2) {
+        p.n_launches = 1;
+        deal(p.launch[0], 0, d.n_rays, p.plan == 1);
+        return p;
+    }
+    p.n_launches = 2;
+    deal(p.launch[0], 0, full, false);
+    deal(p.launch[1], full, d.n_rays - full, true);
+    if (!d.side || !p.queued()) return p;   // both launches on the caller's stream, the second behind the first
+    // The tail path: the surplus workgroups of the queued packets launch render the split items, one ticket each from the
+    // call's third counter, and the second launch - the same kernel, behind the first on the device - renders what they
+    // left, which is nothing when the surplus covers every item; only then is the path taken.  Otherwise nothing changes:
+    // the second launch backfills the first from the side stream, whose low priority keeps its items behind the packets.
+    const bool lean = d.lean && (d.stamped_build || !d.stamps);
+    p.tail = p.launch[0].grid && d.tail && lean && d.tail_built && d.n_rays > full &&
+             p.launch[0].grid - p.launch[0].items >= p.launch[1].items;
+    p.tail_items = p.tail ? p.launch[1].items : 0;
+    p.fork = p.tail ? kForkBehind : kForkFront;
+    return p;
+}
+
+// The kernels that serve a stage, or -1: the terminating and the sharing kernels are lean only, and exclude each other; a
+// stage that carries a role without being lean (separate passes through the full kernels) is a single-pass render for the
+// producer and reads the coarse weights through the hook for the consumer.
+static int stage_variant(const CallDesc& c, int role, bool lean, int n_importance, bool w_in, int net) {
+    const bool share = role != kShareOff && lean;
+    int v = kVariantPlain;
+    if (c.term) v = lean && !share ? kVariantTerm : -1;
+    else if (share) v = n_importance > 0 ? kVariantShare : -1;
+    else if (role != kShareOff && (role == kShareProducer ? n_importance != 0 : !w_in)) v = -1;
+    return v >= 0 && c.built[net][v] ? v : -1;
+}
+
+CallPlan plan_call(const CallDesc& c, int cus) {
+    CallPlan p;
+    const bool lean = c.lean && !c.stamps;   // what picks the kernels: a stamped launch is not lean
+    // Shared coarse pass: with importance samples the call is two launches, the producer over the representatives of the blocks
+    // its rows touch (everything but lean pinhole calls has been refused), then the consumer over its rays.
+    // Separate passes (MFMA precisions): the same two launches for every call with importance samples, each with the kernel of
+    // its own network's shape and with that network in both descriptor slots, so that a kernel copies bias tables of its own
+    // shape only.  A lean call takes the sharing kernels, at k = 1 every pixel its own representative; every other call the
+    // full kernels: the coarse launch is their single-pass render (n_importance = 0) whose weights_coarse output is the table,
+    // the fine launch reads the table through the coarse-weights hook, which takes the place of pass 0.
+    p.separate = c.separate && c.mfma && c.n_importance > 0;
+    p.share = c.n_importance > 0 && (c.share_k > 1 || (p.separate && lean && c.built[0][kVariantShare] && c.built[1][kVariantShare]));
+    p.full = p.separate && !p.share;
+    p.coarse_launch = p.share || (p.full && !c.w_in);   // with the coarse-weights hook armed there is no coarse pass
+    p.share_k = p.share ? c.share_k : 1;
+    p.need_evals = c.term;
+    // the table between the two launches: [n_samples][n_rep] of the sharing kernels, [n_rays][n_samples] of the full ones, which
+    // may be the caller's own
+    if (p.share) p.table_elems = c.n_rep * c.n_samples;
+    else if (p.full && p.coarse_launch && !c.want_weights_coarse) p.table_elems = c.n_rays * c.n_samples;
+    p.coarse_flags = p.full && p.coarse_launch && c.want_flags;
+
+    StagePlan& m = p.main;
+    m.active = true;
+    m.role = p.share || p.full ? kShareConsumer : kShareOff;
+    m.n_rays = c.n_rays; m.n_importance = c.n_importance;
+    m.net = p.separate ? 1 : -1;
+    StagePlan& k = p.coarse;
+    if (p.coarse_launch) {
+        k.active = true;
+        k.role = kShareProducer;
+        k.n_rays = p.share ? c.n_rep : c.n_rays;
+        k.n_importance = p.share ? c.n_importance : 0;
+        k.net = p.separate ? 0 : -1;
+    }
+    p.evals_full = c.n_rays * (int64_t)(c.n_samples + (c.n_importance > 0 ? c.n_samples + c.n_importance : 0));
+    p.evals_run = p.coarse_launch ? k.n_rays * c.n_samples + c.n_rays * (int64_t)(c.n_samples + c.n_importance) : p.evals_full;
+    p.share_rays = p.coarse_launch ? k.n_rays : 0;
+    if (!c.mfma) return p;
+
+    // Work queue: a call that is one fused plain MFMA kernel - plain kernels only: early termination, the shared coarse pass and
+    // separate passes keep their launches as they are - may deal its workgroups from the slot's counters, and its hybrid plan's
+    // second launch may backfill the first from the slot's own stream.
+    const bool plain_only = !p.separate && !p.share && !c.term;
+    const auto describe = [&](const StagePlan& s, bool stage_lean, bool w_in) {
+        PassDesc d;
+        d.n_rays = s.n_rays; d.n_samples = c.n_samples; d.n_importance = s.n_importance;
+        d.role = s.role;
+        d.lean = stage_lean && c.lean; d.stamps = c.stamps; d.stamped_build = c.stamped_build;
+        d.variant = stage_variant(c, s.role, stage_lean && lean, s.n_importance, w_in, s.net > 0 ? 1 : 0);
+        d.tail_built = c.built[s.net > 0 ? 1 : 0][kVariantTail];
+        d.decomposition = c.decomposition; d.queue_mode = c.queue_mode;
+        return d;
+    };
+    // the launches through the full kernels are not lean: the coarse one writes the table, the fine one reads it
+    if (k.active) k.pass = plan_pass(describe(k, !p.full, false), cus);
+    PassDesc d = describe(m, !p.full, p.full || c.w_in);
+    d.may_queue = plain_only && c.queue_mode != 0;
+    d.side = c.backfill; d.tail = c.tail;
+    m.pass = plan_pass(d, cus);
+    p.may_queue = m.pass.queued();   // a call that queues nothing pays nothing
+    p.need_side = p.may_queue && c.backfill;
+    return p;
+}
+
+}  // namespace nwe

@@ -1,0 +1,144 @@
+// The plan of a render call: which launches it is, what each of them gets and what the slot must hold for them.  Plain C++
+// without HIP (nwe_plan.cpp), pure arithmetic on a handful of integers: nwe_abi.hip describes the call, plan_call() decides,
+// and the launchers carry the plan out (nwe_kernel_mfma.hip).  Nothing here asks a device: the CU count is an argument.
+// The plain constants the decisions rest on live here too, and the device headers take them from here.
+#pragma once
+#include <stdint.h>
+
+#include "nwe_pack.h"   // Form
+
+namespace nwe {
+
+constexpr int kMaxSamples = 128;     // n_samples upper bound (LDS tables)
+constexpr int kMaxImportance = 256;  // n_importance upper bound
+
+constexpr int kWaves = 4;
+constexpr int kRaysPerWave = 32;
+
+// Coarse samples the LDS weight / cdf buffer holds: four packets per workgroup keep one buffer per wave (64 samples); the
+// sample-split decomposition has ONE packet per workgroup and one shared buffer, which holds the ABI's full 128 samples
+// in half the space - so more than 64 coarse samples always take that decomposition (plan_pass).
+constexpr int kPacketMaxSamples = 64;
+constexpr int kSplitMaxSamples = kMaxSamples;
+
+// The role of a launch in a call of two (RenderArgs::share & 0xff): the shared coarse pass and separate passes
+constexpr int kShareOff = 0, kShareProducer = 1, kShareConsumer = 2;
+
+// The kernel variants a shape is built in, beside its query kernels (nwe_mfma_query.h).  One instantiation unit holds one variant
+// of one group of shapes (nwe_mfma_inst.hip); the dispatcher's table has one launcher per shape and variant.
+//   plain: eight kernels (three-pass / single-pass, packets / sample split, lean / full)
+//   term:  four, early termination (TERM; lean)        share: four, shared coarse pass (SHARE; lean)
+//   tail:  two, render_mfma_tail_kernel (three-pass / single-pass, each holding both decompositions; lean)
+enum Variant { kVariantPlain, kVariantTerm, kVariantShare, kVariantTail, kVariants };
+
+// Whether a shape has a variant's kernels: the terminating and the sharing kernels exist for the product formulations,
+// kFormReference is a comparison path; every form has the plain kernels and, with them, the queue and the tail kernel.
+constexpr bool variant_built(int variant, int form) {
+    return variant == kVariantTerm || variant == kVariantShare ? form != kFormReference : true;
+}
+
+// The grid of a queued MFMA launch of n work items (nwe_debug_set_work_queue): n plus a quarter, rounded up to a multiple of 8.
+// The hardware deals a grid's workgroups to the 8 XCDs in turn, an eighth each; with a quarter more workgroups than items an
+// XCD up to 25 % faster than the mean still finds workgroups in its eighth to take tickets with.
+inline unsigned queue_grid(unsigned n) { return (unsigned)(((uint64_t)n + (n + 3) / 4 + 7) / 8 * 8); }
+
+// workgroups (= work items) of a launch of `rays` rays (split: one packet per workgroup)
+inline unsigned mfma_workgroups(int64_t rays, bool split) {
+    const int64_t per_wg = split ? kRaysPerWave : kWaves * kRaysPerWave;
+    return (unsigned)((rays + per_wg - 1) / per_wg);
+}
+
+// ---- one launch group: the MFMA launches of one stage of a call ----
+
+struct PassDesc {
+    int64_t n_rays = 0;
+    int n_samples = 0, n_importance = 0;
+    int role = kShareOff;          // costs the launch: a producer runs the coarse pass alone, a consumer the fine pass alone
+    int variant = kVariantPlain;   // the kernels the stage takes: plain, term or share; -1 = none can serve it (the plan is not ok)
+    bool lean = false;             // only rgb / depth / acc / flags of pinhole views, no hook, no table (is_lean without the stamps)
+    bool stamps = false;           // a stamp buffer is set (nwe_debug_set_stamps): such a launch is not lean ...
+    bool stamped_build = false;    // ... except, in a -DNWE_STAMPS build, for the tail path, whose kernel stamps all the same
+    bool tail_built = false;       // the shape has the tail kernel
+    int decomposition = -1;        // nwe_debug_set_decomposition: -1 = by cost, 0 / 1 / 2 forces a plan
+    int queue_mode = -1;           // nwe_debug_set_work_queue: -1 = a launch with more work items than CUs, 1 = every launch
+    bool may_queue = false;        // the queue may be used at all: plain kernels only, and not under queue mode 0
+    bool side = false;             // a side stream is on offer for the second launch (NWE_WORK_QUEUE_BACKFILL)
+    bool tail = false;             // the tail path is allowed (NWE_WORK_QUEUE_TAIL)
+};
+
+// One kernel launch: `rays` rays from ray_first on, as `items` work items of four packets or (split) one packet each; grid = the
+// workgroups of a queued launch, which take tickets from the call's counter of this launch's index, 0 = dealt by the hardware.
+struct LaunchPlan {
+    int64_t ray_first = 0, rays = 0;
+    bool split = false;
+    unsigned items = 0, grid = 0;
+};
+
+enum Fork { kForkNone, kForkFront, kForkBehind };
+
+struct PassPlan {
+    bool ok = false;          // false: no kernel serves the description (the caller refuses the call); the rest then says nothing
+    int variant = kVariantPlain;
+    int plan = -1;            // 0 = all packets, 1 = all sample-split, 2 = hybrid: full rounds as packets, the ragged rest sample-split
+    int n_launches = 0;       // 1, or 2 under plan 2 (either of which may be empty)
+    LaunchPlan launch[2];
+    // Plan 2 with a queued launch and a side stream on offer: the second launch goes to the side stream, which forks from the
+    // caller's stream in front of the first launch (backfill: its quarter-size items are there the moment the packets run out)
+    // or - tail path - behind it (the second launch reads the third counter's final value), and is joined behind the second.
+    int fork = kForkNone;
+    // The tail path: the surplus workgroups of the queued packets launch render the split items (tail kernel, both launches),
+    // taken only when they cover every one of them; tail_items = those items, 0 when the path is not taken.
+    bool tail = false;
+    unsigned tail_items = 0;
+    bool queued() const { return launch[0].grid || launch[1].grid; }
+};
+
+PassPlan plan_pass(const PassDesc& d, int cus);
+
+// ---- the whole call ----
+
+struct CallDesc {
+    int64_t n_rays = 0;
+    int64_t n_rep = 0;             // representatives of the call at the context's k (share_n_rep): the producer's rays under sharing
+    int n_samples = 0, n_importance = 0;
+    bool mfma = false;             // an MFMA precision (the fp32 launcher has no plan: its passes are not planned)
+    bool term = false;             // nwe_set_early_termination > 0
+    int share_k = 1;               // nwe_set_shared_coarse
+    bool separate = false;         // nwe_set_separate_passes
+    bool lean = false, stamps = false, stamped_build = false;   // as in PassDesc
+    bool w_in = false;             // the coarse-weights hook is armed (nwe_debug_set_coarse_weights)
+    bool want_weights_coarse = false, want_flags = false;        // outputs requested
+    bool built[2][kVariants] = {};                               // per network (coarse, fine): the variants its shape has
+    int decomposition = -1, queue_mode = -1;
+    bool backfill = true, tail = true;
+};
+
+// One stage = one launch group with its own RenderArgs: the coarse stage (the producer of a shared coarse pass, the coarse
+// launch of separate passes) where the call has one, and the main stage, which every call has.
+struct StagePlan {
+    bool active = false;
+    int role = kShareOff;     // with k: RenderArgs::share = role | k << 8
+    int64_t n_rays = 0;
+    int n_importance = 0;
+    int net = 0;              // the network (0 coarse, 1 fine) in BOTH descriptor slots under separate passes; -1: (coarse, fine)
+    PassPlan pass;            // MFMA precisions only
+};
+
+struct CallPlan {
+    bool separate = false;        // two launches, each with its own network's kernels
+    bool share = false;           // ... through the sharing kernels (and every shared coarse pass)
+    bool full = false;            // ... through the full kernels: separate && !share
+    bool coarse_launch = false;   // the call has a coarse stage (none with the coarse-weights hook armed under `full`)
+    bool may_queue = false;       // a launch of the main stage is queued: the slot provides zeroed counters and, with the
+    bool need_side = false;       //   backfill on, the side streams exist
+    bool need_evals = false;      // early termination: the slot provides a zeroed evaluation counter
+    int share_k = 1;              // the k in both stages' share word
+    int64_t table_elems = 0;      // the slot's weight table must hold this many floats (0: none, or the caller's own table serves)
+    bool coarse_flags = false;    // the coarse launch's flags go through a word of the slot's (masked into the caller's)
+    int64_t evals_full = 0, evals_run = 0, share_rays = 0;   // nwe_last_ray_evaluations, nwe_last_coarse_launch
+    StagePlan coarse, main;
+};
+
+CallPlan plan_call(const CallDesc& c, int cus);
+
+}  // namespace nwe
