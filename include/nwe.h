@@ -427,6 +427,67 @@ int nwe_get_shared_coarse(const nwe_ctx *ctx);
 int nwe_set_separate_passes(nwe_ctx *ctx, int on);
 int nwe_get_separate_passes(const nwe_ctx *ctx);
 
+/* Occupancy grid, opt-in: a context may hold ONE grid; none (the default) changes nothing.  A grid is an axis-aligned box
+ * lo[3] < hi[3] in world coordinates, a resolution res = (rx, ry, rz) and rx * ry * rz bits, 1 = occupied: each axis 1..1024,
+ * fewer than 2^31 cells in all; bit (ix * ry + iy) * rz + iz sits in word >> 5 at bit & 31 (the layout of a [rx, ry, rz]
+ * array, z fastest).
+ * The rule, per sample and in BOTH passes:
+ *   - the point is the fp32 point the kernels encode: o + d * z, multiply then add (handler.py:223 / :246), before the
+ *     division by 10;
+ *   - its cell is floorf((p_c - lo_c) * inv_c) per axis, a plain fp32 subtraction and multiplication, with
+ *     inv_c = (float)r_c / (hi_c - lo_c) formed once on the host in fp32 (nwe_get_occupancy reports it);
+ *   - a point that is not finite, or whose cell index is outside 0 .. r_c - 1 on any axis, is OCCUPIED: outside the box
+ *     everything is evaluated;
+ *   - a sample in an empty cell has raw = (0, 0, 0, 0) in place of the network's output: in reference terms run_network's rows
+ *     (nerf/models/model_utils.py:13-30) are replaced before raw2outputs, in the coarse pass - so its weight feeding sample_pdf
+ *     is 0 - and in the fine pass alike.  All four channels, not only sigma: the result of a ray then depends on nothing but
+ *     the ray and the grid, never on which rays share its workgroup, and a non-finite colour under a zero weight cannot leak.
+ * The skip is a pure optimisation under that rule: a workgroup does not evaluate a sample iteration in which every live ray
+ * it owns is in an empty cell (the sample-split plan: all four samples of the iteration); in a mixed iteration the network
+ * runs and the masked rays' outputs are replaced.  Frames stay bit-identical across the two work decompositions, the hybrid
+ * plan, row tiles, pose batches and the tiles of nwe_render_tiled, as without a grid.  Two identities follow:
+ *   - a grid with every bit set renders the bits of the same call without a grid;
+ *   - a grid is EXACT for a network whose sigma_raw is <= 0 and finite, with finite colours, throughout every cell marked
+ *     empty: it renders, bit for bit, what the same call renders without one.
+ * Anything else is an approximation whose size is the grid's own error: density the grid calls empty is not rendered.
+ * Honoured by calls that request nothing but rgb / depth / acc / flags of pinhole views - nwe_render and nwe_render_tiled - in
+ * all three precisions, for the folded and the no-view-dirs formulations, with or without importance samples.  While a grid
+ * is set every other call is refused with NWE_ERR_UNSUPPORTED and a message that names the setting, behind every refusal the
+ * call has without it: any further output, all of nwe_render_rays with its hooks and training tables, under the MFMA
+ * precisions a network packed unfolded (nwe_debug_set_fold(0)) or a shape whose occupancy kernel was not built (NWE_PREC_F32
+ * renders both), and every call while early termination (min_transmittance > 0), a shared coarse pass (k > 1) or separate
+ * passes are on as well: these combinations are not built.  nwe_query_points ignores the grid.
+ * nwe_set_network and nwe_set_network_no_view_dirs CLEAR the grid - a grid describes the networks it was made for; a refused
+ * one leaves it in place, like the network.  The grid calls below wait for this context's launches in flight, like
+ * nwe_set_sampling.
+ * nwe_last_ray_evaluations: out[0] = for every group of rays, its live rays x the samples of the iterations it evaluated, both
+ * passes.  A group is 128 consecutive rays of a launch (packets), 32 (sample split: an iteration is four samples), or - under
+ * NWE_PREC_F32 - 16 consecutive rays of the call; nwe_last_launch_parts says which rays went to which launch.
+ *   nwe_set_occupancy    copies the words ((rx ry rz + 31) / 32 of them, from the host or - bits_on_device != 0 - the context's
+ *                        device) into a buffer the context owns.  Refused by name (NWE_ERR_INVALID): null pointers, a box that
+ *                        is not finite or not lo < hi on every axis, a resolution outside the domain.
+ *   nwe_clear_occupancy  no grid.
+ *   nwe_get_occupancy    the grid's box, resolution, the fp32 inv the kernels multiply by and the number of occupied cells; any
+ *                        pointer may be null.  NWE_ERR_STATE (and nothing written) when no grid is set.
+ *   nwe_occupancy_copy   the words, n_words = (rx ry rz + 31) / 32; bits behind the last cell are 0.
+ * Set, clear, get and copy work on a host-only context (the bits are kept on the host there).
+ *   nwe_build_occupancy  builds the grid from the networks that are set, on the device: per cell a probes^3 lattice of points,
+ *                        probes 1..4, along an axis at ((float)i + ((float)j + 0.5f) / probes) * step + lo for cell i and probe j,
+ *                        step = (float)(((double)hi - (double)lo) / r), every operation rounded to fp32 on its own (probes = 1:
+ *                        the cell's centre); sigma_raw of EVERY set network there, by the sigma-only path of nwe_query_points
+ *                        in `precision`; a cell is occupied if any value is > threshold or not finite; then `dilate` (0..2)
+ *                        steps of dilation with the 3 x 3 x 3 box.  The probes are evaluated in chunks through a scratch buffer
+ *                        the context keeps.  Synchronous: queued on `stream` and waited for.  Refused: a host-only context,
+ *                        no network set (NWE_ERR_STATE); the box and resolution as above, probes, dilate, a NaN threshold,
+ *                        an unknown precision (NWE_ERR_INVALID); an MFMA precision for a shape without a query kernel
+ *                        (NWE_ERR_UNSUPPORTED, the query's own message). */
+int nwe_set_occupancy(nwe_ctx *ctx, const float *lo, const float *hi, const int *res, const uint32_t *bits, int bits_on_device);
+int nwe_clear_occupancy(nwe_ctx *ctx);
+int nwe_get_occupancy(const nwe_ctx *ctx, float *lo, float *hi, int *res, float *inv, int64_t *occupied_cells);
+int nwe_occupancy_copy(const nwe_ctx *ctx, uint32_t *host_words, int64_t n_words);
+int nwe_build_occupancy(nwe_ctx *ctx, const float *lo, const float *hi, const int *res, int probes, float threshold, int dilate,
+                        int precision, void *stream);
+
 /* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
  * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1 without separate
  * passes, n_importance == 0, or a call armed with nwe_debug_set_coarse_weights).  Under separate passes with k = 1 it is the
@@ -438,8 +499,8 @@ int nwe_last_coarse_launch(nwe_ctx *ctx, float *ms, int64_t *rays);
  * rules about refused calls; blocks like it): out[0] = executed, counted as the rays of each workgroup times the samples
  * that workgroup walked, out[1] = the full count n_rays * (n_samples [+ n_samples + n_importance]).  A launch without early
  * termination reports out[0] == out[1], except under a shared coarse pass (nwe_set_shared_coarse, k > 1 and n_importance > 0),
- * where out[0] = n_rep * n_samples + n_rays * (n_samples + n_importance) for the n_rep representatives of the call.  Shows the
- * skip without a clock. */
+ * where out[0] = n_rep * n_samples + n_rays * (n_samples + n_importance) for the n_rep representatives of the call, and under an
+ * occupancy grid (nwe_set_occupancy), which counts the iterations each group of rays evaluated.  Shows the skip without a clock. */
 int nwe_last_ray_evaluations(nwe_ctx *ctx, int64_t *out2);
 
 /* Training-mode forward (nerf/training/nerf_replica_training_handler.py:553-580; forward only): the NEXT
@@ -532,7 +593,7 @@ typedef struct nwe_plan_stage {
     int64_t n_rays;       /* the stage's rays: the producer's are the representatives */
     int32_t n_importance;
     int32_t net;          /* the network (0 coarse, 1 fine) in both descriptor slots, -1: (coarse, fine) */
-    int32_t variant;      /* the kernels: 0 plain, 1 terminating, 2 sharing */
+    int32_t variant;      /* the kernels: 0 plain, 1 terminating, 2 sharing, 3 occupancy grid */
     int32_t plan;         /* nwe_debug_last_plan: 0 packets, 1 sample split, 2 packets + split rest */
     int32_t n_launches;   /* 1, or 2 under plan 2 */
     int32_t fork;         /* 0 the second launch follows the first on the caller's stream; it goes to the side stream, which forks

@@ -28,7 +28,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_debug_set_work_queue", "nwe_debug_get_work_queue", "nwe_debug_get_work_queue_backfill", "nwe_debug_queue_grid", "nwe_debug_last_queue",
            "nwe_debug_get_work_queue_tail", "nwe_debug_last_tail", "nwe_debug_last_tail_rest",
            "nwe_query_points", "nwe_last_query_ms", "nwe_debug_set_query_steps",
-           "nwe_packed_colour_finite", "nwe_debug_set_colour_skip", "nwe_debug_get_colour_skip", "nwe_debug_plan")
+           "nwe_packed_colour_finite", "nwe_debug_set_colour_skip", "nwe_debug_get_colour_skip", "nwe_debug_plan",
+           "nwe_set_occupancy", "nwe_clear_occupancy", "nwe_get_occupancy", "nwe_occupancy_copy", "nwe_build_occupancy")
 
 
 class Outputs(C.Structure):
@@ -142,6 +143,11 @@ def load() -> C.CDLL:
         "nwe_debug_set_colour_skip": (I, [P, I]),
         "nwe_debug_get_colour_skip": (I, [P]),
         "nwe_debug_plan": (I, [P, I, I, I, I, I, I64, C.POINTER(Outputs), C.c_uint, I, I, C.POINTER(PlanReport)]),
+        "nwe_set_occupancy": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), P, I]),
+        "nwe_clear_occupancy": (I, [P]),
+        "nwe_get_occupancy": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), C.POINTER(F), C.POINTER(I64)]),
+        "nwe_occupancy_copy": (I, [P, P, I64]),
+        "nwe_build_occupancy": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), I, F, I, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -1,5 +1,6 @@
 // C ABI of libnwe_hip.so (include/nwe.h): context, device resources, table upload, kernel launches.  Weight packing: nwe_pack.cpp.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -93,6 +94,17 @@ struct RenderSlot : Slot {
     unsigned tail_items = 0;
 };
 
+// The occupancy grid of a context (nwe_set_occupancy, nwe_build_occupancy).  The words on the host are the truth of
+// nwe_get_occupancy / nwe_occupancy_copy and all there is on a host-only context; a device context also holds them, and the
+// descriptor the occupancy kernels read, in buffers of its own.
+struct Occupancy {
+    bool set = false;
+    float lo[3] = {}, hi[3] = {}, inv[3] = {};
+    int res[3] = {};
+    int64_t cells = 0, occupied = 0;
+    std::vector<uint32_t> bits;
+};
+
 thread_local std::string g_create_error;
 
 }  // namespace
@@ -132,6 +144,10 @@ struct nwe_ctx {
     float min_trans = 0.f;    // nwe_set_early_termination: 0 = off
     int share_k = 1;          // nwe_set_shared_coarse: 1 = off
     int separate = 0;         // nwe_set_separate_passes: 0 = off
+    Occupancy occ;            // nwe_set_occupancy / nwe_build_occupancy: occ.set = a grid is set
+    DevBuf<uint32_t> d_occ_bits, d_occ_tmp;   // the grid's words on the device; nwe_build_occupancy's second buffer for the dilation
+    DevBuf<OccGrid> d_occ;                    // the descriptor RenderArgs::occ points to
+    DevBuf<float> d_occ_scratch;              // nwe_build_occupancy: probe points and their sigma, one chunk
     int decomposition = -1;   // nwe_debug_set_decomposition
     int work_queue = -1;      // nwe_debug_set_work_queue; a new context takes NWE_WORK_QUEUE=0|1 from the environment
     bool backfill = true;     // the hybrid plan's second launch on the slot's own stream; NWE_WORK_QUEUE_BACKFILL=0: behind the first
@@ -357,6 +373,23 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhol
         if (ctx->ni > 0 && ctx->net[0].form != ctx->net[1].form)
             return fail(ctx, NWE_ERR_UNSUPPORTED, separate + "coarse and fine networks must be packed in the same formulation (nwe_debug_set_fold); use NWE_PREC_F32" + separate_off);
     }
+    if (ctx->occ.set) {
+        const Occupancy& g = ctx->occ;
+        const std::string grid = "an occupancy grid is set (nwe_set_occupancy, " + std::to_string(g.res[0]) + " x " + std::to_string(g.res[1]) + " x " +
+                                 std::to_string(g.res[2]) + "): ";
+        const char* grid_off = "; call nwe_clear_occupancy for this call";
+        if (ctx->min_trans > 0.f)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with early termination (nwe_set_early_termination, min_transmittance = " +
+                                                      std::to_string(ctx->min_trans) + "); switch one of them off");
+        if (ctx->share_k > 1)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with the shared coarse pass (nwe_set_shared_coarse, k = " +
+                                                      std::to_string(ctx->share_k) + "); switch one of them off");
+        if (ctx->separate)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with separate passes (nwe_set_separate_passes); switch one of them off");
+        TRY(check_lean_mode(ctx, out, precision, pinhole, grid, grid_off, "nwe_render_rays, its hooks and its training tables do not read the grid",
+                            "occupancy", kVariantOcc));
+        if (ctx->stamps) return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "a stamped launch (nwe_debug_set_stamps) has no occupancy kernel" + grid_off);
+    }
     return NWE_OK;
 }
 
@@ -386,6 +419,7 @@ CallDesc describe_call(const nwe_ctx* ctx, const RenderArgs& a, int precision) {
     d.n_samples = a.n_samples; d.n_importance = a.n_importance;
     d.mfma = precision != NWE_PREC_F32;
     d.term = a.min_trans > 0.f;
+    d.occ = ctx->occ.set;
     d.share_k = ctx->share_k; d.separate = ctx->separate != 0;
     RenderArgs unstamped = a;
     unstamped.stamps = nullptr;
@@ -468,6 +502,7 @@ int launch(nwe_ctx* ctx, RenderSlot& slot, RenderArgs& a, int precision, hipStre
     const bool mfma = precision != NWE_PREC_F32, three_pass = precision == NWE_PREC_F16X3;
     TRY(provide(ctx, slot, p, stream));
     const RenderArgs prod = stage_args(p, slot, a);
+    if (p.occ) a.occ = ctx->d_occ.get();   // the slot of `stamps`, which such a call does not have (check_ready)
     const NetState &nc = ctx->net[0], &nf = ctx->net[ctx->ni > 0 ? 1 : 0];
     // the launch's own descriptors: whether its lean kernels may take the hollow path with this network (nwe_debug_set_colour_skip)
     const auto with_skip = [&](const NetState& n) {
@@ -478,7 +513,10 @@ int launch(nwe_ctx* ctx, RenderSlot& slot, RenderArgs& a, int precision, hipStre
     const NetMfma mf[2] = {with_skip(nc), with_skip(nf)};
     // one stage: (coarse, fine) in the descriptor slots of one fused kernel, the stage's own network twice under separate passes
     const auto run = [&](const StagePlan& s, const RenderArgs& args, const LaunchResources& res, LaunchReport* report) {
-        if (!mfma) { launch_render_f32(args, nc.f32, nf.f32, stream); return true; }
+        if (!mfma) {
+            if (p.occ) launch_render_f32_occ(args, nc.f32, nf.f32, stream); else launch_render_f32(args, nc.f32, nf.f32, stream);
+            return true;
+        }
         return launch_render_mfma(args, mf[s.net < 0 ? 0 : s.net], mf[s.net < 0 ? 1 : s.net], three_pass, s.pass, res, stream, report);
     };
     const int rc = record_launch(ctx, slot, stream, [&]() -> int {
@@ -674,6 +712,7 @@ int set_network(nwe_ctx* c, int which, const NetShape& shape, const float* const
         n.mf.bias = n.mfma_ok ? n.d_bias.get() : nullptr;
     }
     n.set = true;
+    c->occ.set = false;   // a grid describes the networks it was made for (include/nwe.h); the wait above covers its readers
     return NWE_OK;
 }
 
@@ -696,6 +735,53 @@ constexpr float kMinPartMs = 1e-5f;
 
 // The most recent recorded render launch (nwe_last_kernel_ms, nwe_last_launch_parts), or null
 const RenderSlot* last_render(const nwe_ctx* c) { return c->host_only || c->last_slot < 0 || !c->slots[c->last_slot].used ? nullptr : &c->slots[c->last_slot]; }
+
+// ---- occupancy grid (nwe_set_occupancy, nwe_build_occupancy) ----
+
+int64_t occ_words(int64_t cells) { return (cells + 31) / 32; }
+
+// The refusals nwe_set_occupancy and nwe_build_occupancy share, by name: null pointers, a box that is not finite or not
+// lo < hi on every axis, a resolution outside 1 .. 1024 per axis (1024^3 = 2^30 cells, below 2^31 in all).
+int check_occupancy_box(nwe_ctx* c, const float* lo, const float* hi, const int* res) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!lo || !hi || !res) return fail(c, NWE_ERR_INVALID, "occupancy: null lo, hi or resolution");
+    for (int i = 0; i < 3; ++i) {
+        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !std::isfinite(hi[i] - lo[i]))
+            return fail(c, NWE_ERR_INVALID, "occupancy: the box must be finite");
+        if (!(lo[i] < hi[i])) return fail(c, NWE_ERR_INVALID, "occupancy: the box must have lo < hi on every axis");
+    }
+    for (int i = 0; i < 3; ++i)
+        if (res[i] < 1 || res[i] > 1024) return fail(c, NWE_ERR_INVALID, "occupancy: the resolution must be in 1..1024 on every axis");
+    if ((int64_t)res[0] * res[1] * res[2] >= ((int64_t)1 << 31)) return fail(c, NWE_ERR_INVALID, "occupancy: the grid must have fewer than 2^31 cells");
+    return NWE_OK;
+}
+
+// Makes `words` (host, occ_words(cells) of them) the context's grid.  The bits behind the last cell are cleared; on a device
+// context the words and the descriptor go to the context's own buffers, which no launch reads any more (the caller has waited).
+int install_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* res, std::vector<uint32_t>&& words) {
+    Occupancy g;
+    g.cells = (int64_t)res[0] * res[1] * res[2];
+    for (int i = 0; i < 3; ++i) {
+        g.lo[i] = lo[i]; g.hi[i] = hi[i]; g.res[i] = res[i];
+        g.inv[i] = (float)res[i] / (hi[i] - lo[i]);   // fp32, once: what the kernels multiply by (nwe_get_occupancy reports it)
+    }
+    if (g.cells & 31) words.back() &= (1u << (g.cells & 31)) - 1u;
+    for (const uint32_t w : words) g.occupied += __builtin_popcount(w);
+    g.bits = std::move(words);
+    if (!c->host_only) {
+        c->occ.set = false;   // a failing upload leaves no grid rather than the old one's descriptor over new words
+        HIPCHK(c, c->d_occ_bits.reserve(g.bits.size()));
+        HIPCHK(c, c->d_occ.reserve(1));
+        HIPCHK(c, hipMemcpy(c->d_occ_bits.get(), g.bits.data(), g.bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        OccGrid d = {};
+        for (int i = 0; i < 3; ++i) { d.lo[i] = g.lo[i]; d.inv[i] = g.inv[i]; d.res[i] = g.res[i]; }
+        d.bits = c->d_occ_bits.get();
+        HIPCHK(c, hipMemcpy(c->d_occ.get(), &d, sizeof(d), hipMemcpyHostToDevice));
+    }
+    g.set = true;
+    c->occ = std::move(g);
+    return NWE_OK;
+}
 
 }  // namespace
 
@@ -1107,6 +1193,109 @@ int nwe_set_separate_passes(nwe_ctx* c, int on) {
     return NWE_OK;
 }
 int nwe_get_separate_passes(const nwe_ctx* c) { return c ? c->separate : -1; }
+int nwe_set_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* res, const uint32_t* bits, int bits_on_device) {
+    TRY(check_occupancy_box(c, lo, hi, res));
+    if (!bits) return fail(c, NWE_ERR_INVALID, "occupancy: null bits");
+    if (bits_on_device && c->host_only) return fail(c, NWE_ERR_INVALID, "occupancy: a host-only context takes its bits from the host");
+    std::vector<uint32_t> words((size_t)occ_words((int64_t)res[0] * res[1] * res[2]));
+    if (c->host_only) {
+        std::memcpy(words.data(), bits, words.size() * sizeof(uint32_t));
+        return install_occupancy(c, lo, hi, res, std::move(words));
+    }
+    ON_DEVICE(c);
+    TRY(wait_for_launches(c));   // a queued launch still reads the old grid
+    if (bits_on_device) HIPCHK(c, hipMemcpy(words.data(), bits, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    else std::memcpy(words.data(), bits, words.size() * sizeof(uint32_t));
+    return install_occupancy(c, lo, hi, res, std::move(words));
+}
+
+int nwe_clear_occupancy(nwe_ctx* c) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!c->host_only && c->occ.set) {
+        ON_DEVICE(c);
+        TRY(wait_for_launches(c));
+    }
+    c->occ = Occupancy{};
+    return NWE_OK;
+}
+
+int nwe_get_occupancy(const nwe_ctx* c, float* lo, float* hi, int* res, float* inv, int64_t* occupied_cells) {
+    if (!c) return NWE_ERR_INVALID;
+    const Occupancy& g = c->occ;
+    if (!g.set) return NWE_ERR_STATE;   // no grid is set: the outputs stay untouched (and so does the error text of a const context)
+    for (int i = 0; i < 3; ++i) {
+        if (lo) lo[i] = g.lo[i];
+        if (hi) hi[i] = g.hi[i];
+        if (res) res[i] = g.res[i];
+        if (inv) inv[i] = g.inv[i];
+    }
+    if (occupied_cells) *occupied_cells = g.occupied;
+    return NWE_OK;
+}
+
+int nwe_occupancy_copy(const nwe_ctx* c, uint32_t* host_words, int64_t n_words) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!c->occ.set) return NWE_ERR_STATE;
+    return copy_out(&c->occ.bits, host_words, n_words);
+}
+
+int nwe_build_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* res, int probes, float threshold, int dilate,
+                        int precision, void* stream_) {
+    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
+    TRY(check_occupancy_box(c, lo, hi, res));
+    if (probes < 1 || probes > 4) return fail(c, NWE_ERR_INVALID, "occupancy: probes must be in 1..4");
+    if (dilate < 0 || dilate > 2) return fail(c, NWE_ERR_INVALID, "occupancy: dilate must be in 0..2");
+    if (threshold != threshold) return fail(c, NWE_ERR_INVALID, "occupancy: the threshold must not be NaN");
+    if (precision != NWE_PREC_F16X3 && precision != NWE_PREC_F16X1 && precision != NWE_PREC_F32)
+        return fail(c, NWE_ERR_INVALID, "unknown precision");
+    if (!c->net[0].set && !c->net[1].set) return fail(c, NWE_ERR_STATE, "occupancy: no network is set");
+    for (const NetState& n : c->net)
+        if (n.set && precision != NWE_PREC_F32 && !n.mfma_ok)
+            return fail(c, NWE_ERR_UNSUPPORTED,
+                        "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
+    hipStream_t stream = (hipStream_t)stream_;
+    ON_DEVICE(c);
+    TRY(wait_for_launches(c));   // the build ends in a new grid: a queued launch still reads the old one
+    OccBuild b = {};
+    for (int i = 0; i < 3; ++i) {
+        b.lo[i] = lo[i]; b.res[i] = res[i];
+        b.step[i] = (float)(((double)hi[i] - (double)lo[i]) / (double)res[i]);
+    }
+    b.probes = probes;
+    const int per_cell = probes * probes * probes;
+    const int64_t cells = (int64_t)res[0] * res[1] * res[2], words = occ_words(cells);
+    // the probes of a chunk of cells and their sigma in a scratch buffer the context keeps: 2^20 points (16 MB) at the most
+    const int chunk_cells = (int)std::min<int64_t>(cells, std::max(1, (1 << 20) / per_cell));
+    HIPCHK(c, c->d_occ_scratch.reserve((size_t)chunk_cells * per_cell * 4));
+    HIPCHK(c, c->d_occ_tmp.reserve((size_t)words * 2));
+    float* points = c->d_occ_scratch.get();
+    float* sigma = points + (size_t)chunk_cells * per_cell * 3;
+    uint32_t* buf[2] = {c->d_occ_tmp.get(), c->d_occ_tmp.get() + words};
+    HIPCHK(c, hipMemsetAsync(buf[0], 0, (size_t)words * sizeof(uint32_t), stream));
+    for (const NetState& n : c->net) {
+        if (!n.set) continue;
+        for (int64_t first = 0; first < cells; first += chunk_cells) {
+            const int count = (int)std::min<int64_t>(chunk_cells, cells - first);
+            const int64_t n_points = (int64_t)count * per_cell;
+            launch_occ_probe_points(b, first, count, points, stream);
+            QueryArgs q = {};   // the sigma-only query of nwe_query_points: no directions, the density trunk alone where it is built
+            q.points = points; q.sigma = sigma; q.n_points = (int)n_points; q.points_per_dir = 1; q.density_only = 1;
+            if (precision == NWE_PREC_F32) launch_query_f32(q, n.f32, c->query_steps, c->cus, stream);
+            else if (!launch_query_mfma(q, n.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
+                return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
+            launch_occ_reduce_bits(sigma, first, count, per_cell, threshold, buf[0], stream);
+        }
+    }
+    int cur = 0;
+    for (int d = 0; d < dilate; ++d, cur ^= 1)
+        launch_occ_dilate(buf[cur], buf[cur ^ 1], res, stream);
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint32_t> host((size_t)words);
+    HIPCHK(c, hipMemcpyAsync(host.data(), buf[cur], (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    return install_occupancy(c, lo, hi, res, std::move(host));
+}
+
 int nwe_set_train_tables(nwe_ctx* c, const float* t_rand_dev, const float* noise_coarse_dev, const float* noise_fine_dev, const float* u_sorted_dev) {
     return set_on(c, [&] { c->trn_t = t_rand_dev; c->trn_nc = noise_coarse_dev; c->trn_nf = noise_fine_dev; c->trn_u = u_sorted_dev; });
 }

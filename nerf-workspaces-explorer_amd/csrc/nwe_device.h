@@ -16,6 +16,15 @@
 
 namespace nwe {
 
+// The occupancy grid of a context (include/nwe.h, nwe_set_occupancy) as the occupancy instantiations of both kernels read it: a
+// small struct in device memory that RenderArgs points to.  inv = (float)res / (hi - lo), formed once on the host in fp32.
+struct OccGrid {
+    float lo[3], inv[3];
+    int res[3];
+    int pad;
+    const uint32_t* bits;   // bit (ix * ry + iy) * rz + iz in word >> 5 at bit & 31; 1 = occupied
+};
+
 // Kernel arguments common to both kernels (passed by value).
 struct RenderArgs {
     // ray source: either precomputed rays [n_rays,11] or pinhole poses
@@ -49,7 +58,12 @@ struct RenderArgs {
     const float* u_rand;     // [n_rays, ni]      inverse-CDF arguments, ASCENDING per ray   (rays.py:98)
     int white_bkgd;          // rendering.white_background (model_utils.py:97-98): rgb += 1 - acc
     int n_samples, n_importance;
-    unsigned long long* stamps;  // diagnostic builds (-DNWE_STAMPS): per-wave cycle sums, else unused
+    union {
+        unsigned long long* stamps;  // diagnostic builds (-DNWE_STAMPS): per-wave cycle sums, else unused
+        // The occupancy instantiations only (render_mfma_occ_kernel, render_f32_kernel<.., OCC>): the context's grid.  A call
+        // with a grid is lean and never stamped, so the slot is free; `evals` below counts what such a launch evaluated.
+        const OccGrid* occ;
+    };
     nwe_outputs out;
     // early ray termination (nwe_set_early_termination): read by the terminating instantiations only, which a launch takes
     // exactly if min_trans > 0.  Behind `out`, so that no other kernel's argument offsets move.
@@ -225,6 +239,23 @@ __device__ __forceinline__ void point_at(const Ray& r, float z, float& px, float
     px = __fadd_rn(r.ox, __fmul_rn(r.dx, z));
     py = __fadd_rn(r.oy, __fmul_rn(r.dy, z));
     pz = __fadd_rn(r.oz, __fmul_rn(r.dz, z));
+}
+
+// The occupancy rule of include/nwe.h for one sample point - the fp32 point the kernels encode, before the division by 10:
+// cell = floorf((p - lo) * inv) per axis, plain fp32 subtract and multiply; true = the point lies in a cell whose bit is 0.
+// A point that is not finite, or whose cell is outside 0 .. res - 1 on any axis, is occupied: NaN fails every comparison, +-inf
+// the range.  The word is read only by lanes inside the box, so the load never leaves the grid's buffer.
+__device__ __forceinline__ bool occ_empty(const OccGrid* g, float px, float py, float pz) {
+    const float cx = floorf(__fmul_rn(__fsub_rn(px, g->lo[0]), g->inv[0]));
+    const float cy = floorf(__fmul_rn(__fsub_rn(py, g->lo[1]), g->inv[1]));
+    const float cz = floorf(__fmul_rn(__fsub_rn(pz, g->lo[2]), g->inv[2]));
+    const int rx = g->res[0], ry = g->res[1], rz = g->res[2];
+    bool empty = false;
+    if (cx >= 0.f && cx < (float)rx && cy >= 0.f && cy < (float)ry && cz >= 0.f && cz < (float)rz) {
+        const int cell = ((int)cx * ry + (int)cy) * rz + (int)cz;   // below 2^31 by the ABI's check
+        empty = ((g->bits[cell >> 5] >> (cell & 31)) & 1u) == 0u;
+    }
+    return empty;
 }
 
 // Front-to-back alpha compositing of one ray, one sample per step.  nerf/models/model_utils.py:49-100.

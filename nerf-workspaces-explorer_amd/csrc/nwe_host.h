@@ -12,6 +12,9 @@ namespace nwe {
 // a.min_trans > 0 (early ray termination, with a.evals set) takes the terminating instantiation of either kernel,
 // a.share != kShareOff (shared coarse pass, with a.share_w set) the sharing one
 void launch_render_f32(const RenderArgs& a, const NetF32& nc, const NetF32& nf, hipStream_t stream);
+// the occupancy kernel of the fp32 path (an occupancy grid is set: a.occ and a.evals); the MFMA launcher takes its own from the
+// plan's variant
+void launch_render_f32_occ(const RenderArgs& a, const NetF32& nc, const NetF32& nf, hipStream_t stream);
 
 // true if a kernel instantiation exists for this shape (in_dir == 0 exactly for kFormNoViewDirs)
 bool mfma_supported(int D, int W, int in_xyz, int in_dir, int skip, int form);
@@ -72,6 +75,21 @@ int query_steps(int64_t packets, int forced, int cus);
 void launch_query_f32(const QueryArgs& a, const NetF32& net, int forced_steps, int cus, hipStream_t stream);
 // false: no query kernel for the network's shape (the shapes of mfma_supported), or its stream does not fit the instantiation
 bool launch_query_mfma(const QueryArgs& a, const NetMfma& net, bool three_pass, int forced_steps, int cus, hipStream_t stream);
+
+// ---- nwe_build_occupancy (nwe_occupancy.hip) ----
+// The box of a build as its kernels read it: per axis lo and step = (float)(((double)hi - (double)lo) / res), the step of
+// NeRFReplicaInferenceHandler.grid_centres, whose centres are the probes = 1 lattice.
+struct OccBuild {
+    float lo[3], step[3];
+    int res[3];
+    int probes;
+};
+// the probe points [n_cells * probes^3, 3] of cells first .. first + n_cells - 1, cell-major
+void launch_occ_probe_points(const OccBuild& b, int64_t first, int n_cells, float* points, hipStream_t stream);
+// ORs the bit of every cell of the chunk with a value > threshold or not finite among its per_cell values into `bits`
+void launch_occ_reduce_bits(const float* sigma, int64_t first, int n_cells, int per_cell, float threshold, uint32_t* bits, hipStream_t stream);
+// dst = src dilated by one cell with the 3 x 3 x 3 box; res = (rx, ry, rz)
+void launch_occ_dilate(const uint32_t* src, uint32_t* dst, const int* res, hipStream_t stream);
 
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);

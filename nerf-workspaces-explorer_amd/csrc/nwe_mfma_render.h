@@ -235,6 +235,56 @@ __global__ void __launch_bounds__(256) render_mfma_tail_kernel(RenderArgs a_in, 
 #include "nwe_mfma_render_item.h"
     }
 }
+// OCC: the occupancy grid (include/nwe.h, nwe_set_occupancy), for the LEAN kernels of the folded and the no-view-dirs
+// formulations, in a kernel of its own name: the other kernels keep their symbols and see no new token (NWE_ITEM_OCC).  In BOTH passes a
+// sample whose point lies in a cell marked empty has raw = (0, 0, 0, 0) in place of the network's output - a per-ray rule,
+// whatever the rays around it do - and a workgroup leaves out the evaluation of an iteration in which every live ray it owns
+// is in an empty cell: in the sample-split plan all four samples of the iteration.  In a mixed iteration the network runs and
+// the masked lanes' rr, rg, rb, rs are replaced by 0 behind it.  The density-only coarse pass and the hollow colour path are
+// the plain lean kernel's.
+// The decision is workgroup-uniform by construction and is taken at the top of a sample iteration, in front of
+// NWE_PRIME_STREAM.  Unlike early termination the vote concerns THIS iteration, so there is no lag and one barrier more:
+//   1. each lane looks up the cell of its ray's point at this iteration's depth (fresh_ray, point_at: the point
+//      NWE_EVAL_POINT encodes; one 4-byte load for a lane inside the box) and the wave votes
+//      __all(gone || empty) - in the sample-split plan also "my sample 4 it + wave lies behind the pass's last";
+//   2. lane 0 writes the vote to word [n & 1][wave] behind the LDS layout, n = the iteration's number (packets: counted over
+//      both passes, which no barrier separates; sample split: within the pass, which two barriers close);
+//   3. one __syncthreads(), which waits for every wave's LDS write;
+//   4. all four waves read the same four words [n & 1][*] and AND them: the same value in every wave.
+// Word [n & 1][w] is next written at the top of iteration n + 2 (n + 1: the other parity), and its writer gets there only
+// through the vote barrier of iteration n + 1, which the slowest wave reaches behind its read of iteration n.
+// The barrier is safe where it stands: the tile that ends the previous evaluation streams nothing behind it, so no LDS-DMA
+// piece is in flight and no barrier of the tile walk is half passed (the place where the terminating kernels leave the loop),
+// and every wave reaches it in every iteration - the skip is decided behind it, never in front.
+// A skipped iteration primes no stream and enters none of the evaluation's barriers, all four waves alike.  The packets plan
+// composites shade(0, 0, 0, 0, ..) as ever.  The sample-split plan composites the previous iteration's samples - published by
+// the vote barrier, which every wave reaches behind its own write to the exchange buffer - rotates zp and publishes its shaded
+// zero sample: the raw_in branch's iteration without a barrier of its own.  Exchange buffer [it & 1] is written at the end of
+// iteration it and was last read by drain(it - 2) in iteration it - 1, which every wave has left when one passes the vote
+// barrier of iteration it.
+// The lane's "empty" flag crosses the evaluation as the wave's ballot in two scalar registers.
+// The ray evaluations executed go to *a.evals, one atomic per wave (packets) or workgroup (sample split): its live rays x the
+// samples of the iterations its workgroup evaluated, both passes.
+template <int W, int D, int SKIP, bool X3, bool SPLIT, int FORM>
+__global__ void __launch_bounds__(256) render_mfma_occ_kernel(RenderArgs a_in, NetMfma nc, NetMfma nf) {
+    static_assert(FORM != kFormReference, "occupancy grid: lean kernels of the product formulations only");
+    constexpr bool LEAN = true, TERM = false, SHARE = false;
+    RenderArgs a = a_in;
+    const OccGrid* const occ = a_in.occ;
+    a.out.raw_coarse = a.out.raw_fine = a.out.z_fine = a.out.weights_coarse = nullptr;
+    a.out.disp = a.out.z_std = a.out.rgb_coarse = a.out.depth_coarse = a.out.acc_coarse = a.out.disp_coarse = nullptr;
+    a.out.sample_cond = a.out.sample_amp = a.out.sample_switch = a.out.feat_map = nullptr;
+    a.z_fine_in = a.raw_in_c = a.raw_in_f = a.w_in = a.t_rand = a.noise_c = a.noise_f = a.u_rand = nullptr;
+    a.stamps = nullptr; a.rays = nullptr;
+    using S = Shape<W, D>;
+    using SM = Smem<W, D, SPLIT>;
+    __shared__ __attribute__((aligned(16))) char smem[SM::TOTAL + kVoteBytes];
+    const unsigned item = blockIdx.x;   // never queued: the evaluation counter has the queue's slot
+    NWE_STAMP(const unsigned stamp_item = item;)
+#define NWE_ITEM_OCC
+#include "nwe_mfma_render_item.h"
+#undef NWE_ITEM_OCC
+}
 #undef NWE_PRIME_STREAM
 #undef NWE_EVAL_POINT
 
@@ -250,7 +300,7 @@ using RenderLauncher = void (*)(RenderArgs, const NetMfma&, const NetMfma&, bool
 // One launch of a shape's kernels of one variant for `rays` rays from ray_first on; `split` says which decomposition, and so the
 // size of a work item.  Explicitly instantiated per shape and variant (nwe_mfma_shapes.h, nwe_mfma_inst.hip), which instantiates
 // the kernels; the plan of a call's launches, and the conditions under which a variant is taken, are nwe_kernel_mfma.hip's (term:
-// is_lean(a), a.min_trans > 0, a.evals; share: a.share, a.share_w; tail: a.tail, a.share).  Nothing for a shape that does not have
+// is_lean(a), a.min_trans > 0, a.evals; share: a.share, a.share_w; occ: a.occ, a.evals; tail: a.tail, a.share).  Nothing for a shape that does not have
 // the variant, so that the instantiation exists all the same.
 template <int W, int D, int SKIP, int FORM, int VARIANT>
 void launch_one(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_pass, bool split, int64_t ray_first, int64_t rays,
@@ -276,6 +326,11 @@ void launch_one(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_p
             const RenderKernel kernels[2] = {render_mfma_tail_kernel<W, D, SKIP, true, FORM, kTailLean>,
                                              render_mfma_tail_kernel<W, D, SKIP, false, FORM, kTailLean>};
             kernel = kernels[three_pass ? 0 : 1];
+        } else if constexpr (VARIANT == kVariantOcc) {   // lean only: the caller has checked
+#define NWE_KERNEL(X3_, SPLIT_) render_mfma_occ_kernel<W, D, SKIP, X3_, SPLIT_, FORM>
+            const RenderKernel kernels[4] = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true), NWE_KERNEL(false, false)};
+#undef NWE_KERNEL
+            kernel = kernels[(three_pass ? 0 : 2) + (split ? 0 : 1)];
         } else {   // lean only: the caller has checked
 #define NWE_KERNEL(X3_, SPLIT_) render_mfma_kernel<W, D, SKIP, X3_, SPLIT_, FORM, true, VARIANT == kVariantTerm, VARIANT == kVariantShare>
             const RenderKernel kernels[4] = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true), NWE_KERNEL(false, false)};

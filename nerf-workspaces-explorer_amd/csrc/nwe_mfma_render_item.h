@@ -6,6 +6,9 @@
 //   W, D, SKIP, X3, SPLIT, FORM, LEAN, TERM, SHARE  compile-time constants (template parameters or constexpr locals)
 //   S = Shape<W, D>, SM = Smem<W, D, SPLIT>
 //   a (RenderArgs, the kernel's own copy: a.ray_first is the first ray of the item's launch), nc, nf, smem, item
+//   NWE_ITEM_OCC, defined by render_mfma_occ_kernel alone, with occ (const OccGrid*: the occupancy grid; that kernel's comment
+//   holds the argument).  The occupancy code is under the preprocessor, not under `if constexpr`, so that every other kernel
+//   compiles the very tokens it compiled before: their device code is the same to the byte (tools/device_code_digest.py).
 //   stamp_item (diagnostic builds only): the item's row group in the stamp buffer
 // and NWE_PRIME_STREAM / NWE_EVAL_POINT.  The first word of smem may hold a queued launch's ticket up to the barrier behind the
 // table copies.
@@ -101,6 +104,9 @@
 
     Composite comp;
     uint32_t flags = 0;
+#ifdef NWE_ITEM_OCC
+    int occ_evals = 0;   // the samples of the iterations this workgroup evaluated, both passes
+#endif
 #ifdef NWE_STAMPS
     unsigned long long st_enc = 0, st_sync = 0, st_mlp = 0, st_comp = 0;
     const unsigned long long st_begin = __builtin_amdgcn_s_memtime();
@@ -179,7 +185,35 @@
                     // comp holds the samples of iterations 0 .. it - 2: iteration it - 1 is composited behind this one's barrier
                     if (stops && it > 0 && __all(gone || comp.below(eps))) { it_end = it; break; }
                 }
+#ifdef NWE_ITEM_OCC
+                // the vote on this iteration's four samples, one per wave
+                unsigned long long occ_mask = 0;   // the lanes whose sample lies in an empty cell
+                bool occ_skip = false;             // workgroup-uniform: nothing is evaluated
+                {
+                    const OccGrid* g = occ;
+                    asm volatile("" : "+s"(g));   // read again every iteration: nothing of the grid stays in registers across an evaluation
+                    const Ray ray = fresh_ray();
+                    float zo = zq[0];
+                    if (wave == 1) zo = zq[1];
+                    if (wave == 2) zo = zq[2];
+                    if (wave == 3) zo = zq[3];
+                    float px, py, pz;
+                    point_at(ray, zo, px, py, pz);
+                    const bool empty = occ_empty(g, px, py, pz);
+                    occ_mask = __ballot(empty);
+                    const int mine = __all(gone || 4 * it + wave >= Stot || empty);
+                    int* vote = reinterpret_cast<int*>(smem + SM::TOTAL);
+                    if (lane == 0) vote[(it & 1) * kWaves + wave] = mine;
+                    __syncthreads();
+                    const int* v = vote + (it & 1) * kWaves;
+                    occ_skip = __builtin_amdgcn_readfirstlane(v[0] & v[1] & v[2] & v[3]) != 0;
+                    if (!occ_skip) occ_evals += Stot - 4 * it < 4 ? Stot - 4 * it : 4;
+                }
+#endif
                 NWE_STAMP(const unsigned long long t0 = __builtin_amdgcn_s_memtime();)
+#ifdef NWE_ITEM_OCC
+                if (!occ_skip)
+#endif
                 if (!raw_in) NWE_PRIME_STREAM();
                 const Ray ray = fresh_ray();
                 const int s_own = 4 * it + wave;
@@ -198,10 +232,21 @@
 #pragma unroll
                     for (int k = 0; k < 4; ++k) zp[k] = zq[k];
                     read_raw(raw_in, rclamp * Stot + (own_valid ? s_own : Stot - 1), rr, rg, rb, rs);
+#ifdef NWE_ITEM_OCC
+                } else if (occ_skip) {
+                    // the vote's barrier has published the previous iteration's shaded samples
+                    if (it > 0) drain(it - 1);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) zp[k] = zq[k];
+                    rr = rg = rb = rs = 0.f;
+#endif
                 } else {
                     // its barrier also publishes the previous iteration's shaded samples; they are composited behind the fragment
                     // reads, whose latency that covers
                     NWE_EVAL_POINT(z_own, if (it > 0) drain(it - 1); _Pragma("unroll") for (int k = 0; k < 4; ++k) zp[k] = zq[k];);
+#ifdef NWE_ITEM_OCC
+                    if ((occ_mask >> lane) & 1) rr = rg = rb = rs = 0.f;   // all four channels (include/nwe.h)
+#endif
                 }
                 NWE_STAMP(const unsigned long long t3 = __builtin_amdgcn_s_memtime();)
                 if (own_valid) {
@@ -255,7 +300,32 @@
                         }
                     }
                 }
+#ifdef NWE_ITEM_OCC
+                // the vote on this iteration's sample of the workgroup's four packets
+                unsigned long long occ_mask = 0;   // the lanes whose sample lies in an empty cell
+                bool occ_skip = false;             // workgroup-uniform: nothing is evaluated
+                {
+                    const OccGrid* g = occ;
+                    asm volatile("" : "+s"(g));   // read again every iteration: nothing of the grid stays in registers across an evaluation
+                    const Ray ray = fresh_ray();
+                    float px, py, pz;
+                    point_at(ray, z_cur, px, py, pz);
+                    const bool empty = occ_empty(g, px, py, pz);
+                    occ_mask = __ballot(empty);
+                    const int mine = __all(gone || empty);
+                    const int n = pass == 0 ? s : ns + s;   // the iteration's number over both passes: no barrier separates them
+                    int* vote = reinterpret_cast<int*>(smem + SM::TOTAL);
+                    if (lane == 0) vote[(n & 1) * kWaves + wave] = mine;
+                    __syncthreads();
+                    const int* v = vote + (n & 1) * kWaves;
+                    occ_skip = __builtin_amdgcn_readfirstlane(v[0] & v[1] & v[2] & v[3]) != 0;
+                    if (!occ_skip) ++occ_evals;
+                }
+#endif
                 NWE_STAMP(const unsigned long long t0 = __builtin_amdgcn_s_memtime();)
+#ifdef NWE_ITEM_OCC
+                if (!occ_skip)
+#endif
                 if (!raw_in) NWE_PRIME_STREAM();
                 const Ray ray = fresh_ray();
                 if (s + 1 < Stot) {
@@ -265,8 +335,15 @@
                 float rr, rg, rb, rs;
                 if (raw_in) {
                     read_raw(raw_in, rclamp * Stot + s, rr, rg, rb, rs);
+#ifdef NWE_ITEM_OCC
+                } else if (occ_skip) {
+                    rr = rg = rb = rs = 0.f;
+#endif
                 } else {
                     NWE_EVAL_POINT(z_cur, );
+#ifdef NWE_ITEM_OCC
+                    if ((occ_mask >> lane) & 1) rr = rg = rb = rs = 0.f;   // all four channels (include/nwe.h)
+#endif
                 }
                 NWE_STAMP(const unsigned long long t3 = __builtin_amdgcn_s_memtime();)
                 const float4 shaded = Composite::shade(rr, rg, rb, rs, z_cur, z_next, s + 1 == Stot, ray.dnorm, noise ? noise[rclamp * Stot + s] : 0.f);
@@ -298,6 +375,12 @@
         // (separate passes at k = 1, where every ray runs its own coarse pass: nwe_abi.hip)
         if (producer) break;
     }
+#ifdef NWE_ITEM_OCC
+    {   // every wave of a sample-split workgroup holds the same 32 rays: wave 0 counts them
+        const unsigned long long mine = __popcll(__ballot(lane_live));
+        if (lane == 0 && mine && (!SPLIT || wave == 0)) atomicAdd(a.evals, mine * (unsigned long long)occ_evals);
+    }
+#endif
     if (flags && a.out.flags) atomicOr(a.out.flags, flags);
 #ifdef NWE_STAMPS
     if (a.stamps && lane == 0) {   // diagnostic build only: a buffer no other code reads

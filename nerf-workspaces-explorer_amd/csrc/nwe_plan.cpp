@@ -65,13 +65,14 @@ PassPlan plan_pass(const PassDesc& d, int cus) {
     return p;
 }
 
-// The kernels that serve a stage, or -1: the terminating and the sharing kernels are lean only, and exclude each other; a
+// The kernels that serve a stage, or -1: the terminating, the sharing and the occupancy kernels are lean only, and exclude one another; a
 // stage that carries a role without being lean (separate passes through the full kernels) is a single-pass render for the
 // producer and reads the coarse weights through the hook for the consumer.
 static int stage_variant(const CallDesc& c, int role, bool lean, int n_importance, bool w_in, int net) {
     const bool share = role != kShareOff && lean;
     int v = kVariantPlain;
-    if (c.term) v = lean && !share ? kVariantTerm : -1;
+    if (c.occ) v = lean && role == kShareOff && !c.term ? kVariantOcc : -1;
+    else if (c.term) v = lean && !share ? kVariantTerm : -1;
     else if (share) v = n_importance > 0 ? kVariantShare : -1;
     else if (role != kShareOff && (role == kShareProducer ? n_importance != 0 : !w_in)) v = -1;
     return v >= 0 && c.built[net][v] ? v : -1;
@@ -92,7 +93,8 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     p.full = p.separate && !p.share;
     p.coarse_launch = p.share || (p.full && !c.w_in);   // with the coarse-weights hook armed there is no coarse pass
     p.share_k = p.share ? c.share_k : 1;
-    p.need_evals = c.term;
+    p.occ = c.occ;
+    p.need_evals = c.term || c.occ;
     // the table between the two launches: [n_samples][n_rep] of the sharing kernels, [n_rays][n_samples] of the full ones, which
     // may be the caller's own
     if (p.share) p.table_elems = c.n_rep * c.n_samples;
@@ -117,10 +119,10 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     p.share_rays = p.coarse_launch ? k.n_rays : 0;
     if (!c.mfma) return p;
 
-    // Work queue: a call that is one fused plain MFMA kernel - plain kernels only: early termination, the shared coarse pass and
-    // separate passes keep their launches as they are - may deal its workgroups from the slot's counters, and its hybrid plan's
-    // second launch may backfill the first from the slot's own stream.
-    const bool plain_only = !p.separate && !p.share && !c.term;
+    // Work queue: a call that is one fused plain MFMA kernel - plain kernels only: early termination, the occupancy grid, the
+    // shared coarse pass and separate passes keep their launches as they are - may deal its workgroups from the slot's counters,
+    // and its hybrid plan's second launch may backfill the first from the slot's own stream.
+    const bool plain_only = !p.separate && !p.share && !c.term && !c.occ;
     const auto describe = [&](const StagePlan& s, bool stage_lean, bool w_in) {
         PassDesc d;
         d.n_rays = s.n_rays; d.n_samples = c.n_samples; d.n_importance = s.n_importance;

@@ -28,13 +28,16 @@ constexpr int kShareOff = 0, kShareProducer = 1, kShareConsumer = 2;
 // of one group of shapes (nwe_mfma_inst.hip); the dispatcher's table has one launcher per shape and variant.
 //   plain: eight kernels (three-pass / single-pass, packets / sample split, lean / full)
 //   term:  four, early termination (TERM; lean)        share: four, shared coarse pass (SHARE; lean)
+//   occ:   four, occupancy grid (render_mfma_occ_kernel; lean)
 //   tail:  two, render_mfma_tail_kernel (three-pass / single-pass, each holding both decompositions; lean)
-enum Variant { kVariantPlain, kVariantTerm, kVariantShare, kVariantTail, kVariants };
+// The first four are what a plan's `variant` may say (nwe_debug_plan reports the number); the tail kernel is taken through
+// PassPlan::tail.
+enum Variant { kVariantPlain, kVariantTerm, kVariantShare, kVariantOcc, kVariantTail, kVariants };
 
-// Whether a shape has a variant's kernels: the terminating and the sharing kernels exist for the product formulations,
-// kFormReference is a comparison path; every form has the plain kernels and, with them, the queue and the tail kernel.
+// Whether a shape has a variant's kernels: the terminating, the sharing and the occupancy kernels exist for the product
+// formulations, kFormReference is a comparison path; every form has the plain kernels and, with them, the queue and the tail kernel.
 constexpr bool variant_built(int variant, int form) {
-    return variant == kVariantTerm || variant == kVariantShare ? form != kFormReference : true;
+    return variant == kVariantTerm || variant == kVariantShare || variant == kVariantOcc ? form != kFormReference : true;
 }
 
 // The grid of a queued MFMA launch of n work items (nwe_debug_set_work_queue): n plus a quarter, rounded up to a multiple of 8.
@@ -54,7 +57,7 @@ struct PassDesc {
     int64_t n_rays = 0;
     int n_samples = 0, n_importance = 0;
     int role = kShareOff;          // costs the launch: a producer runs the coarse pass alone, a consumer the fine pass alone
-    int variant = kVariantPlain;   // the kernels the stage takes: plain, term or share; -1 = none can serve it (the plan is not ok)
+    int variant = kVariantPlain;   // the kernels the stage takes: plain, term, share or occ; -1 = none can serve it (the plan is not ok)
     bool lean = false;             // only rgb / depth / acc / flags of pinhole views, no hook, no table (is_lean without the stamps)
     bool stamps = false;           // a stamp buffer is set (nwe_debug_set_stamps): such a launch is not lean ...
     bool stamped_build = false;    // ... except, in a -DNWE_STAMPS build, for the tail path, whose kernel stamps all the same
@@ -103,6 +106,7 @@ struct CallDesc {
     int n_samples = 0, n_importance = 0;
     bool mfma = false;             // an MFMA precision (the fp32 launcher has no plan: its passes are not planned)
     bool term = false;             // nwe_set_early_termination > 0
+    bool occ = false;              // an occupancy grid is set (nwe_set_occupancy): excludes term, sharing and separate passes
     int share_k = 1;               // nwe_set_shared_coarse
     bool separate = false;         // nwe_set_separate_passes
     bool lean = false, stamps = false, stamped_build = false;   // as in PassDesc
@@ -131,7 +135,8 @@ struct CallPlan {
     bool coarse_launch = false;   // the call has a coarse stage (none with the coarse-weights hook armed under `full`)
     bool may_queue = false;       // a launch of the main stage is queued: the slot provides zeroed counters and, with the
     bool need_side = false;       //   backfill on, the side streams exist
-    bool need_evals = false;      // early termination: the slot provides a zeroed evaluation counter
+    bool need_evals = false;      // early termination, occupancy grid: the slot provides a zeroed evaluation counter
+    bool occ = false;             // the main stage reads the context's occupancy grid (both kernels' occupancy instantiations)
     int share_k = 1;              // the k in both stages' share word
     int64_t table_elems = 0;      // the slot's weight table must hold this many floats (0: none, or the caller's own table serves)
     bool coarse_flags = false;    // the coarse launch's flags go through a word of the slot's (masked into the caller's)

@@ -51,8 +51,14 @@ class NeRFReplicaInferenceHandler:
 
     def __init__(self, office_name: str, ckpt_path: str, device: int = 0, precision: str = "auto",
                  devices: Optional[Sequence[int]] = None, early_termination: float = 0.0, shared_coarse: int = 1,
-                 separate_passes: Optional[bool] = None) -> None:
-        """``early_termination`` (or the environment variable NWE_EARLY_TERMINATION, for the same two-argument callers):
+                 separate_passes: Optional[bool] = None, occupancy: Optional[Mapping[str, object]] = None) -> None:
+        """``occupancy``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128), "probes" (2),
+        "dilate" (1), "threshold" (0.0): initialize_models() builds an occupancy grid over the box from the networks it has
+        uploaded (Renderer.build_occupancy) and frames skip the samples in cells it marks empty.  The environment variable
+        NWE_OCCUPANCY = "res[,probes[,dilate]]" overrides these three over the box given here, for the same two-argument
+        callers; without a box there is no grid.  While a grid is set ``_render_rays`` raises what the ABI says; it is
+        refused together with ``early_termination > 0``, ``shared_coarse > 1`` and ``separate_passes``.
+        ``early_termination`` (or the environment variable NWE_EARLY_TERMINATION, for the same two-argument callers):
         the minimum transmittance of Renderer.set_early_termination, applied in initialize_models(); 0 = off.  While it is on,
         frames (render, render_batch, render_coordinates) are terminated and ``_render_rays`` raises what the ABI says.
         ``shared_coarse`` (or the environment variable NWE_SHARED_COARSE): the block edge k of Renderer.set_shared_coarse,
@@ -93,6 +99,21 @@ class NeRFReplicaInferenceHandler:
         if separate_passes and self._early_termination > 0.0:
             raise ValueError("separate_passes and early_termination > 0 are not supported together")
         self._separate_passes = separate_passes
+        self._occupancy = None
+        if occupancy is not None:
+            unknown = set(occupancy) - {"lo", "hi", "resolution", "probes", "dilate", "threshold"}
+            if unknown or "lo" not in occupancy or "hi" not in occupancy:
+                raise ValueError(f"occupancy needs 'lo' and 'hi' and may hold resolution, probes, dilate, threshold; got {sorted(occupancy)}")
+            grid = {"resolution": 128, "probes": 2, "dilate": 1, "threshold": 0.0}
+            grid.update(occupancy)
+            env = [v.strip() for v in os.environ.get("NWE_OCCUPANCY", "").split(",") if v.strip() != ""]
+            if len(env) > 3:
+                raise ValueError("NWE_OCCUPANCY must be res[,probes[,dilate]]")
+            for key, value in zip(("resolution", "probes", "dilate"), env):
+                grid[key] = int(value)
+            if self._early_termination > 0.0 or self._shared_coarse > 1 or self._separate_passes:
+                raise ValueError("an occupancy grid is not supported together with early_termination > 0, shared_coarse > 1 or separate_passes")
+            self._occupancy = grid
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -180,6 +201,8 @@ class NeRFReplicaInferenceHandler:
                 shapes = " / ".join(str(self._renderer.shapes.get(w)) for w in nets)
                 print(f"[nwe] network shape {shapes} has no MFMA instantiation: rendering with the "
                       f"fp32 vector-ALU kernel (same results, ~25x slower){hint}")
+        if self._occupancy is not None:     # behind the networks (set_network clears a grid) and the precision
+            self.build_occupancy(**self._occupancy)
 
     def _need_renderer(self) -> Renderer:
         if self._renderer is None:
@@ -336,6 +359,20 @@ class NeRFReplicaInferenceHandler:
             pts = self.grid_centres(lo, hi, res3, start, count, device=r.device)
             out[start:start + count] = r.query_points(pts, None, which=w, precision=precision or auto, outputs=("sigma",))["sigma"]
         return out.reshape(res3)
+
+    def build_occupancy(self, lo: Sequence[float], hi: Sequence[float], resolution=128, probes: int = 2, threshold: float = 0.0,
+                        dilate: int = 1, precision: Optional[str] = None) -> None:
+        """Builds an occupancy grid over the box lo..hi from the uploaded networks (Renderer.build_occupancy); frames then skip
+        the samples in cells it marks empty, and ``_render_rays`` raises what the ABI says until clear_occupancy()."""
+        self._need_renderer().build_occupancy(lo, hi, resolution, probes, threshold, dilate, precision or self._precision)
+
+    def clear_occupancy(self) -> None:
+        self._need_renderer().clear_occupancy()
+
+    @property
+    def occupancy(self):
+        """The renderer's grid (Renderer.occupancy), None without one."""
+        return self._need_renderer().occupancy
 
     # ------------------------------------------------------------------------------------------------
     @property

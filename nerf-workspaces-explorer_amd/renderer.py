@@ -375,6 +375,93 @@ class Renderer:
     def separate_passes(self) -> bool:
         return int(self._lib.nwe_get_separate_passes(self._ctx)) == 1
 
+    # -- occupancy grid ---------------------------------------------------------------------------
+    @staticmethod
+    def _occupancy_box(lo, hi, resolution):
+        res3 = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(r) for r in resolution)
+        if len(res3) != 3 or len(lo) != 3 or len(hi) != 3:
+            raise ValueError("occupancy needs lo, hi of three coordinates and a resolution of one or three ints")
+        return (C.c_float * 3)(*[float(v) for v in lo]), (C.c_float * 3)(*[float(v) for v in hi]), (C.c_int * 3)(*res3), res3
+
+    @staticmethod
+    def pack_occupancy(bits) -> np.ndarray:
+        """uint32 words of a bool [rx, ry, rz] array (numpy or torch): bit (ix * ry + iy) * rz + iz in word >> 5 at bit & 31."""
+        if isinstance(bits, torch.Tensor):
+            bits = bits.detach().cpu().numpy()
+        flat = np.ascontiguousarray(bits).astype(bool).reshape(-1)
+        padded = np.zeros((flat.size + 31) // 32 * 32, dtype=np.uint8)
+        padded[:flat.size] = flat
+        shifted = padded.reshape(-1, 32).astype(np.uint32) << np.arange(32, dtype=np.uint32)[None, :]
+        return np.ascontiguousarray(np.bitwise_or.reduce(shifted, axis=1), dtype=np.uint32)
+
+    @staticmethod
+    def unpack_occupancy(words: np.ndarray, resolution) -> np.ndarray:
+        """The bool [rx, ry, rz] array of packed words (pack_occupancy's inverse)."""
+        rx, ry, rz = (int(r) for r in resolution)
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        flat = ((w[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).astype(bool).reshape(-1)
+        return flat[:rx * ry * rz].reshape(rx, ry, rz)
+
+    def set_occupancy(self, bits, lo: Sequence[float], hi: Sequence[float], resolution) -> None:
+        """Opt-in occupancy grid (include/nwe.h): the box lo..hi in world coordinates cut into resolution = (rx, ry, rz) cells,
+        ``bits`` a bool [rx, ry, rz] array (numpy or torch; True = occupied) or the packed uint32 words (pack_occupancy).  A
+        sample in a cell marked empty counts as raw = 0 in both passes and a workgroup whose rays are all in empty cells at
+        an iteration does not evaluate it; outside the box everything is evaluated.  ``render`` honours it for rgb / depth /
+        acc; every other call raises NotImplementedError while a grid is set, and so does every call while early
+        termination, a shared coarse pass or separate passes are on as well.  ``set_network`` clears the grid."""
+        lo3, hi3, res3, res = self._occupancy_box(lo, hi, resolution)
+        n_words = (res[0] * res[1] * res[2] + 31) // 32 if min(res) > 0 else 0
+        if isinstance(bits, torch.Tensor) and bits.dtype != torch.bool:
+            bits = bits.detach().cpu().numpy()
+        arr = bits if isinstance(bits, torch.Tensor) else np.asarray(bits)
+        if arr.dtype in (np.uint32, np.int32) and arr.ndim == 1:
+            words = np.ascontiguousarray(arr).view(np.uint32)
+        else:
+            if tuple(arr.shape) != res:
+                raise ValueError(f"occupancy bits must be a bool array of shape {res} or packed uint32 words, got {tuple(arr.shape)}")
+            words = self.pack_occupancy(arr)
+        if min(res) > 0 and words.size != n_words:
+            raise ValueError(f"occupancy needs {n_words} words for resolution {res}, got {words.size}")
+        self._check(self._lib.nwe_set_occupancy(self._ctx, lo3, hi3, res3, words.ctypes.data if words.size else None, 0), "nwe_set_occupancy")
+
+    def build_occupancy(self, lo: Sequence[float], hi: Sequence[float], resolution, probes: int = 2, threshold: float = 0.0,
+                        dilate: int = 1, precision: str = "f16x3") -> None:
+        """Builds the grid from the networks that are set (nwe_build_occupancy): a cell is occupied if sigma_raw of any set
+        network at any of its probes^3 lattice points is > threshold or not finite, then ``dilate`` steps of 3 x 3 x 3
+        dilation.  An approximation unless the networks have no density in the cells it marks empty."""
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"unknown precision {precision!r}")
+        lo3, hi3, res3, _ = self._occupancy_box(lo, hi, resolution)
+        stream = None
+        if self.device is not None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.nwe_build_occupancy(self._ctx, lo3, hi3, res3, int(probes), float(threshold), int(dilate),
+                                                  _lib.PRECISIONS[precision], stream), "nwe_build_occupancy")
+
+    def clear_occupancy(self) -> None:
+        self._check(self._lib.nwe_clear_occupancy(self._ctx), "nwe_clear_occupancy")
+
+    @property
+    def occupancy(self) -> Optional[Dict[str, object]]:
+        """None, or the grid: "lo", "hi", "resolution", "inv" (the fp32 factors the kernels multiply by), "occupied_cells" and
+        "occupied" (their share of the cells)."""
+        lo, hi, res, inv, occ = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_int * 3)(), (C.c_float * 3)(), C.c_int64(0)
+        if self._lib.nwe_get_occupancy(self._ctx, lo, hi, res, inv, C.byref(occ)) != _lib.NWE_OK:
+            return None
+        cells = res[0] * res[1] * res[2]
+        return {"lo": tuple(lo), "hi": tuple(hi), "resolution": tuple(res), "inv": np.array(list(inv), dtype=np.float32),
+                "occupied_cells": int(occ.value), "occupied": occ.value / cells}
+
+    def occupancy_bits(self) -> Optional[np.ndarray]:
+        """The grid as a bool [rx, ry, rz] array, None without one."""
+        g = self.occupancy
+        if g is None:
+            return None
+        rx, ry, rz = g["resolution"]
+        words = np.empty((rx * ry * rz + 31) // 32, dtype=np.uint32)
+        self._check(self._lib.nwe_occupancy_copy(self._ctx, words.ctypes.data, words.size), "nwe_occupancy_copy")
+        return self.unpack_occupancy(words, (rx, ry, rz))
+
     def last_coarse_launch(self) -> Optional[Tuple[float, int]]:
         """(ms, rays) of the coarse (producer) launch of the last render, None if it had none (k = 1 without separate passes,
         n_importance == 0)."""
@@ -574,6 +661,23 @@ class TiledRenderer:
     def set_separate_passes(self, on: bool) -> None:
         for p in self.parts:
             p.set_separate_passes(on)
+
+    def set_occupancy(self, bits, lo: Sequence[float], hi: Sequence[float], resolution) -> None:
+        for p in self.parts:
+            p.set_occupancy(bits, lo, hi, resolution)
+
+    def build_occupancy(self, lo: Sequence[float], hi: Sequence[float], resolution, probes: int = 2, threshold: float = 0.0,
+                        dilate: int = 1, precision: str = "f16x3") -> None:
+        """Built once, on the first part, and copied to the others: every tile reads the same bits."""
+        first = self.parts[0]
+        first.build_occupancy(lo, hi, resolution, probes, threshold, dilate, precision)
+        g = first.occupancy
+        for p in self.parts[1:]:
+            p.set_occupancy(first.occupancy_bits(), g["lo"], g["hi"], g["resolution"])
+
+    def clear_occupancy(self) -> None:
+        for p in self.parts:
+            p.clear_occupancy()
 
     def render(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
                rows: Optional[Tuple[int, int]] = None, precision: str = "f16x3",
