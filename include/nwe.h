@@ -488,11 +488,81 @@ int nwe_occupancy_copy(const nwe_ctx *ctx, uint32_t *host_words, int64_t n_words
 int nwe_build_occupancy(nwe_ctx *ctx, const float *lo, const float *hi, const int *res, int probes, float threshold, int dilate,
                         int precision, void *stream);
 
+/* Baked coarse pass, opt-in: a context may hold ONE coarse density grid; none (the default) changes nothing.  A grid is an
+ * axis-aligned box lo[3] < hi[3] in world coordinates, a resolution res = (rx, ry, rz), each axis 1..512, and rx * ry * rz fp32
+ * values of sigma_raw (before the ReLU) at the cell centres, in the layout of a [rx, ry, rz] array, z fastest - what
+ * handler.density_grid returns.
+ * Why: a lean frame reads nothing of its coarse pass but the weights that feed sample_pdf, and the quantity behind them,
+ * sigma_coarse(x), depends on the position only.  While a grid is set, a lean call with n_importance > 0 - nwe_render or
+ * nwe_render_tiled requesting nothing but rgb / depth / acc / flags of pinhole views - does not run the coarse network.
+ * The rule, for each ray and each coarse sample i:
+ *   - the depth z_i and the fp32 point p = o + d * z_i are the ones the kernels encode (near * (1 - t) + far * t, handler.py:218;
+ *     multiply then add, handler.py:223), before the division by 10;
+ *   - its grid coordinate is g_c = (p_c - lo_c) * inv_c - 0.5f per axis: an fp32 subtraction, multiplication and subtraction, each
+ *     rounded on its own, with inv_c = (float)r_c / (hi_c - lo_c) formed once on the host in fp32 (nwe_get_coarse_grid reports it);
+ *   - OUTSIDE the box the sample has sigma_raw = 0: if any p_c is not finite, or g_c < -0.5f or g_c > r_c - 0.5f on any axis.
+ *     Nothing is known there; the weight is 0 and only sample_pdf's 1e-5 floor remains;
+ *   - inside, i0 = floorf(g_c) and f_c = g_c - i0 (exact); the two indices i0 and i0 + 1 are clamped to 0 .. r_c - 1, so within half
+ *     a cell of a face the value is the face cell's; the eight values are interpolated along z, then y, then x, each
+ *     interpolation a + (b - a) * f in three separately rounded fp32 operations, no FMA: a numpy float32 restatement gives the
+ *     same bits (tests/coarse_grid.py).  A non-finite grid value propagates;
+ *   - the ray's coarse weights are raw2outputs' fourth return value (nerf/models/model_utils.py:49-100) for
+ *     raw = (0, 0, 0, sigma_raw_i), computed with the device code the render kernels composite with: for equal sigma they are,
+ *     bit for bit, the weights a coarse pass produces;
+ *   - everything behind that is the ordinary call: sample_pdf on weights[1:-1], the merge, the fine network, the compositing.
+ * So a ray's outputs depend on the ray and the grid only; frames stay bit-identical across the work decompositions, the hybrid
+ * plan, row tiles, pose batches and the tiles of nwe_render_tiled; the coarse flag bits are never raised.  With
+ * n_importance == 0 the only pass is the output and the call renders exactly as without a grid.
+ * It is an approximation whose size is the trilinear interpolation error of the coarse density at the grid's resolution.
+ * A call is two launches on the caller's stream: the producer (one thread per ray; it fills the slot's weight table
+ * [n_samples][n_rays] from the grid) and behind it the consumer of the shared coarse pass at k = 1 with the FINE network's
+ * kernels.  The coarse network's shape is therefore not constrained; under the MFMA precisions the fine network's shape needs
+ * its sharing kernels.  nwe_debug_plan reports the coarse stage as active, role 1 (producer), n_rays = the call's rays,
+ * n_launches = 1 and variant = plan = -1: it is no MFMA launch group and has neither; the rest of the stage is zero.
+ * nwe_last_ray_evaluations: out[1] stays n_rays * (2 n_samples + n_importance), out[0] = n_rays * (n_samples + n_importance).
+ * nwe_last_coarse_launch: the producer's time and the call's rays; nwe_last_kernel_ms spans both launches.
+ * While a grid is set every other call is refused with NWE_ERR_UNSUPPORTED and a message that names the setting, behind every
+ * refusal the call has without it and whatever n_importance is: any output beyond rgb / depth / acc / flags, all of
+ * nwe_render_rays with its hooks and training tables, under the MFMA precisions (n_importance > 0) a fine network packed unfolded
+ * (nwe_debug_set_fold(0)) or one whose sharing kernels were not built (NWE_PREC_F32 renders both), a stamped launch, and every
+ * call while early termination (min_transmittance > 0), a shared coarse pass (k > 1), separate passes or an occupancy grid is on
+ * as well: these combinations are not built.  nwe_query_points ignores the grid.
+ * nwe_set_network / nwe_set_network_no_view_dirs with which == NWE_NET_COARSE CLEAR the grid - it describes that network; setting
+ * the fine network leaves it, and so does a refused call.  The grid calls below wait for this context's launches in flight,
+ * like nwe_set_sampling.
+ *   nwe_set_coarse_grid      copies the values (from the host or - on_device != 0 - the context's device) into a buffer the
+ *                            context owns; a host-only context keeps them on the host.  Refused by name (NWE_ERR_INVALID): null
+ *                            pointers, a box that is not finite or not lo < hi on every axis (or so thin that inv is not finite),
+ *                            a resolution outside the domain.
+ *   nwe_clear_coarse_grid    no grid.
+ *   nwe_get_coarse_grid      the grid's box, resolution and the fp32 inv the kernel multiplies by; any pointer may be null.
+ *                            NWE_ERR_STATE (and nothing written) when no grid is set.
+ *   nwe_coarse_grid_copy     the values, n_values = rx * ry * rz, to the host.
+ *   nwe_bake_coarse_grid     sigma_raw of the COARSE network at the cell centres, through the sigma-only path of
+ *                            nwe_query_points in `precision`, in chunks, into the context's grid.  The centres are
+ *                            ((float)i + 0.5f) * step + lo with step = (float)(((double)hi - (double)lo) / r): the probes = 1
+ *                            arithmetic of nwe_build_occupancy and handler.grid_centres.  Synchronous: queued on `stream` and
+ *                            waited for.  Refused: a host-only context, the coarse network not set (NWE_ERR_STATE); the box and
+ *                            resolution as above, an unknown precision (NWE_ERR_INVALID); an MFMA precision for a shape without
+ *                            a query kernel (NWE_ERR_UNSUPPORTED, the query's own message).
+ *   nwe_coarse_grid_weights  test hook: the producer alone for the rays of nwe_render with these camera arguments: DEVICE
+ *                            sigma_out [n_rays, n_samples] (the grid's sigma_raw per sample) and weights_out [n_rays, n_samples]
+ *                            (the layout of weights_coarse); either may be NULL.  Needs a grid and nwe_set_sampling, no network.
+ *                            Asynchronous on `stream`, with events of its own like nwe_create_rays. */
+int nwe_set_coarse_grid(nwe_ctx *ctx, const float *lo, const float *hi, const int *res, const float *sigma, int on_device);
+int nwe_clear_coarse_grid(nwe_ctx *ctx);
+int nwe_get_coarse_grid(const nwe_ctx *ctx, float *lo, float *hi, int *res, float *inv);
+int nwe_coarse_grid_copy(nwe_ctx *ctx, float *host_values, int64_t n_values);
+int nwe_bake_coarse_grid(nwe_ctx *ctx, const float *lo, const float *hi, const int *res, int precision, void *stream);
+int nwe_coarse_grid_weights(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy,
+                            float near, float far, int row_begin, int row_end, float *sigma_out_dev, float *weights_out_dev,
+                            void *stream);
+
 /* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
  * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1 without separate
  * passes, n_importance == 0, or a call armed with nwe_debug_set_coarse_weights).  Under separate passes with k = 1 it is the
- * coarse launch and *rays the call's rays.  nwe_last_kernel_ms spans both launches, nwe_last_launch_parts describes the
- * consumer's. */
+ * coarse launch and *rays the call's rays; under a baked coarse pass (nwe_set_coarse_grid) the grid producer and the call's rays.
+ * nwe_last_kernel_ms spans both launches, nwe_last_launch_parts describes the consumer's. */
 int nwe_last_coarse_launch(nwe_ctx *ctx, float *ms, int64_t *rays);
 
 /* Ray evaluations of the most recent render launch of this context (the launch nwe_last_kernel_ms describes, under the same
@@ -593,8 +663,8 @@ typedef struct nwe_plan_stage {
     int64_t n_rays;       /* the stage's rays: the producer's are the representatives */
     int32_t n_importance;
     int32_t net;          /* the network (0 coarse, 1 fine) in both descriptor slots, -1: (coarse, fine) */
-    int32_t variant;      /* the kernels: 0 plain, 1 terminating, 2 sharing, 3 occupancy grid */
-    int32_t plan;         /* nwe_debug_last_plan: 0 packets, 1 sample split, 2 packets + split rest */
+    int32_t variant;      /* the kernels: 0 plain, 1 terminating, 2 sharing, 3 occupancy grid; -1: the grid producer of a baked coarse pass */
+    int32_t plan;         /* nwe_debug_last_plan: 0 packets, 1 sample split, 2 packets + split rest; -1: that producer, which has none */
     int32_t n_launches;   /* 1, or 2 under plan 2 */
     int32_t fork;         /* 0 the second launch follows the first on the caller's stream; it goes to the side stream, which forks
                              1 in front of the first launch (backfill), 2 behind it (tail path) */

@@ -29,7 +29,9 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_debug_get_work_queue_tail", "nwe_debug_last_tail", "nwe_debug_last_tail_rest",
            "nwe_query_points", "nwe_last_query_ms", "nwe_debug_set_query_steps",
            "nwe_packed_colour_finite", "nwe_debug_set_colour_skip", "nwe_debug_get_colour_skip", "nwe_debug_plan",
-           "nwe_set_occupancy", "nwe_clear_occupancy", "nwe_get_occupancy", "nwe_occupancy_copy", "nwe_build_occupancy")
+           "nwe_set_occupancy", "nwe_clear_occupancy", "nwe_get_occupancy", "nwe_occupancy_copy", "nwe_build_occupancy",
+           "nwe_set_coarse_grid", "nwe_clear_coarse_grid", "nwe_get_coarse_grid", "nwe_coarse_grid_copy", "nwe_bake_coarse_grid",
+           "nwe_coarse_grid_weights")
 
 
 class Outputs(C.Structure):
@@ -148,6 +150,12 @@ def load() -> C.CDLL:
         "nwe_get_occupancy": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), C.POINTER(F), C.POINTER(I64)]),
         "nwe_occupancy_copy": (I, [P, P, I64]),
         "nwe_build_occupancy": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), I, F, I, I, P]),
+        "nwe_set_coarse_grid": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), P, I]),
+        "nwe_clear_coarse_grid": (I, [P]),
+        "nwe_get_coarse_grid": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), C.POINTER(F)]),
+        "nwe_coarse_grid_copy": (I, [P, P, I64]),
+        "nwe_bake_coarse_grid": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), I, P]),
+        "nwe_coarse_grid_weights": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

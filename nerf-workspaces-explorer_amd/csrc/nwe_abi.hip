@@ -105,6 +105,16 @@ struct Occupancy {
     std::vector<uint32_t> bits;
 };
 
+// The coarse density grid of a context (nwe_set_coarse_grid, nwe_bake_coarse_grid).  A device context keeps the values on its
+// device only (d_cgrid: up to 512^3 floats), a host-only context in `host`.
+struct CoarseGridState {
+    bool set = false;
+    float lo[3] = {}, hi[3] = {}, inv[3] = {};
+    int res[3] = {};
+    int64_t cells = 0;
+    std::vector<float> host;
+};
+
 thread_local std::string g_create_error;
 
 }  // namespace
@@ -148,6 +158,8 @@ struct nwe_ctx {
     DevBuf<uint32_t> d_occ_bits, d_occ_tmp;   // the grid's words on the device; nwe_build_occupancy's second buffer for the dilation
     DevBuf<OccGrid> d_occ;                    // the descriptor RenderArgs::occ points to
     DevBuf<float> d_occ_scratch;              // nwe_build_occupancy: probe points and their sigma, one chunk
+    CoarseGridState cgrid;    // nwe_set_coarse_grid / nwe_bake_coarse_grid: cgrid.set = a grid is set
+    DevBuf<float> d_cgrid;                    // its values on the device; nwe_bake_coarse_grid's cell centres go through d_occ_scratch
     int decomposition = -1;   // nwe_debug_set_decomposition
     int work_queue = -1;      // nwe_debug_set_work_queue; a new context takes NWE_WORK_QUEUE=0|1 from the environment
     bool backfill = true;     // the hybrid plan's second launch on the slot's own stream; NWE_WORK_QUEUE_BACKFILL=0: behind the first
@@ -300,7 +312,7 @@ RenderArgs camera_args(const Camera& m, const float* poses_dev) {
 // The refusals early termination and the shared coarse pass share: both render lean pinhole calls only, through kernels of
 // their own.  `on` / `off` open and close the mode's texts, `no_rays` is its word for nwe_render_rays, `kind` names its kernels.
 int check_lean_mode(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole, const std::string& on, const char* off,
-                    const char* no_rays, const std::string& kind, int variant) {
+                    const char* no_rays, const std::string& kind, int variant, bool fine_only = false) {
     // what only a ray's own full passes can give is refused by name rather than changed in silence
     if (!pinhole) return fail(ctx, NWE_ERR_UNSUPPORTED, on + no_rays + off);
     nwe_outputs rest = *out;
@@ -309,7 +321,8 @@ int check_lean_mode(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pi
     if (std::memcmp(&rest, &none, sizeof(none)) != 0)
         return fail(ctx, NWE_ERR_UNSUPPORTED, on + "only rgb / depth / acc / flags can be requested" + off);
     if (precision == NWE_PREC_F32) return NWE_OK;
-    for (int i = 0; i < (ctx->ni > 0 ? 2 : 1); ++i) {
+    // fine_only (baked coarse pass): the coarse network runs no kernel, and with n_importance == 0 the call is the ordinary one
+    for (int i = fine_only ? 1 : 0; i < (ctx->ni > 0 ? 2 : 1); ++i) {
         const NetState& n = ctx->net[i];
         if (mfma_variant_built(n.D, n.W, n.skip, n.form, variant)) continue;
         return fail(ctx, NWE_ERR_UNSUPPORTED,
@@ -346,7 +359,9 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhol
             return fail(ctx, NWE_ERR_UNSUPPORTED, "feat_map (endpoint_feat) is computed by the NWE_PREC_F32 kernel only");
     }
     if (precision != NWE_PREC_F32) {
-        if (!ctx->net[0].mfma_ok || (ctx->ni > 0 && !ctx->net[1].mfma_ok))
+        // a baked coarse pass (nwe_set_coarse_grid) runs no kernel of the coarse network: its shape is not constrained
+        const bool coarse_runs = !(ctx->cgrid.set && ctx->ni > 0);
+        if ((coarse_runs && !ctx->net[0].mfma_ok) || (ctx->ni > 0 && !ctx->net[1].mfma_ok))
             return fail(ctx, NWE_ERR_UNSUPPORTED,
                         "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
         if (ctx->ns > mfma_max_samples())
@@ -390,6 +405,25 @@ int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhol
                             "occupancy", kVariantOcc));
         if (ctx->stamps) return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "a stamped launch (nwe_debug_set_stamps) has no occupancy kernel" + grid_off);
     }
+    if (ctx->cgrid.set) {
+        const CoarseGridState& g = ctx->cgrid;
+        const std::string grid = "a coarse density grid is set (nwe_set_coarse_grid, " + std::to_string(g.res[0]) + " x " + std::to_string(g.res[1]) + " x " +
+                                 std::to_string(g.res[2]) + "): ";
+        const char* grid_off = "; call nwe_clear_coarse_grid for this call";
+        if (ctx->min_trans > 0.f)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with early termination (nwe_set_early_termination, min_transmittance = " +
+                                                      std::to_string(ctx->min_trans) + "); switch one of them off");
+        if (ctx->share_k > 1)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with the shared coarse pass (nwe_set_shared_coarse, k = " +
+                                                      std::to_string(ctx->share_k) + "); switch one of them off");
+        if (ctx->separate)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with separate passes (nwe_set_separate_passes); switch one of them off");
+        if (ctx->occ.set)
+            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with an occupancy grid (nwe_set_occupancy); clear one of them");
+        TRY(check_lean_mode(ctx, out, precision, pinhole, grid, grid_off, "nwe_render_rays, its hooks and its training tables do not read the grid",
+                            "sharing", kVariantShare, true));
+        if (ctx->stamps) return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "a stamped launch (nwe_debug_set_stamps) has no sharing kernel" + grid_off);
+    }
     return NWE_OK;
 }
 
@@ -421,6 +455,7 @@ CallDesc describe_call(const nwe_ctx* ctx, const RenderArgs& a, int precision) {
     d.term = a.min_trans > 0.f;
     d.occ = ctx->occ.set;
     d.share_k = ctx->share_k; d.separate = ctx->separate != 0;
+    d.baked = ctx->cgrid.set;   // check_ready has let nothing but lean pinhole calls through
     RenderArgs unstamped = a;
     unstamped.stamps = nullptr;
     d.lean = mfma_is_lean(unstamped); d.stamps = a.stamps != nullptr; d.stamped_build = kStampedBuild;
@@ -493,6 +528,14 @@ RenderArgs stage_args(const CallPlan& p, const RenderSlot& slot, RenderArgs& a) 
     return prod;
 }
 
+// The context's coarse density grid as the producer kernel takes it.
+CoarseGrid coarse_grid_args(const nwe_ctx* ctx) {
+    CoarseGrid g = {};
+    for (int i = 0; i < 3; ++i) { g.lo[i] = ctx->cgrid.lo[i]; g.inv[i] = ctx->cgrid.inv[i]; g.res[i] = ctx->cgrid.res[i]; }
+    g.sigma = ctx->d_cgrid.get();
+    return g;
+}
+
 // A render launch on the ring slot prepare_slot() made ready (ctx->slots[ctx->next_slot]): describe the call, plan it, carry
 // the plan out.  The ring moves on here, once the launch has been recorded.
 int launch(nwe_ctx* ctx, RenderSlot& slot, RenderArgs& a, int precision, hipStream_t stream) {
@@ -529,7 +572,11 @@ int launch(nwe_ctx* ctx, RenderSlot& slot, RenderArgs& a, int precision, hipStre
         slot.evals_full = p.evals_full; slot.evals_run = p.evals_run; slot.share_rays = p.share_rays;
         const char* shapes_differ = "coarse and fine networks must have the same shape for the MFMA kernel";
         LaunchReport report;
-        if (p.coarse.active) {
+        if (p.baked) {   // the coarse stage is the grid producer: the table from the context's grid, on the caller's stream
+            launch_coarse_grid_weights(a, coarse_grid_args(ctx), slot.share_w.get(), nullptr, nullptr, stream);
+            HIPCHK(ctx, hipEventRecord(slot.ev_share, stream));
+            slot.has_share = true;
+        } else if (p.coarse.active) {
             if (!run(p.coarse, prod, LaunchResources{}, &report)) return fail(ctx, NWE_ERR_UNSUPPORTED, shapes_differ);
             if (p.full && prod.out.flags)
                 hipLaunchKernelGGL(or_masked_flags_kernel, dim3(1), dim3(1), 0, stream, prod.out.flags,
@@ -713,6 +760,7 @@ int set_network(nwe_ctx* c, int which, const NetShape& shape, const float* const
     }
     n.set = true;
     c->occ.set = false;   // a grid describes the networks it was made for (include/nwe.h); the wait above covers its readers
+    if (which == NWE_NET_COARSE) c->cgrid = CoarseGridState{};   // the coarse density grid describes the coarse network
     return NWE_OK;
 }
 
@@ -781,6 +829,39 @@ int install_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* r
     g.set = true;
     c->occ = std::move(g);
     return NWE_OK;
+}
+
+// ---- coarse density grid (nwe_set_coarse_grid, nwe_bake_coarse_grid) ----
+
+// The refusals nwe_set_coarse_grid and nwe_bake_coarse_grid share, by name: null pointers, a box that is not finite or not
+// lo < hi on every axis (or so thin that the fp32 inv is not finite), a resolution outside 1 .. 512 per axis.
+int check_coarse_grid_box(nwe_ctx* c, const float* lo, const float* hi, const int* res) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!lo || !hi || !res) return fail(c, NWE_ERR_INVALID, "coarse grid: null lo, hi or resolution");
+    for (int i = 0; i < 3; ++i) {
+        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !std::isfinite(hi[i] - lo[i]))
+            return fail(c, NWE_ERR_INVALID, "coarse grid: the box must be finite");
+        if (!(lo[i] < hi[i])) return fail(c, NWE_ERR_INVALID, "coarse grid: the box must have lo < hi on every axis");
+    }
+    for (int i = 0; i < 3; ++i)
+        if (res[i] < 1 || res[i] > 512) return fail(c, NWE_ERR_INVALID, "coarse grid: the resolution must be in 1..512 on every axis");
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite((float)res[i] / (hi[i] - lo[i])))
+            return fail(c, NWE_ERR_INVALID, "coarse grid: the box must be finite (resolution / (hi - lo) is not, in fp32)");
+    return NWE_OK;
+}
+
+// The box, the resolution and inv of a new grid; the values are in place (d_cgrid or g.host) when this is called.
+void install_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, std::vector<float>&& host) {
+    CoarseGridState g;
+    g.cells = (int64_t)res[0] * res[1] * res[2];
+    for (int i = 0; i < 3; ++i) {
+        g.lo[i] = lo[i]; g.hi[i] = hi[i]; g.res[i] = res[i];
+        g.inv[i] = (float)res[i] / (hi[i] - lo[i]);   // fp32, once: what the kernel multiplies by (nwe_get_coarse_grid reports it)
+    }
+    g.host = std::move(host);
+    g.set = true;
+    c->cgrid = std::move(g);
 }
 
 }  // namespace
@@ -1125,6 +1206,10 @@ int nwe_debug_plan(nwe_ctx* c, int n_poses, int H, int W, int row_begin, int row
         nwe_plan_stage& r = i == 0 ? report->coarse : report->main;
         if (!s.active) continue;
         r.active = 1; r.role = s.role; r.n_rays = s.n_rays; r.n_importance = s.n_importance; r.net = s.net;
+        if (p.baked && i == 0) {   // the grid producer: one launch that is no MFMA launch group, so it has no variant and no plan
+            r.variant = r.plan = -1; r.n_launches = 1;
+            continue;
+        }
         if (precision == NWE_PREC_F32) continue;   // the fp32 launcher has no plan
         // what launch_render_mfma refuses: no kernel for the stage, or one fused kernel over two networks of different shapes
         const NetState &nc = c->net[0], &nf = c->net[1];
@@ -1294,6 +1379,119 @@ int nwe_build_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int*
     HIPCHK(c, hipMemcpyAsync(host.data(), buf[cur], (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIPCHK(c, hipStreamSynchronize(stream));
     return install_occupancy(c, lo, hi, res, std::move(host));
+}
+
+int nwe_set_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, const float* sigma, int on_device) {
+    TRY(check_coarse_grid_box(c, lo, hi, res));
+    if (!sigma) return fail(c, NWE_ERR_INVALID, "coarse grid: null sigma");
+    if (on_device && c->host_only) return fail(c, NWE_ERR_INVALID, "coarse grid: a host-only context takes its values from the host");
+    const size_t cells = (size_t)res[0] * res[1] * res[2];
+    if (c->host_only) {
+        install_coarse_grid(c, lo, hi, res, std::vector<float>(sigma, sigma + cells));
+        return NWE_OK;
+    }
+    ON_DEVICE(c);
+    TRY(wait_for_launches(c));   // a queued launch still reads the old grid
+    c->cgrid = CoarseGridState{};   // a failing upload leaves no grid rather than the old box over new values
+    HIPCHK(c, c->d_cgrid.reserve(cells));
+    HIPCHK(c, hipMemcpy(c->d_cgrid.get(), sigma, cells * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    install_coarse_grid(c, lo, hi, res, {});
+    return NWE_OK;
+}
+
+int nwe_clear_coarse_grid(nwe_ctx* c) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!c->host_only && c->cgrid.set) {
+        ON_DEVICE(c);
+        TRY(wait_for_launches(c));
+    }
+    c->cgrid = CoarseGridState{};
+    return NWE_OK;
+}
+
+int nwe_get_coarse_grid(const nwe_ctx* c, float* lo, float* hi, int* res, float* inv) {
+    if (!c) return NWE_ERR_INVALID;
+    const CoarseGridState& g = c->cgrid;
+    if (!g.set) return NWE_ERR_STATE;   // no grid is set: the outputs stay untouched (and so does the error text of a const context)
+    for (int i = 0; i < 3; ++i) {
+        if (lo) lo[i] = g.lo[i];
+        if (hi) hi[i] = g.hi[i];
+        if (res) res[i] = g.res[i];
+        if (inv) inv[i] = g.inv[i];
+    }
+    return NWE_OK;
+}
+
+int nwe_coarse_grid_copy(nwe_ctx* c, float* host_values, int64_t n_values) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!c->cgrid.set) return NWE_ERR_STATE;
+    if (!host_values || n_values != c->cgrid.cells) return fail(c, NWE_ERR_INVALID, "coarse grid: the copy needs rx * ry * rz values");
+    if (c->host_only) return copy_out(&c->cgrid.host, host_values, n_values);
+    ON_DEVICE(c);
+    HIPCHK(c, hipMemcpy(host_values, c->d_cgrid.get(), (size_t)n_values * sizeof(float), hipMemcpyDeviceToHost));
+    return NWE_OK;
+}
+
+int nwe_bake_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, int precision, void* stream_) {
+    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
+    TRY(check_coarse_grid_box(c, lo, hi, res));
+    if (precision != NWE_PREC_F16X3 && precision != NWE_PREC_F16X1 && precision != NWE_PREC_F32)
+        return fail(c, NWE_ERR_INVALID, "unknown precision");
+    const NetState& n = c->net[NWE_NET_COARSE];
+    if (!n.set) return fail(c, NWE_ERR_STATE, "coarse grid: the coarse network is not set");
+    if (precision != NWE_PREC_F32 && !n.mfma_ok)
+        return fail(c, NWE_ERR_UNSUPPORTED,
+                    "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
+    hipStream_t stream = (hipStream_t)stream_;
+    ON_DEVICE(c);
+    TRY(wait_for_launches(c));   // the bake ends in a new grid: a queued launch still reads the old one
+    c->cgrid = CoarseGridState{};   // a failing bake leaves no grid
+    OccBuild b = {};   // the probes = 1 lattice of nwe_build_occupancy: the cells' centres
+    for (int i = 0; i < 3; ++i) {
+        b.lo[i] = lo[i]; b.res[i] = res[i];
+        b.step[i] = (float)(((double)hi[i] - (double)lo[i]) / (double)res[i]);
+    }
+    b.probes = 1;
+    const int64_t cells = (int64_t)res[0] * res[1] * res[2];
+    const int chunk_cells = (int)std::min<int64_t>(cells, 1 << 20);   // the centres of a chunk in the scratch buffer: 12 MB at the most
+    HIPCHK(c, c->d_occ_scratch.reserve((size_t)chunk_cells * 3));
+    HIPCHK(c, c->d_cgrid.reserve((size_t)cells));
+    float* points = c->d_occ_scratch.get();
+    for (int64_t first = 0; first < cells; first += chunk_cells) {
+        const int count = (int)std::min<int64_t>(chunk_cells, cells - first);
+        launch_occ_probe_points(b, first, count, points, stream);
+        QueryArgs q = {};   // the sigma-only query of nwe_query_points, straight into the grid
+        q.points = points; q.sigma = c->d_cgrid.get() + first; q.n_points = count; q.points_per_dir = 1; q.density_only = 1;
+        if (precision == NWE_PREC_F32) launch_query_f32(q, n.f32, c->query_steps, c->cus, stream);
+        else if (!launch_query_mfma(q, n.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
+            return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(stream));
+    install_coarse_grid(c, lo, hi, res, {});
+    return NWE_OK;
+}
+
+int nwe_coarse_grid_weights(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near,
+                            float far, int row_begin, int row_end, float* sigma_out_dev, float* weights_out_dev, void* stream_) {
+    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
+    if (!c->cgrid.set) return fail(c, NWE_ERR_STATE, "coarse grid: no grid is set (nwe_set_coarse_grid, nwe_bake_coarse_grid)");
+    if (c->ns <= 0) return fail(c, NWE_ERR_STATE, "nwe_set_sampling has not been called");
+    const Camera m{c2w, n_poses, H, W, fx, fy, cx, cy, near, far, row_begin, row_end};
+    TRY(check_camera(c, m));
+    hipStream_t stream = (hipStream_t)stream_;
+    ON_DEVICE(c);
+    Slot& slot = c->rays_slot;   // not a slot of the ring, like nwe_create_rays: the timing calls keep describing the last render
+    TRY(prepare_slot(c, slot));
+    TRY(upload_poses(c, slot, c2w, n_poses, stream));
+    RenderArgs a = camera_args(m, slot.poses.get());
+    if (a.n_rays > INT32_MAX) return fail(c, NWE_ERR_INVALID, "more than 2^31 - 1 rays in one call");
+    context_args(c, a);
+    if (a.n_rays == 0 || (!sigma_out_dev && !weights_out_dev)) return NWE_OK;
+    return record_launch(c, slot, stream, [&]() -> int {
+        launch_coarse_grid_weights(a, coarse_grid_args(c), nullptr, sigma_out_dev, weights_out_dev, stream);
+        return NWE_OK;
+    });
 }
 
 int nwe_set_train_tables(nwe_ctx* c, const float* t_rand_dev, const float* noise_coarse_dev, const float* noise_fine_dev, const float* u_sorted_dev) {

@@ -91,6 +91,19 @@ void launch_occ_reduce_bits(const float* sigma, int64_t first, int n_cells, int 
 // dst = src dilated by one cell with the 3 x 3 x 3 box; res = (rx, ry, rz)
 void launch_occ_dilate(const uint32_t* src, uint32_t* dst, const int* res, hipStream_t stream);
 
+// ---- baked coarse pass (nwe_set_coarse_grid; nwe_coarse_grid.hip) ----
+// The coarse density grid of a context as its producer kernel reads it (by value): inv = (float)res / (hi - lo), formed once on
+// the host in fp32; sigma = res[0] * res[1] * res[2] values of sigma_raw at the cell centres, z fastest, on the device.
+struct CoarseGrid {
+    float lo[3], inv[3];
+    int res[3];
+    int pad;
+    const float* sigma;
+};
+// The producer: one thread per ray of `a` (pinhole rays: a.poses, the camera, a.t_vals / a.omt_vals, a.n_samples).  table
+// [n_samples][n_rays] (the consumer's, sample-major), sigma and weights [n_rays][n_samples]; each may be null.
+void launch_coarse_grid_weights(const RenderArgs& a, const CoarseGrid& g, float* table, float* sigma, float* weights, hipStream_t stream);
+
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);
 

@@ -88,8 +88,12 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     // shape only.  A lean call takes the sharing kernels, at k = 1 every pixel its own representative; every other call the
     // full kernels: the coarse launch is their single-pass render (n_importance = 0) whose weights_coarse output is the table,
     // the fine launch reads the table through the coarse-weights hook, which takes the place of pass 0.
+    // Baked coarse pass (a lean pinhole call - everything else has been refused - with importance samples): the same two
+    // stages at k = 1, but the producer fills the table from the context's density grid and is no MFMA launch group; the consumer
+    // takes the fine network's sharing kernels with that network in both descriptor slots, so the coarse network's shape is free.
+    p.baked = c.baked && c.n_importance > 0;
     p.separate = c.separate && c.mfma && c.n_importance > 0;
-    p.share = c.n_importance > 0 && (c.share_k > 1 || (p.separate && lean && c.built[0][kVariantShare] && c.built[1][kVariantShare]));
+    p.share = c.n_importance > 0 && (p.baked || c.share_k > 1 || (p.separate && lean && c.built[0][kVariantShare] && c.built[1][kVariantShare]));
     p.full = p.separate && !p.share;
     p.coarse_launch = p.share || (p.full && !c.w_in);   // with the coarse-weights hook armed there is no coarse pass
     p.share_k = p.share ? c.share_k : 1;
@@ -97,7 +101,8 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     p.need_evals = c.term || c.occ;
     // the table between the two launches: [n_samples][n_rep] of the sharing kernels, [n_rays][n_samples] of the full ones, which
     // may be the caller's own
-    if (p.share) p.table_elems = c.n_rep * c.n_samples;
+    if (p.baked) p.table_elems = c.n_rays * c.n_samples;
+    else if (p.share) p.table_elems = c.n_rep * c.n_samples;
     else if (p.full && p.coarse_launch && !c.want_weights_coarse) p.table_elems = c.n_rays * c.n_samples;
     p.coarse_flags = p.full && p.coarse_launch && c.want_flags;
 
@@ -105,17 +110,18 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     m.active = true;
     m.role = p.share || p.full ? kShareConsumer : kShareOff;
     m.n_rays = c.n_rays; m.n_importance = c.n_importance;
-    m.net = p.separate ? 1 : -1;
+    m.net = p.separate || p.baked ? 1 : -1;
     StagePlan& k = p.coarse;
     if (p.coarse_launch) {
         k.active = true;
         k.role = kShareProducer;
-        k.n_rays = p.share ? c.n_rep : c.n_rays;
-        k.n_importance = p.share ? c.n_importance : 0;
-        k.net = p.separate ? 0 : -1;
+        k.n_rays = p.share && !p.baked ? c.n_rep : c.n_rays;
+        k.n_importance = p.share && !p.baked ? c.n_importance : 0;
+        k.net = p.separate || p.baked ? 0 : -1;
     }
     p.evals_full = c.n_rays * (int64_t)(c.n_samples + (c.n_importance > 0 ? c.n_samples + c.n_importance : 0));
-    p.evals_run = p.coarse_launch ? k.n_rays * c.n_samples + c.n_rays * (int64_t)(c.n_samples + c.n_importance) : p.evals_full;
+    if (p.baked) p.evals_run = c.n_rays * (int64_t)(c.n_samples + c.n_importance);   // no coarse evaluation is run
+    else p.evals_run = p.coarse_launch ? k.n_rays * c.n_samples + c.n_rays * (int64_t)(c.n_samples + c.n_importance) : p.evals_full;
     p.share_rays = p.coarse_launch ? k.n_rays : 0;
     if (!c.mfma) return p;
 
@@ -134,7 +140,7 @@ CallPlan plan_call(const CallDesc& c, int cus) {
         return d;
     };
     // the launches through the full kernels are not lean: the coarse one writes the table, the fine one reads it
-    if (k.active) k.pass = plan_pass(describe(k, !p.full, false), cus);
+    if (k.active && !p.baked) k.pass = plan_pass(describe(k, !p.full, false), cus);
     PassDesc d = describe(m, !p.full, p.full || c.w_in);
     d.may_queue = plain_only && c.queue_mode != 0;
     d.side = c.backfill; d.tail = c.tail;

@@ -109,6 +109,7 @@ struct CallDesc {
     bool occ = false;              // an occupancy grid is set (nwe_set_occupancy): excludes term, sharing and separate passes
     int share_k = 1;               // nwe_set_shared_coarse
     bool separate = false;         // nwe_set_separate_passes
+    bool baked = false;            // a coarse density grid is set (nwe_set_coarse_grid): excludes term, occ, k > 1 and separate passes
     bool lean = false, stamps = false, stamped_build = false;   // as in PassDesc
     bool w_in = false;             // the coarse-weights hook is armed (nwe_debug_set_coarse_weights)
     bool want_weights_coarse = false, want_flags = false;        // outputs requested
@@ -137,6 +138,8 @@ struct CallPlan {
     bool need_side = false;       //   backfill on, the side streams exist
     bool need_evals = false;      // early termination, occupancy grid: the slot provides a zeroed evaluation counter
     bool occ = false;             // the main stage reads the context's occupancy grid (both kernels' occupancy instantiations)
+    bool baked = false;           // baked coarse pass: the coarse stage is the grid producer (nwe_coarse_grid.hip), which has no
+                                  //   PassPlan; the main stage is the sharing consumer at k = 1 with the fine network's kernels
     int share_k = 1;              // the k in both stages' share word
     int64_t table_elems = 0;      // the slot's weight table must hold this many floats (0: none, or the caller's own table serves)
     bool coarse_flags = false;    // the coarse launch's flags go through a word of the slot's (masked into the caller's)

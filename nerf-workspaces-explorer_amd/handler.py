@@ -51,8 +51,15 @@ class NeRFReplicaInferenceHandler:
 
     def __init__(self, office_name: str, ckpt_path: str, device: int = 0, precision: str = "auto",
                  devices: Optional[Sequence[int]] = None, early_termination: float = 0.0, shared_coarse: int = 1,
-                 separate_passes: Optional[bool] = None, occupancy: Optional[Mapping[str, object]] = None) -> None:
-        """``occupancy``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128), "probes" (2),
+                 separate_passes: Optional[bool] = None, occupancy: Optional[Mapping[str, object]] = None,
+                 baked_coarse: Optional[Mapping[str, object]] = None) -> None:
+        """``baked_coarse``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128, one int or
+        three): initialize_models() bakes the coarse network's density into a grid over the box (Renderer.bake_coarse_grid) and
+        frames take their coarse weights from it instead of running the coarse network - an approximation, off by default.
+        The environment variable NWE_BAKED_COARSE = "res" overrides the resolution over the box given here, for the same
+        two-argument callers; without a box there is no grid.  While a grid is set ``_render_rays`` raises what the ABI says;
+        it is refused together with ``early_termination > 0``, ``shared_coarse > 1``, ``separate_passes`` and ``occupancy``.
+        ``occupancy``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128), "probes" (2),
         "dilate" (1), "threshold" (0.0): initialize_models() builds an occupancy grid over the box from the networks it has
         uploaded (Renderer.build_occupancy) and frames skip the samples in cells it marks empty.  The environment variable
         NWE_OCCUPANCY = "res[,probes[,dilate]]" overrides these three over the box given here, for the same two-argument
@@ -114,6 +121,22 @@ class NeRFReplicaInferenceHandler:
             if self._early_termination > 0.0 or self._shared_coarse > 1 or self._separate_passes:
                 raise ValueError("an occupancy grid is not supported together with early_termination > 0, shared_coarse > 1 or separate_passes")
             self._occupancy = grid
+        self._baked_coarse = None
+        if baked_coarse is not None:
+            unknown = set(baked_coarse) - {"lo", "hi", "resolution"}
+            if unknown or "lo" not in baked_coarse or "hi" not in baked_coarse:
+                raise ValueError(f"baked_coarse needs 'lo' and 'hi' and may hold resolution; got {sorted(baked_coarse)}")
+            grid = {"resolution": 128}
+            grid.update(baked_coarse)
+            env = os.environ.get("NWE_BAKED_COARSE", "").strip()
+            if env != "":
+                if not env.isdigit():
+                    raise ValueError("NWE_BAKED_COARSE must be a resolution (one integer)")
+                grid["resolution"] = int(env)
+            if self._early_termination > 0.0 or self._shared_coarse > 1 or self._separate_passes or self._occupancy is not None:
+                raise ValueError("a baked coarse pass is not supported together with early_termination > 0, shared_coarse > 1, "
+                                 "separate_passes or an occupancy grid")
+            self._baked_coarse = grid
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -193,7 +216,8 @@ class NeRFReplicaInferenceHandler:
                 # the fused MFMA kernel runs both passes with one instantiation; separate passes launch one per network, which
                 # must still share their encodings (in_xyz, in_dir)
                 same_encodings = self._renderer.shapes[_lib.NET_COARSE][2:4] == self._renderer.shapes[_lib.NET_FINE][2:4]
-                mfma = self._separate_passes and same_encodings
+                # ... and so does a baked coarse pass, which runs the fine network's kernels only
+                mfma = (self._separate_passes or self._baked_coarse is not None) and same_encodings
                 if same_encodings and not mfma:
                     hint = "; separate_passes=True or NWE_SEPARATE_PASSES=1 renders such a pair with the MFMA kernels"
             self._precision = "f16x3" if mfma else "f32"
@@ -203,6 +227,8 @@ class NeRFReplicaInferenceHandler:
                       f"fp32 vector-ALU kernel (same results, ~25x slower){hint}")
         if self._occupancy is not None:     # behind the networks (set_network clears a grid) and the precision
             self.build_occupancy(**self._occupancy)
+        if self._baked_coarse is not None:
+            self.bake_coarse_grid(**self._baked_coarse)
 
     def _need_renderer(self) -> Renderer:
         if self._renderer is None:
@@ -368,6 +394,19 @@ class NeRFReplicaInferenceHandler:
 
     def clear_occupancy(self) -> None:
         self._need_renderer().clear_occupancy()
+
+    def bake_coarse_grid(self, lo: Sequence[float], hi: Sequence[float], resolution=128, precision: Optional[str] = None) -> None:
+        """Bakes the coarse network's density over the box lo..hi into the renderer's coarse grid (Renderer.bake_coarse_grid);
+        frames then take their coarse weights from it, and ``_render_rays`` raises what the ABI says until clear_coarse_grid()."""
+        self._need_renderer().bake_coarse_grid(lo, hi, resolution, precision or self._query_net("coarse")[1])
+
+    def clear_coarse_grid(self) -> None:
+        self._need_renderer().clear_coarse_grid()
+
+    @property
+    def coarse_grid(self):
+        """The renderer's coarse density grid (Renderer.coarse_grid), None without one."""
+        return self._need_renderer().coarse_grid
 
     @property
     def occupancy(self):

@@ -462,6 +462,86 @@ class Renderer:
         self._check(self._lib.nwe_occupancy_copy(self._ctx, words.ctypes.data, words.size), "nwe_occupancy_copy")
         return self.unpack_occupancy(words, (rx, ry, rz))
 
+    # -- baked coarse pass ------------------------------------------------------------------------
+    def set_coarse_grid(self, sigma, lo: Sequence[float], hi: Sequence[float], resolution=None) -> None:
+        """Opt-in baked coarse pass (include/nwe.h): ``sigma`` holds sigma_raw of the coarse network at the cell centres of the
+        box lo..hi, a float32 [rx, ry, rz] array (numpy, or a torch tensor on any device; what handler.density_grid returns) or
+        a flat array with ``resolution`` given.  While a grid is set, ``render`` of rgb / depth / acc with n_importance > 0 takes
+        its coarse weights from the trilinearly interpolated grid instead of running the coarse network; every other call
+        raises NotImplementedError, and so does every call while early termination, a shared coarse pass, separate passes or
+        an occupancy grid are on as well.  ``set_network`` of the coarse network clears the grid."""
+        if resolution is None:
+            resolution = tuple(sigma.shape)
+        lo3, hi3, res3, res = self._occupancy_box(lo, hi, resolution)
+        on_device = isinstance(sigma, torch.Tensor) and self.device is not None and sigma.device == self.device
+        if on_device:
+            values = sigma.detach().to(torch.float32).contiguous()
+            n, ptr = values.numel(), values.data_ptr()
+        else:
+            if isinstance(sigma, torch.Tensor):
+                sigma = sigma.detach().cpu().numpy()
+            values = np.ascontiguousarray(np.asarray(sigma, dtype=np.float32))
+            n, ptr = values.size, values.ctypes.data
+        if min(res) > 0 and n != res[0] * res[1] * res[2]:
+            raise ValueError(f"the coarse grid needs {res[0] * res[1] * res[2]} values for resolution {res}, got {n}")
+        if on_device:
+            torch.cuda.current_stream(self.device).synchronize()   # the copy inside is not ordered with torch's stream
+        self._check(self._lib.nwe_set_coarse_grid(self._ctx, lo3, hi3, res3, ptr if n else None, 1 if on_device else 0), "nwe_set_coarse_grid")
+
+    def bake_coarse_grid(self, lo: Sequence[float], hi: Sequence[float], resolution, precision: str = "f16x3") -> None:
+        """Bakes the grid from the coarse network that is set (nwe_bake_coarse_grid): its sigma_raw at the cell centres."""
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"unknown precision {precision!r}")
+        lo3, hi3, res3, _ = self._occupancy_box(lo, hi, resolution)
+        stream = None
+        if self.device is not None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.nwe_bake_coarse_grid(self._ctx, lo3, hi3, res3, _lib.PRECISIONS[precision], stream), "nwe_bake_coarse_grid")
+
+    def clear_coarse_grid(self) -> None:
+        self._check(self._lib.nwe_clear_coarse_grid(self._ctx), "nwe_clear_coarse_grid")
+
+    @property
+    def coarse_grid(self) -> Optional[Dict[str, object]]:
+        """None, or the grid: "lo", "hi", "resolution" and "inv" (the fp32 factors the kernel multiplies by)."""
+        lo, hi, res, inv = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_int * 3)(), (C.c_float * 3)()
+        if self._lib.nwe_get_coarse_grid(self._ctx, lo, hi, res, inv) != _lib.NWE_OK:
+            return None
+        return {"lo": tuple(lo), "hi": tuple(hi), "resolution": tuple(res), "inv": np.array(list(inv), dtype=np.float32)}
+
+    def coarse_grid_values(self) -> Optional[np.ndarray]:
+        """The grid's values as a float32 [rx, ry, rz] array on the host, None without one."""
+        g = self.coarse_grid
+        if g is None:
+            return None
+        rx, ry, rz = g["resolution"]
+        values = np.empty(rx * ry * rz, dtype=np.float32)
+        self._check(self._lib.nwe_coarse_grid_copy(self._ctx, values.ctypes.data, values.size), "nwe_coarse_grid_copy")
+        return values.reshape(rx, ry, rz)
+
+    def coarse_grid_weights(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
+                            rows: Optional[Tuple[int, int]] = None, outputs: Sequence[str] = ("sigma", "weights")) -> Dict[str, torch.Tensor]:
+        """Test hook (nwe_coarse_grid_weights): the producer of the baked coarse pass alone, for the rays of ``render`` with the
+        same arguments: "sigma" [R, n_samples] = the grid's sigma_raw per coarse sample, "weights" [R, n_samples] = the coarse
+        weights it composites from them."""
+        outputs = tuple(outputs)
+        if set(outputs) - {"sigma", "weights"}:
+            raise ValueError(f"outputs must be a choice of 'sigma' and 'weights', got {outputs!r}")
+        poses = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(-1, 4, 4))
+        r0, r1 = rows if rows is not None else (0, H)
+        if self.device is None:   # a host-only context: the ABI's own refusal
+            self._check(self._lib.nwe_coarse_grid_weights(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far,
+                                                          r0, r1, None, None, None), "nwe_coarse_grid_weights")
+        n_rays = poses.shape[0] * max(r1 - r0, 0) * W
+        with torch.cuda.device(self.device):
+            res = {k: torch.empty((n_rays, self.n_samples), dtype=torch.float32, device=self.device) for k in outputs}
+            ptr = lambda k: res[k].data_ptr() if k in res else None
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self._lib.nwe_coarse_grid_weights(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, r0, r1,
+                                                   ptr("sigma"), ptr("weights"), stream)
+        self._check(rc, "nwe_coarse_grid_weights")
+        return res
+
     def last_coarse_launch(self) -> Optional[Tuple[float, int]]:
         """(ms, rays) of the coarse (producer) launch of the last render, None if it had none (k = 1 without separate passes,
         n_importance == 0)."""
@@ -678,6 +758,25 @@ class TiledRenderer:
     def clear_occupancy(self) -> None:
         for p in self.parts:
             p.clear_occupancy()
+
+    def set_coarse_grid(self, sigma, lo: Sequence[float], hi: Sequence[float], resolution=None) -> None:
+        if isinstance(sigma, torch.Tensor):   # one host copy serves every part, whatever device it is on
+            sigma = sigma.detach().cpu().numpy()
+        for p in self.parts:
+            p.set_coarse_grid(sigma, lo, hi, resolution)
+
+    def bake_coarse_grid(self, lo: Sequence[float], hi: Sequence[float], resolution, precision: str = "f16x3") -> None:
+        """Baked once, on the first part, and copied to the others: every tile reads the same values."""
+        first = self.parts[0]
+        first.bake_coarse_grid(lo, hi, resolution, precision)
+        g = first.coarse_grid
+        values = first.coarse_grid_values() if len(self.parts) > 1 else None
+        for p in self.parts[1:]:
+            p.set_coarse_grid(values, g["lo"], g["hi"], g["resolution"])
+
+    def clear_coarse_grid(self) -> None:
+        for p in self.parts:
+            p.clear_coarse_grid()
 
     def render(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
                rows: Optional[Tuple[int, int]] = None, precision: str = "f16x3",
