@@ -714,6 +714,19 @@ int nwe_debug_last_tail_rest(nwe_ctx *ctx, unsigned *rendered);
 int nwe_debug_set_colour_skip(nwe_ctx *ctx, int mode);
 int nwe_debug_get_colour_skip(const nwe_ctx *ctx);              /* -1 for a null context */
 
+/* Packets of 8x4 pixel blocks ("Samples without density"): in a lean nwe_render call on the plain MFMA
+ * kernels (no early termination, shared or baked coarse pass, occupancy grid or separate passes) whose rows per pose are a
+ * multiple of 4 and whose W is a multiple of 8, the 32 rays of a wave are one block of 8 columns x 4 rows instead of 32
+ * consecutive pixels of a row, so that the hollow path above is taken more often.  No bit of any output depends on it.
+ * on = 1 (default) / 0; NWE_PACKET_BLOCKS=0 / 1 in the environment sets what a new context starts with.
+ * nwe_debug_last_packet_blocks: 1 / 0 = the call most recently planned on this context - rendered, or asked about with
+ * nwe_debug_plan - was / was not blocked; -1 for a null context.
+ * nwe_debug_packet_pixels: pixels[i] = the pixel index (row-major over [pose][row][column] of the call) that ray index first + i
+ * of a blocked call of width W names; needs no context. */
+int nwe_debug_set_packet_blocks(nwe_ctx *ctx, int on);
+int nwe_debug_last_packet_blocks(const nwe_ctx *ctx);
+int nwe_debug_packet_pixels(int64_t first, int64_t n, int W, int32_t *pixels);
+
 /* Diagnostic builds only (make -C csrc stamps): DEVICE buffer of 14 uint64 per wave that a -DNWE_STAMPS build of the MFMA
  * kernel fills with s_memtime cycle sums (tools/stamp_run.py); the product build never touches it.  NULL switches it off.
  * Row = (work item of its launch) * 4 + wave, however the items were dealt (nwe_debug_set_work_queue), and the rows of the hybrid

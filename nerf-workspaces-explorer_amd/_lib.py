@@ -31,7 +31,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_packed_colour_finite", "nwe_debug_set_colour_skip", "nwe_debug_get_colour_skip", "nwe_debug_plan",
            "nwe_set_occupancy", "nwe_clear_occupancy", "nwe_get_occupancy", "nwe_occupancy_copy", "nwe_build_occupancy",
            "nwe_set_coarse_grid", "nwe_clear_coarse_grid", "nwe_get_coarse_grid", "nwe_coarse_grid_copy", "nwe_bake_coarse_grid",
-           "nwe_coarse_grid_weights")
+           "nwe_coarse_grid_weights",
+           "nwe_debug_set_packet_blocks", "nwe_debug_last_packet_blocks", "nwe_debug_packet_pixels")
 
 
 class Outputs(C.Structure):
@@ -144,6 +145,9 @@ def load() -> C.CDLL:
         "nwe_packed_colour_finite": (I, [P, I]),
         "nwe_debug_set_colour_skip": (I, [P, I]),
         "nwe_debug_get_colour_skip": (I, [P]),
+        "nwe_debug_set_packet_blocks": (I, [P, I]),
+        "nwe_debug_last_packet_blocks": (I, [P]),
+        "nwe_debug_packet_pixels": (I, [I64, I64, I, P]),
         "nwe_debug_plan": (I, [P, I, I, I, I, I, I64, C.POINTER(Outputs), C.c_uint, I, I, C.POINTER(PlanReport)]),
         "nwe_set_occupancy": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), P, I]),
         "nwe_clear_occupancy": (I, [P]),

@@ -166,6 +166,8 @@ struct nwe_ctx {
     bool tail = true;         // the hybrid plan's split items in the packets launch's tail; NWE_WORK_QUEUE_TAIL=0: as without it
     int colour_skip = 1;      // nwe_debug_set_colour_skip; NWE_COLOUR_SKIP=0: a new context starts with 0
     int last_plan = -1;       // nwe_debug_last_plan
+    bool packet_blocks = true;       // nwe_debug_set_packet_blocks; NWE_PACKET_BLOCKS=0: a new context starts without
+    int last_packet_blocks = 0;      // nwe_debug_last_packet_blocks: the last call planned (rendered, or nwe_debug_plan) was blocked
     unsigned long long* stamps = nullptr;   // nwe_debug_set_stamps
     const float *trn_t = nullptr, *trn_nc = nullptr, *trn_nf = nullptr, *trn_u = nullptr;   // nwe_set_train_tables, one call
     std::string err;
@@ -468,6 +470,8 @@ CallDesc describe_call(const nwe_ctx* ctx, const RenderArgs& a, int precision) {
         }
     d.decomposition = ctx->decomposition; d.queue_mode = ctx->work_queue;
     d.backfill = ctx->backfill; d.tail = ctx->tail;
+    if (!a.rays) { d.rows = a.rows; d.width = a.W; }
+    d.packet_blocks = ctx->packet_blocks;
     return d;
 }
 
@@ -546,6 +550,8 @@ int launch(nwe_ctx* ctx, RenderSlot& slot, RenderArgs& a, int precision, hipStre
     TRY(provide(ctx, slot, p, stream));
     const RenderArgs prod = stage_args(p, slot, a);
     if (p.occ) a.occ = ctx->d_occ.get();   // the slot of `stamps`, which such a call does not have (check_ready)
+    if (p.blocks) a.ray_cols |= kPacketBlocksBit;   // a pinhole call: nothing else reads the word (nwe_packet_blocks.h)
+    ctx->last_packet_blocks = p.blocks ? 1 : 0;
     const NetState &nc = ctx->net[0], &nf = ctx->net[ctx->ni > 0 ? 1 : 0];
     // the launch's own descriptors: whether its lean kernels may take the hollow path with this network (nwe_debug_set_colour_skip)
     const auto with_skip = [&](const NetState& n) {
@@ -881,6 +887,8 @@ int nwe_create(nwe_ctx** out, int device) {
         if ((e[0] == '0' || e[0] == '1') && !e[1]) c->tail = e[0] == '1';
     if (const char* e = std::getenv("NWE_COLOUR_SKIP"))           // A/B timing of the hollow path on one library
         if ((e[0] == '0' || e[0] == '1') && !e[1]) c->colour_skip = e[0] - '0';
+    if (const char* e = std::getenv("NWE_PACKET_BLOCKS"))         // A/B timing of the 8x4 packets on one library
+        if ((e[0] == '0' || e[0] == '1') && !e[1]) c->packet_blocks = e[0] == '1';
     if (!c->host_only) {
         const hipError_t e = hipSetDevice(device);
         if (e != hipSuccess) { delete c; return fail(nullptr, NWE_ERR_HIP, std::string("nwe_create: ") + hipGetErrorString(e)); }
@@ -1167,6 +1175,13 @@ int nwe_debug_set_work_queue(nwe_ctx* c, int mode) { return set_on(mode < -1 || 
 int nwe_debug_get_work_queue(const nwe_ctx* c) { return c ? c->work_queue : -2; }
 int nwe_debug_set_colour_skip(nwe_ctx* c, int mode) { return set_on(mode < 0 || mode > 2 ? nullptr : c, [&] { c->colour_skip = mode; }); }
 int nwe_debug_get_colour_skip(const nwe_ctx* c) { return c ? c->colour_skip : -1; }
+int nwe_debug_set_packet_blocks(nwe_ctx* c, int on) { return set_on(on < 0 || on > 1 ? nullptr : c, [&] { c->packet_blocks = on != 0; }); }
+int nwe_debug_last_packet_blocks(const nwe_ctx* c) { return c ? c->last_packet_blocks : -1; }
+int nwe_debug_packet_pixels(int64_t first, int64_t n, int W, int32_t* pixels) {
+    if (first < 0 || n < 0 || first + n > INT32_MAX || W < 1 || W > (INT32_MAX / kBlockH) || (n > 0 && !pixels)) return NWE_ERR_INVALID;
+    for (int64_t i = 0; i < n; ++i) pixels[i] = packet_block_pixel((int)(first + i), W);
+    return NWE_OK;
+}
 int nwe_debug_get_work_queue_backfill(const nwe_ctx* c) { return c ? (c->backfill ? 1 : 0) : -1; }
 unsigned nwe_debug_queue_grid(unsigned items) { return queue_grid(items); }
 // The plan of a call without the call: check_ready's refusals, the entry point's own, then plan_call at the given CU count.
@@ -1196,6 +1211,7 @@ int nwe_debug_plan(nwe_ctx* c, int n_poses, int H, int W, int row_begin, int row
     context_args(c, a);
     if (a.n_rays <= 0) return NWE_OK;   // the call launches nothing
     const CallPlan p = plan_call(describe_call(c, a, precision), cus);
+    c->last_packet_blocks = p.blocks ? 1 : 0;
     report->separate = p.separate; report->share = p.share; report->full = p.full; report->coarse_launch = p.coarse_launch;
     report->may_queue = p.may_queue; report->need_side = p.need_side; report->need_evals = p.need_evals;
     report->coarse_flags = p.coarse_flags; report->share_k = p.share_k;

@@ -38,7 +38,16 @@
     const bool gone = ridx64 >= a.n_rays;                      // TERM: a lane past the call's rays computes along and has no say
     // One 32-bit row index per lane (the ABI keeps n_rays below 2^31): the ray's own index, or the call's last ray for the
     // lanes of a ragged last packet, which compute along and store nothing.  64-bit only where an offset is formed.
-    const int row = (int)(ridx64 < a.n_rays ? ridx64 : a.n_rays - 1);
+    int row_of = (int)(ridx64 < a.n_rays ? ridx64 : a.n_rays - 1);
+#ifndef NWE_ITEM_OCC
+    // A blocked call (nwe_packet_blocks.h; the lean plain and tail kernels, by plan_call's decision): the index names pixel pi(j),
+    // so that the packet is an 8x4 block.  Everything from here on - the seed, the tables' rows, every store - sees the pixel; gone,
+    // lane_live and live above are the index's, and such a call has no ragged packet.
+    if constexpr (LEAN && !TERM && !SHARE) {
+        if (a.ray_cols & kPacketBlocksBit) row_of = packet_block_pixel(row_of, a.W);
+    }
+#endif
+    const int row = row_of;
     const int64_t ridx = row, rclamp = row;
     // The ray is kept as its three-register seed and expanded at the top of every sample iteration (bit-identical by
     // construction): nothing of it but |d| stays in registers across an MLP evaluation.  The empty asm hides the seed from

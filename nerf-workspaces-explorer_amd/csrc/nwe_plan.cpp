@@ -147,6 +147,12 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     m.pass = plan_pass(d, cus);
     p.may_queue = m.pass.queued();   // a call that queues nothing pays nothing
     p.need_side = p.may_queue && c.backfill;
+    // Packets of 8x4 pixel blocks (nwe_packet_blocks.h): a lean pinhole frame that is one fused launch group of the plain kernels
+    // (the tail kernel with them) - the terminating, sharing and occupancy kernels and the baked consumer keep their linear
+    // packets - whose rows per pose are whole bands and whose width is whole blocks.  Then n_rays, the hybrid plan's first ray
+    // of the second launch (whole rounds of 128-ray workgroups) and the tail kernel's split part all are multiples of 32: no
+    // packet is ragged, and every packet is one block.
+    p.blocks = c.packet_blocks && lean && plain_only && m.pass.ok && m.pass.variant == kVariantPlain && packet_blocks_fit(c.rows, c.width);
     return p;
 }
 

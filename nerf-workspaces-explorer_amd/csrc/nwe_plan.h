@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "nwe_pack.h"   // Form
+#include "nwe_packet_blocks.h"
 
 namespace nwe {
 
@@ -14,6 +15,7 @@ constexpr int kMaxImportance = 256;  // n_importance upper bound
 
 constexpr int kWaves = 4;
 constexpr int kRaysPerWave = 32;
+static_assert(kBlockW * kBlockH == kRaysPerWave, "a packet is one pixel block");
 
 // Coarse samples the LDS weight / cdf buffer holds: four packets per workgroup keep one buffer per wave (64 samples); the
 // sample-split decomposition has ONE packet per workgroup and one shared buffer, which holds the ABI's full 128 samples
@@ -116,6 +118,8 @@ struct CallDesc {
     bool built[2][kVariants] = {};                               // per network (coarse, fine): the variants its shape has
     int decomposition = -1, queue_mode = -1;
     bool backfill = true, tail = true;
+    int rows = 0, width = 0;       // a pinhole call: the rows rendered per pose and the image width; 0 for a ray list
+    bool packet_blocks = false;    // nwe_debug_set_packet_blocks
 };
 
 // One stage = one launch group with its own RenderArgs: the coarse stage (the producer of a shared coarse pass, the coarse
@@ -141,6 +145,7 @@ struct CallPlan {
     bool baked = false;           // baked coarse pass: the coarse stage is the grid producer (nwe_coarse_grid.hip), which has no
                                   //   PassPlan; the main stage is the sharing consumer at k = 1 with the fine network's kernels
     int share_k = 1;              // the k in both stages' share word
+    bool blocks = false;          // the call is blocked (nwe_packet_blocks.h): the launches carry kPacketBlocksBit
     int64_t table_elems = 0;      // the slot's weight table must hold this many floats (0: none, or the caller's own table serves)
     bool coarse_flags = false;    // the coarse launch's flags go through a word of the slot's (masked into the caller's)
     int64_t evals_full = 0, evals_run = 0, share_rays = 0;   // nwe_last_ray_evaluations, nwe_last_coarse_launch

@@ -333,6 +333,15 @@ class Renderer:
     def debug_get_colour_skip(self) -> int:
         return int(self._lib.nwe_debug_get_colour_skip(self._ctx))
 
+    def debug_set_packet_blocks(self, on: bool) -> None:
+        """Packets of 8x4 pixel blocks in lean frames on the plain MFMA kernels (include/nwe.h); on by default, or what
+        NWE_PACKET_BLOCKS set when the renderer was created.  No output depends on it."""
+        self._check(self._lib.nwe_debug_set_packet_blocks(self._ctx, 1 if on else 0), "nwe_debug_set_packet_blocks")
+
+    def debug_last_packet_blocks(self) -> int:
+        """1 / 0: the call most recently planned (rendered, or asked about with nwe_debug_plan) was / was not blocked."""
+        return int(self._lib.nwe_debug_last_packet_blocks(self._ctx))
+
     def debug_get_work_queue_tail(self) -> bool:
         """Whether this renderer may take the tail path: fixed when it was created (NWE_WORK_QUEUE_TAIL=0 in the environment then)."""
         return bool(self._lib.nwe_debug_get_work_queue_tail(self._ctx))

@@ -7,13 +7,14 @@
 #            nobackfill       the product library with NWE_WORK_QUEUE_BACKFILL=0: queued launches one after the other
 #            notail           the product library with NWE_WORK_QUEUE_TAIL=0: the split items in a launch of their own, beside the packets
 #            noskip           the product library with NWE_COLOUR_SKIP=0: every evaluation runs its colour layers
+#            noblocks         the product library with NWE_PACKET_BLOCKS=0: packets of 32 consecutive pixels of a row
 # Usage (on the GPU box): bash tools/ab_bench.sh arm1 [arm2 ...] -> one line per run on stdout, and in the file $AB_OUT if that is set
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=${AB_OUT:-/dev/null}
 : > $OUT
 for rep in 1 2 3; do
   for v in product "$@"; do
-    unset NWE_LIB NWE_WORK_QUEUE NWE_WORK_QUEUE_BACKFILL NWE_WORK_QUEUE_TAIL NWE_COLOUR_SKIP
+    unset NWE_LIB NWE_WORK_QUEUE NWE_WORK_QUEUE_BACKFILL NWE_WORK_QUEUE_TAIL NWE_COLOUR_SKIP NWE_PACKET_BLOCKS
     TREE=$ROOT
     case "$v" in
       product) ;;
@@ -21,6 +22,7 @@ for rep in 1 2 3; do
       nobackfill) export NWE_WORK_QUEUE_BACKFILL=0 ;;
       notail) export NWE_WORK_QUEUE_TAIL=0 ;;
       noskip) export NWE_COLOUR_SKIP=0 ;;
+      noblocks) export NWE_PACKET_BLOCKS=0 ;;
       *=*) if [ -d "${v#*=}" ]; then TREE=${v#*=}; else export NWE_LIB=${v#*=}; fi ;;
       *) export NWE_LIB=$ROOT/nerf-workspaces-explorer_amd/csrc/exp/libnwe_$v.so ;;
     esac
