@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "nwe_check.h"
 #include "nwe_host.h"
 #include "nwe_pack.h"
 
@@ -42,13 +43,10 @@ struct DevBuf {
     }
 };
 
-struct NetState : NetShape {
-    bool set = false;
+struct NetState : NetDesc {       // shape, set, form, mfma_ok, built: what the checks and the planner read (nwe_check.h)
     int64_t flops = 0;
     Packed p;                      // host side: blob + offsets, stream, bias table, scale (nwe_pack.h)
     NetF32 f32 = {};               // fp32 kernel: p.f32 with the blob on the device
-    bool mfma_ok = false;
-    int form = kFormFolded;        // MFMA stream: which formulation it holds (nwe_pack.h: Form)
     NetMfma mf = {};
     DevBuf<float> d_blob, d_bias;  // device side: copies of p.blob, p.bias_tab
     DevBuf<uint8_t> d_stream;      //              and of p.stream
@@ -94,14 +92,36 @@ struct RenderSlot : Slot {
     unsigned tail_items = 0;
 };
 
+// The box of either grid of a context, as its checks let it through (check_grid_box).
+struct GridBox {
+    float lo[3] = {}, hi[3] = {}, inv[3] = {};
+    int res[3] = {};
+    int64_t cells = 0;
+    GridBox() = default;
+    GridBox(const float* lo_, const float* hi_, const int* res_) : cells((int64_t)res_[0] * res_[1] * res_[2]) {
+        for (int i = 0; i < 3; ++i) {
+            lo[i] = lo_[i]; hi[i] = hi_[i]; res[i] = res_[i];
+            inv[i] = (float)res[i] / (hi[i] - lo[i]);   // fp32, once: what the kernels multiply by (nwe_get_occupancy / _coarse_grid report it)
+        }
+    }
+    // nwe_get_occupancy, nwe_get_coarse_grid: every pointer may be null
+    void read(float* lo_, float* hi_, int* res_, float* inv_) const {
+        for (int i = 0; i < 3; ++i) {
+            if (lo_) lo_[i] = lo[i];
+            if (hi_) hi_[i] = hi[i];
+            if (res_) res_[i] = res[i];
+            if (inv_) inv_[i] = inv[i];
+        }
+    }
+};
+
 // The occupancy grid of a context (nwe_set_occupancy, nwe_build_occupancy).  The words on the host are the truth of
 // nwe_get_occupancy / nwe_occupancy_copy and all there is on a host-only context; a device context also holds them, and the
 // descriptor the occupancy kernels read, in buffers of its own.
 struct Occupancy {
     bool set = false;
-    float lo[3] = {}, hi[3] = {}, inv[3] = {};
-    int res[3] = {};
-    int64_t cells = 0, occupied = 0;
+    GridBox box;
+    int64_t occupied = 0;
     std::vector<uint32_t> bits;
 };
 
@@ -109,9 +129,7 @@ struct Occupancy {
 // device only (d_cgrid: up to 512^3 floats), a host-only context in `host`.
 struct CoarseGridState {
     bool set = false;
-    float lo[3] = {}, hi[3] = {}, inv[3] = {};
-    int res[3] = {};
-    int64_t cells = 0;
+    GridBox box;
     std::vector<float> host;
 };
 
@@ -197,6 +215,28 @@ struct DeviceGuard {
     } while (0)
 #define ON_DEVICE(c) DeviceGuard guard; HIPCHK(c, hipSetDevice(c->device))   // the rest of the entry point runs on c's device
 #define TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+// A check of nwe_check.h: its refusal, if any, becomes the context's error and the entry point's return value.
+#define CHECK(c, check) do { const Refusal r_ = (check); if (r_) return fail(c, r_.code, r_.text); } while (0)
+
+// The context as plain data, read here and nowhere else: what a call is checked against (nwe_check.h) and planned from (describe_call).
+ContextDesc describe_context(const nwe_ctx* c) {
+    ContextDesc d;
+    for (int i = 0; i < 2; ++i) d.net[i] = c->net[i];
+    d.ns = c->ns; d.ni = c->ni; d.host_only = c->host_only;
+    d.min_trans = c->min_trans; d.share_k = c->share_k; d.separate = c->separate != 0;
+    d.occ.set = c->occ.set; d.cgrid.set = c->cgrid.set;
+    for (int i = 0; i < 3; ++i) { d.occ.res[i] = c->occ.box.res[i]; d.cgrid.res[i] = c->cgrid.box.res[i]; }
+    d.stamps = c->stamps != nullptr;
+    d.decomposition = c->decomposition; d.queue_mode = c->work_queue;
+    d.backfill = c->backfill; d.tail = c->tail; d.packet_blocks = c->packet_blocks;
+    return d;
+}
+// ... of a context that may be null: what the checks that refuse a null context take
+struct MaybeContext {
+    ContextDesc d;
+    const ContextDesc* p = nullptr;
+    explicit MaybeContext(const nwe_ctx* c) { if (c) { d = describe_context(c); p = &d; } }
+};
 
 __global__ void to8b_kernel(const float* __restrict__ x, uint8_t* __restrict__ y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -288,19 +328,6 @@ int upload_poses(nwe_ctx* c, Slot& s, const float* c2w, int n_poses, hipStream_t
     return NWE_OK;
 }
 
-// The camera of nwe_render, nwe_render_tiled and nwe_create_rays: poses, image, intrinsics, depth range and the rows asked for.
-struct Camera { const float* c2w; int n_poses, H, W; float fx, fy, cx, cy, near, far; int row_begin, row_end; };
-
-// The one check of a camera, in the order every entry point refuses in; the two texts that differ between them are arguments.
-int check_camera(nwe_ctx* c, const Camera& m, const char* bad_image = "bad pose / image / row range",
-                 const char* far_below_near = "far < near: the sorted merge of the fine pass needs ascending depths") {
-    if (!m.c2w || m.n_poses < 1 || m.H < 1 || m.W < 1 || m.row_begin < 0 || m.row_end > m.H || m.row_begin > m.row_end)
-        return fail(c, NWE_ERR_INVALID, bad_image);
-    if (!(m.fx != 0.f) || !(m.fy != 0.f)) return fail(c, NWE_ERR_INVALID, "fx and fy must be non-zero");
-    if (m.far < m.near) return fail(c, NWE_ERR_INVALID, far_below_near);
-    return NWE_OK;
-}
-
 // The camera part of RenderArgs: rays are generated in the kernel from the pose table `poses_dev`.
 RenderArgs camera_args(const Camera& m, const float* poses_dev) {
     RenderArgs a = {};
@@ -309,124 +336,6 @@ RenderArgs camera_args(const Camera& m, const float* poses_dev) {
     a.n_rays = (int64_t)m.n_poses * a.rows * m.W;
     a.fx = m.fx; a.fy = m.fy; a.cx = m.cx; a.cy = m.cy; a.near = m.near; a.far = m.far;
     return a;
-}
-
-// The refusals early termination and the shared coarse pass share: both render lean pinhole calls only, through kernels of
-// their own.  `on` / `off` open and close the mode's texts, `no_rays` is its word for nwe_render_rays, `kind` names its kernels.
-int check_lean_mode(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole, const std::string& on, const char* off,
-                    const char* no_rays, const std::string& kind, int variant, bool fine_only = false) {
-    // what only a ray's own full passes can give is refused by name rather than changed in silence
-    if (!pinhole) return fail(ctx, NWE_ERR_UNSUPPORTED, on + no_rays + off);
-    nwe_outputs rest = *out;
-    rest.struct_bytes = 0; rest.rgb = rest.depth = rest.acc = nullptr; rest.flags = nullptr;
-    const nwe_outputs none = {};
-    if (std::memcmp(&rest, &none, sizeof(none)) != 0)
-        return fail(ctx, NWE_ERR_UNSUPPORTED, on + "only rgb / depth / acc / flags can be requested" + off);
-    if (precision == NWE_PREC_F32) return NWE_OK;
-    // fine_only (baked coarse pass): the coarse network runs no kernel, and with n_importance == 0 the call is the ordinary one
-    for (int i = fine_only ? 1 : 0; i < (ctx->ni > 0 ? 2 : 1); ++i) {
-        const NetState& n = ctx->net[i];
-        if (mfma_variant_built(n.D, n.W, n.skip, n.form, variant)) continue;
-        return fail(ctx, NWE_ERR_UNSUPPORTED,
-                    on + (n.form == kFormReference ? "a network packed unfolded (nwe_debug_set_fold(0)) has no " + kind + " MFMA kernel"
-                                                   : "no " + kind + " MFMA kernel was built for this network shape") + "; use NWE_PREC_F32" + off);
-    }
-    return NWE_OK;
-}
-
-// pinhole: nwe_render / a tile of nwe_render_tiled (false: nwe_render_rays).  The refusals of early termination and of the
-// shared coarse pass come last, and those of separate passes behind them.  planning: nwe_debug_plan, which a host-only context serves.
-int check_ready(nwe_ctx* ctx, const nwe_outputs* out, int precision, bool pinhole, bool planning = false) {
-    if (!ctx || !out) return fail(ctx, NWE_ERR_INVALID, "null context or outputs");
-    if (out->struct_bytes != sizeof(nwe_outputs))
-        return fail(ctx, NWE_ERR_INVALID, "nwe_outputs.struct_bytes != sizeof(nwe_outputs): the caller was built against another version of include/nwe.h");
-    if (ctx->host_only && !planning) return fail(ctx, NWE_ERR_STATE, "host-only context cannot render");
-    if (ctx->ns <= 0) return fail(ctx, NWE_ERR_STATE, "nwe_set_sampling has not been called");
-    if (!ctx->net[0].set) return fail(ctx, NWE_ERR_STATE, "coarse network not set");
-    if (ctx->ni > 0 && !ctx->net[1].set) return fail(ctx, NWE_ERR_STATE, "fine network not set but n_importance > 0");
-    if (precision != NWE_PREC_F16X3 && precision != NWE_PREC_F16X1 && precision != NWE_PREC_F32)
-        return fail(ctx, NWE_ERR_INVALID, "unknown precision");
-    if (ctx->ni > 0 && (ctx->net[0].in_dir == 0) != (ctx->net[1].in_dir == 0))
-        return fail(ctx, NWE_ERR_STATE, "coarse and fine networks must both have, or both lack, view directions");
-    // one Embedding serves both networks in the reference (handler.py:93-103) and one gamma(d) per ray both passes here
-    if (ctx->ni > 0 && (ctx->net[0].in_xyz != ctx->net[1].in_xyz || ctx->net[0].in_dir != ctx->net[1].in_dir))
-        return fail(ctx, NWE_ERR_STATE,
-                    "coarse and fine networks must share their encodings: in_xyz " + std::to_string(ctx->net[0].in_xyz) + " / " +
-                        std::to_string(ctx->net[1].in_xyz) + ", in_dir " + std::to_string(ctx->net[0].in_dir) + " / " +
-                        std::to_string(ctx->net[1].in_dir) + " (coarse / fine)");
-    if (out->feat_map) {
-        if (ctx->ni <= 0 || ctx->net[1].in_dir == 0)
-            return fail(ctx, NWE_ERR_INVALID, "feat_map is the fine pass's view-layer output: it needs n_importance > 0 and networks with view directions");
-        if (precision != NWE_PREC_F32)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, "feat_map (endpoint_feat) is computed by the NWE_PREC_F32 kernel only");
-    }
-    if (precision != NWE_PREC_F32) {
-        // a baked coarse pass (nwe_set_coarse_grid) runs no kernel of the coarse network: its shape is not constrained
-        const bool coarse_runs = !(ctx->cgrid.set && ctx->ni > 0);
-        if ((coarse_runs && !ctx->net[0].mfma_ok) || (ctx->ni > 0 && !ctx->net[1].mfma_ok))
-            return fail(ctx, NWE_ERR_UNSUPPORTED,
-                        "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
-        if (ctx->ns > mfma_max_samples())
-            return fail(ctx, NWE_ERR_UNSUPPORTED, "the MFMA kernel supports n_samples <= 128; use NWE_PREC_F32");
-    }
-    const std::string sharing = "the shared coarse pass is on (nwe_set_shared_coarse, k = " + std::to_string(ctx->share_k) + "): ";
-    if (ctx->share_k > 1 && ctx->min_trans > 0.f)
-        return fail(ctx, NWE_ERR_UNSUPPORTED, sharing + "it is not built together with early termination (nwe_set_early_termination, min_transmittance = " +
-                                                  std::to_string(ctx->min_trans) + "); switch one of them off");
-    if (ctx->share_k > 1)
-        TRY(check_lean_mode(ctx, out, precision, pinhole, sharing, "; set shared_coarse to 1 for this call",
-                            "nwe_render_rays has no pixel grid to share over", "sharing", kVariantShare));
-    if (ctx->min_trans > 0.f)
-        TRY(check_lean_mode(ctx, out, precision, pinhole,
-                            "early termination is on (nwe_set_early_termination, min_transmittance = " + std::to_string(ctx->min_trans) + "): ",
-                            "; set min_transmittance to 0 for this call", "nwe_render_rays, its hooks and its training tables are not terminated",
-                            "terminating", kVariantTerm));
-    if (ctx->separate && precision != NWE_PREC_F32) {
-        const std::string separate = "separate passes are on (nwe_set_separate_passes): ";
-        const char* separate_off = "; set separate_passes to 0 for this call";
-        if (ctx->min_trans > 0.f)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, separate + "they are not built together with early termination (nwe_set_early_termination, min_transmittance = " +
-                                                      std::to_string(ctx->min_trans) + "), which would need terminating consumer kernels; switch one of them off");
-        if (ctx->ni > 0 && ctx->net[0].form != ctx->net[1].form)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, separate + "coarse and fine networks must be packed in the same formulation (nwe_debug_set_fold); use NWE_PREC_F32" + separate_off);
-    }
-    if (ctx->occ.set) {
-        const Occupancy& g = ctx->occ;
-        const std::string grid = "an occupancy grid is set (nwe_set_occupancy, " + std::to_string(g.res[0]) + " x " + std::to_string(g.res[1]) + " x " +
-                                 std::to_string(g.res[2]) + "): ";
-        const char* grid_off = "; call nwe_clear_occupancy for this call";
-        if (ctx->min_trans > 0.f)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with early termination (nwe_set_early_termination, min_transmittance = " +
-                                                      std::to_string(ctx->min_trans) + "); switch one of them off");
-        if (ctx->share_k > 1)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with the shared coarse pass (nwe_set_shared_coarse, k = " +
-                                                      std::to_string(ctx->share_k) + "); switch one of them off");
-        if (ctx->separate)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with separate passes (nwe_set_separate_passes); switch one of them off");
-        TRY(check_lean_mode(ctx, out, precision, pinhole, grid, grid_off, "nwe_render_rays, its hooks and its training tables do not read the grid",
-                            "occupancy", kVariantOcc));
-        if (ctx->stamps) return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "a stamped launch (nwe_debug_set_stamps) has no occupancy kernel" + grid_off);
-    }
-    if (ctx->cgrid.set) {
-        const CoarseGridState& g = ctx->cgrid;
-        const std::string grid = "a coarse density grid is set (nwe_set_coarse_grid, " + std::to_string(g.res[0]) + " x " + std::to_string(g.res[1]) + " x " +
-                                 std::to_string(g.res[2]) + "): ";
-        const char* grid_off = "; call nwe_clear_coarse_grid for this call";
-        if (ctx->min_trans > 0.f)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with early termination (nwe_set_early_termination, min_transmittance = " +
-                                                      std::to_string(ctx->min_trans) + "); switch one of them off");
-        if (ctx->share_k > 1)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with the shared coarse pass (nwe_set_shared_coarse, k = " +
-                                                      std::to_string(ctx->share_k) + "); switch one of them off");
-        if (ctx->separate)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with separate passes (nwe_set_separate_passes); switch one of them off");
-        if (ctx->occ.set)
-            return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "it is not built together with an occupancy grid (nwe_set_occupancy); clear one of them");
-        TRY(check_lean_mode(ctx, out, precision, pinhole, grid, grid_off, "nwe_render_rays, its hooks and its training tables do not read the grid",
-                            "sharing", kVariantShare, true));
-        if (ctx->stamps) return fail(ctx, NWE_ERR_UNSUPPORTED, grid + "a stamped launch (nwe_debug_set_stamps) has no sharing kernel" + grid_off);
-    }
-    return NWE_OK;
 }
 
 #ifdef NWE_STAMPS
@@ -446,32 +355,29 @@ void context_args(const nwe_ctx* ctx, RenderArgs& a) {
 }
 
 // The call as the planner sees it (nwe_plan.h): `a` as the entry point and context_args() filled it, the context's modes.
-CallDesc describe_call(const nwe_ctx* ctx, const RenderArgs& a, int precision) {
+CallDesc describe_call(const ContextDesc& ctx, const RenderArgs& a, int precision) {
     CallDesc d;
     d.n_rays = a.n_rays;
     RenderArgs consumer = a;
-    consumer.share = kShareConsumer | ctx->share_k << 8;
+    consumer.share = kShareConsumer | ctx.share_k << 8;
     d.n_rep = share_n_rep(consumer, share_grid(consumer));   // at most n_rays
     d.n_samples = a.n_samples; d.n_importance = a.n_importance;
     d.mfma = precision != NWE_PREC_F32;
     d.term = a.min_trans > 0.f;
-    d.occ = ctx->occ.set;
-    d.share_k = ctx->share_k; d.separate = ctx->separate != 0;
-    d.baked = ctx->cgrid.set;   // check_ready has let nothing but lean pinhole calls through
+    d.occ = ctx.occ.set;
+    d.share_k = ctx.share_k; d.separate = ctx.separate;
+    d.baked = ctx.cgrid.set;   // check_ready has let nothing but lean pinhole calls through
     RenderArgs unstamped = a;
     unstamped.stamps = nullptr;
     d.lean = mfma_is_lean(unstamped); d.stamps = a.stamps != nullptr; d.stamped_build = kStampedBuild;
     d.w_in = a.w_in != nullptr;
     d.want_weights_coarse = a.out.weights_coarse != nullptr; d.want_flags = a.out.flags != nullptr;
     for (int i = 0; i < 2; ++i)
-        for (int v = 0; v < kVariants; ++v) {
-            const NetState& n = ctx->net[i];
-            d.built[i][v] = n.set && n.mfma_ok && mfma_variant_built(n.D, n.W, n.skip, n.form, v);
-        }
-    d.decomposition = ctx->decomposition; d.queue_mode = ctx->work_queue;
-    d.backfill = ctx->backfill; d.tail = ctx->tail;
+        for (int v = 0; v < kVariants; ++v) d.built[i][v] = ctx.net[i].set && ctx.net[i].mfma_ok && ctx.net[i].built[v];
+    d.decomposition = ctx.decomposition; d.queue_mode = ctx.queue_mode;
+    d.backfill = ctx.backfill; d.tail = ctx.tail;
     if (!a.rays) { d.rows = a.rows; d.width = a.W; }
-    d.packet_blocks = ctx->packet_blocks;
+    d.packet_blocks = ctx.packet_blocks;
     return d;
 }
 
@@ -535,17 +441,18 @@ RenderArgs stage_args(const CallPlan& p, const RenderSlot& slot, RenderArgs& a) 
 // The context's coarse density grid as the producer kernel takes it.
 CoarseGrid coarse_grid_args(const nwe_ctx* ctx) {
     CoarseGrid g = {};
-    for (int i = 0; i < 3; ++i) { g.lo[i] = ctx->cgrid.lo[i]; g.inv[i] = ctx->cgrid.inv[i]; g.res[i] = ctx->cgrid.res[i]; }
+    const GridBox& box = ctx->cgrid.box;
+    for (int i = 0; i < 3; ++i) { g.lo[i] = box.lo[i]; g.inv[i] = box.inv[i]; g.res[i] = box.res[i]; }
     g.sigma = ctx->d_cgrid.get();
     return g;
 }
 
 // A render launch on the ring slot prepare_slot() made ready (ctx->slots[ctx->next_slot]): describe the call, plan it, carry
 // the plan out.  The ring moves on here, once the launch has been recorded.
-int launch(nwe_ctx* ctx, RenderSlot& slot, RenderArgs& a, int precision, hipStream_t stream) {
+int launch(nwe_ctx* ctx, const ContextDesc& desc, RenderSlot& slot, RenderArgs& a, int precision, hipStream_t stream) {
     context_args(ctx, a);
     if (a.n_rays <= 0) return NWE_OK;
-    const CallPlan p = plan_call(describe_call(ctx, a, precision), ctx->cus);
+    const CallPlan p = plan_call(describe_call(desc, a, precision), ctx->cus);
     const bool mfma = precision != NWE_PREC_F32, three_pass = precision == NWE_PREC_F16X3;
     TRY(provide(ctx, slot, p, stream));
     const RenderArgs prod = stage_args(p, slot, a);
@@ -617,16 +524,17 @@ int launch(nwe_ctx* ctx, RenderSlot& slot, RenderArgs& a, int precision, hipStre
 
 // nwe_render, and one tile of nwe_render_tiled.  Refuses in this order: check_ready, camera, device.
 int render_rows(nwe_ctx* c, const Camera& m, int precision, const nwe_outputs* out, hipStream_t stream) {
-    TRY(check_ready(c, out, precision, true));
-    TRY(check_camera(c, m));
+    const MaybeContext desc(c);
+    CHECK(c, check_ready(desc.p, out, precision, true));
+    CHECK(c, check_camera(m));
     ON_DEVICE(c);
     RenderSlot& slot = c->slots[c->next_slot];
     TRY(prepare_slot(c, slot));
     TRY(upload_poses(c, slot, m.c2w, m.n_poses, stream));
     RenderArgs a = camera_args(m, slot.poses.get());
-    if (a.n_rays > INT32_MAX) return fail(c, NWE_ERR_INVALID, "more than 2^31 - 1 rays in one call");
+    CHECK(c, check_ray_count(a.n_rays, false));
     a.out = *out;
-    return launch(c, slot, a, precision, stream);
+    return launch(c, desc.d, slot, a, precision, stream);
 }
 
 // 1 / 0: device `from` can / cannot read and write `to`'s memory directly; -1: the query failed (*err says how)
@@ -717,15 +625,6 @@ int queue_tile(nwe_ctx* c, nwe_ctx* c0, int i, const Camera& m, int precision, c
     return NWE_OK;   // record_on_exit records tile_done
 }
 
-// The refusals nwe_set_network and nwe_set_network_no_view_dirs share: the first four of each.
-int check_network_head(nwe_ctx* c, int which, int depth, int width, const float* const* w, const float* const* b) {
-    if (!c || !w || !b) return fail(c, NWE_ERR_INVALID, "null argument");
-    if (which != NWE_NET_COARSE && which != NWE_NET_FINE) return fail(c, NWE_ERR_INVALID, "which must be 0 or 1");
-    if (depth < 1 || depth > kMaxDepth) return fail(c, NWE_ERR_UNSUPPORTED, "depth must be in 1..16");
-    if (width < 2 || width > 256 || width % 2) return fail(c, NWE_ERR_UNSUPPORTED, "width must be even and <= 256");
-    return NWE_OK;
-}
-
 template <class T>
 int upload(nwe_ctx* c, DevBuf<T>& dst, const std::vector<T>& src) {
     HIPCHK(c, dst.reserve(src.size()));
@@ -734,9 +633,6 @@ int upload(nwe_ctx* c, DevBuf<T>& dst, const std::vector<T>& src) {
 }
 
 int set_network(nwe_ctx* c, int which, const NetShape& shape, const float* const* w, const float* const* b) {
-    const int n_layers = shape.in_dir == 0 ? shape.D + 1 : shape.D + 4;
-    for (int i = 0; i < n_layers; ++i)
-        if (!w[i] || !b[i]) return fail(c, NWE_ERR_INVALID, "null weight or bias pointer");
     NetState& n = c->net[which];
     n.set = false;   // stays false if anything below fails
     static_cast<NetShape&>(n) = shape;
@@ -746,6 +642,7 @@ int set_network(nwe_ctx* c, int which, const NetShape& shape, const float* const
     n.f32 = n.p.f32;
     n.form = n.in_dir == 0 ? kFormNoViewDirs : (c->fold != 0 ? kFormFolded : kFormReference);
     n.mfma_ok = mfma_supported(n.D, n.W, n.in_xyz, n.in_dir, n.skip, n.form);
+    for (int v = 0; v < kVariants; ++v) n.built[v] = mfma_variant_built(n.D, n.W, n.skip, n.form, v);
     if (n.mfma_ok) pack_mfma(n.p, n, n.form, w, b); else { n.p.stream.clear(); n.p.bias_tab.clear(); n.p.n_chunks = 0; }
     n.mf = {};
     n.mf.D = n.D; n.mf.W = n.W; n.mf.skip = n.skip; n.mf.form = n.form;
@@ -794,32 +691,12 @@ const RenderSlot* last_render(const nwe_ctx* c) { return c->host_only || c->last
 
 int64_t occ_words(int64_t cells) { return (cells + 31) / 32; }
 
-// The refusals nwe_set_occupancy and nwe_build_occupancy share, by name: null pointers, a box that is not finite or not
-// lo < hi on every axis, a resolution outside 1 .. 1024 per axis (1024^3 = 2^30 cells, below 2^31 in all).
-int check_occupancy_box(nwe_ctx* c, const float* lo, const float* hi, const int* res) {
-    if (!c) return NWE_ERR_INVALID;
-    if (!lo || !hi || !res) return fail(c, NWE_ERR_INVALID, "occupancy: null lo, hi or resolution");
-    for (int i = 0; i < 3; ++i) {
-        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !std::isfinite(hi[i] - lo[i]))
-            return fail(c, NWE_ERR_INVALID, "occupancy: the box must be finite");
-        if (!(lo[i] < hi[i])) return fail(c, NWE_ERR_INVALID, "occupancy: the box must have lo < hi on every axis");
-    }
-    for (int i = 0; i < 3; ++i)
-        if (res[i] < 1 || res[i] > 1024) return fail(c, NWE_ERR_INVALID, "occupancy: the resolution must be in 1..1024 on every axis");
-    if ((int64_t)res[0] * res[1] * res[2] >= ((int64_t)1 << 31)) return fail(c, NWE_ERR_INVALID, "occupancy: the grid must have fewer than 2^31 cells");
-    return NWE_OK;
-}
-
 // Makes `words` (host, occ_words(cells) of them) the context's grid.  The bits behind the last cell are cleared; on a device
 // context the words and the descriptor go to the context's own buffers, which no launch reads any more (the caller has waited).
-int install_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* res, std::vector<uint32_t>&& words) {
+int install_occupancy(nwe_ctx* c, const GridBox& box, std::vector<uint32_t>&& words) {
     Occupancy g;
-    g.cells = (int64_t)res[0] * res[1] * res[2];
-    for (int i = 0; i < 3; ++i) {
-        g.lo[i] = lo[i]; g.hi[i] = hi[i]; g.res[i] = res[i];
-        g.inv[i] = (float)res[i] / (hi[i] - lo[i]);   // fp32, once: what the kernels multiply by (nwe_get_occupancy reports it)
-    }
-    if (g.cells & 31) words.back() &= (1u << (g.cells & 31)) - 1u;
+    g.box = box;
+    if (box.cells & 31) words.back() &= (1u << (box.cells & 31)) - 1u;
     for (const uint32_t w : words) g.occupied += __builtin_popcount(w);
     g.bits = std::move(words);
     if (!c->host_only) {
@@ -828,7 +705,7 @@ int install_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* r
         HIPCHK(c, c->d_occ.reserve(1));
         HIPCHK(c, hipMemcpy(c->d_occ_bits.get(), g.bits.data(), g.bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         OccGrid d = {};
-        for (int i = 0; i < 3; ++i) { d.lo[i] = g.lo[i]; d.inv[i] = g.inv[i]; d.res[i] = g.res[i]; }
+        for (int i = 0; i < 3; ++i) { d.lo[i] = box.lo[i]; d.inv[i] = box.inv[i]; d.res[i] = box.res[i]; }
         d.bits = c->d_occ_bits.get();
         HIPCHK(c, hipMemcpy(c->d_occ.get(), &d, sizeof(d), hipMemcpyHostToDevice));
     }
@@ -839,35 +716,70 @@ int install_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* r
 
 // ---- coarse density grid (nwe_set_coarse_grid, nwe_bake_coarse_grid) ----
 
-// The refusals nwe_set_coarse_grid and nwe_bake_coarse_grid share, by name: null pointers, a box that is not finite or not
-// lo < hi on every axis (or so thin that the fp32 inv is not finite), a resolution outside 1 .. 512 per axis.
-int check_coarse_grid_box(nwe_ctx* c, const float* lo, const float* hi, const int* res) {
-    if (!c) return NWE_ERR_INVALID;
-    if (!lo || !hi || !res) return fail(c, NWE_ERR_INVALID, "coarse grid: null lo, hi or resolution");
-    for (int i = 0; i < 3; ++i) {
-        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !std::isfinite(hi[i] - lo[i]))
-            return fail(c, NWE_ERR_INVALID, "coarse grid: the box must be finite");
-        if (!(lo[i] < hi[i])) return fail(c, NWE_ERR_INVALID, "coarse grid: the box must have lo < hi on every axis");
-    }
-    for (int i = 0; i < 3; ++i)
-        if (res[i] < 1 || res[i] > 512) return fail(c, NWE_ERR_INVALID, "coarse grid: the resolution must be in 1..512 on every axis");
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite((float)res[i] / (hi[i] - lo[i])))
-            return fail(c, NWE_ERR_INVALID, "coarse grid: the box must be finite (resolution / (hi - lo) is not, in fp32)");
-    return NWE_OK;
-}
-
 // The box, the resolution and inv of a new grid; the values are in place (d_cgrid or g.host) when this is called.
-void install_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, std::vector<float>&& host) {
+void install_coarse_grid(nwe_ctx* c, const GridBox& box, std::vector<float>&& host) {
     CoarseGridState g;
-    g.cells = (int64_t)res[0] * res[1] * res[2];
-    for (int i = 0; i < 3; ++i) {
-        g.lo[i] = lo[i]; g.hi[i] = hi[i]; g.res[i] = res[i];
-        g.inv[i] = (float)res[i] / (hi[i] - lo[i]);   // fp32, once: what the kernel multiplies by (nwe_get_coarse_grid reports it)
-    }
+    g.box = box;
     g.host = std::move(host);
     g.set = true;
     c->cgrid = std::move(g);
+}
+
+// ---- the probe lattice of a box: what nwe_build_occupancy asks the networks at, and - probes = 1, the cells' centres - what
+// nwe_bake_coarse_grid does ----
+
+struct Lattice {
+    OccBuild b;
+    int per_cell;       // probes^3
+    int chunk_cells;    // the cells whose probes go through the scratch buffer at a time: 2^20 points at the most
+};
+
+Lattice probe_lattice(const GridBox& box, int probes) {
+    Lattice l = {};
+    for (int i = 0; i < 3; ++i) {
+        l.b.lo[i] = box.lo[i]; l.b.res[i] = box.res[i];
+        l.b.step[i] = (float)(((double)box.hi[i] - (double)box.lo[i]) / (double)box.res[i]);
+    }
+    l.b.probes = probes;
+    l.per_cell = probes * probes * probes;
+    l.chunk_cells = (int)std::min<int64_t>(box.cells, std::max(1, (1 << 20) / l.per_cell));
+    return l;
+}
+
+// Chunk by chunk on `stream`: the probe points of the chunk's cells into `points`, network n's sigma at them - the sigma-only
+// query of nwe_query_points: no directions, the density trunk alone where it is built - to where sigma_of(first cell) says, then
+// done(sigma, first cell, cells), which queues what the caller makes of them.
+template <class SigmaOf, class Done>
+int query_lattice(nwe_ctx* c, const NetState& n, const Lattice& l, int64_t cells, float* points, int precision, hipStream_t stream,
+                  SigmaOf&& sigma_of, Done&& done) {
+    for (int64_t first = 0; first < cells; first += l.chunk_cells) {
+        const int count = (int)std::min<int64_t>(l.chunk_cells, cells - first);
+        launch_occ_probe_points(l.b, first, count, points, stream);
+        QueryArgs q = {};
+        q.points = points; q.sigma = sigma_of(first); q.n_points = count * l.per_cell; q.points_per_dir = 1; q.density_only = 1;
+        if (precision == NWE_PREC_F32) launch_query_f32(q, n.f32, c->query_steps, c->cus, stream);
+        else if (!launch_query_mfma(q, n.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
+            return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
+        done(q.sigma, first, count);
+    }
+    return NWE_OK;
+}
+
+// nwe_last_kernel_ms, nwe_last_query_ms: the time between the events of a recorded launch, or -1 and the context's error
+float elapsed_ms(nwe_ctx* c, const Slot& s, const char* who) {
+    DeviceGuard guard;
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = hipEventSynchronize(s.ev1);
+    float ms = -1.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, s.ev0, s.ev1);
+    if (e != hipSuccess) { c->err = std::string(who) + ": " + hipGetErrorString(e); (void)hipGetLastError(); return -1.f; }
+    return ms;
+}
+
+// A switch of the environment that a new context starts from (A/B timing on one library): 0 or 1, or -1 for anything else
+int env_switch(const char* name) {
+    const char* e = std::getenv(name);
+    return e && (e[0] == '0' || e[0] == '1') && !e[1] ? e[0] - '0' : -1;
 }
 
 }  // namespace
@@ -879,16 +791,12 @@ int nwe_create(nwe_ctx** out, int device) {
     nwe_ctx* c = new nwe_ctx();
     c->device = device;
     c->host_only = device < 0;
-    if (const char* e = std::getenv("NWE_WORK_QUEUE"))   // the default of a new context: A/B timing on one library
-        if ((e[0] == '0' || e[0] == '1') && !e[1]) c->work_queue = e[0] - '0';
-    if (const char* e = std::getenv("NWE_WORK_QUEUE_BACKFILL"))   // A/B timing of the queue with and without the backfill
-        if (e[0] == '0' && !e[1]) c->backfill = false;
-    if (const char* e = std::getenv("NWE_WORK_QUEUE_TAIL"))       // A/B timing of the tail path on one library
-        if ((e[0] == '0' || e[0] == '1') && !e[1]) c->tail = e[0] == '1';
-    if (const char* e = std::getenv("NWE_COLOUR_SKIP"))           // A/B timing of the hollow path on one library
-        if ((e[0] == '0' || e[0] == '1') && !e[1]) c->colour_skip = e[0] - '0';
-    if (const char* e = std::getenv("NWE_PACKET_BLOCKS"))         // A/B timing of the 8x4 packets on one library
-        if ((e[0] == '0' || e[0] == '1') && !e[1]) c->packet_blocks = e[0] == '1';
+    // the defaults of a new context: the queue, its backfill (which only 0 changes), its tail path, the hollow path, the 8x4 packets
+    if (const int v = env_switch("NWE_WORK_QUEUE"); v >= 0) c->work_queue = v;
+    if (env_switch("NWE_WORK_QUEUE_BACKFILL") == 0) c->backfill = false;
+    if (const int v = env_switch("NWE_WORK_QUEUE_TAIL"); v >= 0) c->tail = v == 1;
+    if (const int v = env_switch("NWE_COLOUR_SKIP"); v >= 0) c->colour_skip = v;
+    if (const int v = env_switch("NWE_PACKET_BLOCKS"); v >= 0) c->packet_blocks = v == 1;
     if (!c->host_only) {
         const hipError_t e = hipSetDevice(device);
         if (e != hipSuccess) { delete c; return fail(nullptr, NWE_ERR_HIP, std::string("nwe_create: ") + hipGetErrorString(e)); }
@@ -915,26 +823,19 @@ const char* nwe_last_error(const nwe_ctx* c) { return c ? c->err.c_str() : g_cre
 
 int nwe_set_network(nwe_ctx* c, int which, int depth, int width, int in_xyz, int in_dir, int skip_layer,
                     const float* const* w, const float* const* b) {
-    TRY(check_network_head(c, which, depth, width, w, b));
-    if (in_xyz < 3 || in_xyz > 93 || (in_xyz - 3) % 6 || in_dir < 3 || in_dir > 63 || (in_dir - 3) % 6)
-        return fail(c, NWE_ERR_UNSUPPORTED, "encoded widths must be 3 + 6*num_freqs (xyz <= 93, dir <= 63)");
+    CHECK(c, check_network(!c || !w || !b, which, depth, width, in_xyz, in_dir, 0, true, w, b));
     return set_network(c, which, NetShape{depth, width, in_xyz, in_dir, skip_layer, 0}, w, b);
 }
 
 int nwe_set_network_no_view_dirs(nwe_ctx* c, int which, int depth, int width, int in_xyz, int skip_layer, int output_ch,
                                  const float* const* w, const float* const* b) {
-    TRY(check_network_head(c, which, depth, width, w, b));
-    if (in_xyz < 3 || in_xyz > 93 || (in_xyz - 3) % 6) return fail(c, NWE_ERR_UNSUPPORTED, "encoded width must be 3 + 6*num_freqs (<= 93)");
-    if (output_ch < 4 || output_ch > 256) return fail(c, NWE_ERR_UNSUPPORTED, "output_ch must be in 4..256 (rgb_raw, sigma_raw, ignored rest)");
+    CHECK(c, check_network(!c || !w || !b, which, depth, width, in_xyz, 0, output_ch, false, w, b));
     return set_network(c, which, NetShape{depth, width, in_xyz, 0, skip_layer, output_ch}, w, b);
 }
 
 int nwe_set_sampling(nwe_ctx* c, const float* t_vals, const float* one_minus_t, int n_samples, const float* u,
                      int n_importance) {
-    if (!c || !t_vals || !one_minus_t) return fail(c, NWE_ERR_INVALID, "null argument");
-    if (n_samples < 2 || n_samples > kMaxSamples) return fail(c, NWE_ERR_UNSUPPORTED, "n_samples must be in 2..128");
-    if (n_importance < 0 || n_importance > kMaxImportance) return fail(c, NWE_ERR_UNSUPPORTED, "n_importance must be in 0..256");
-    if (n_importance > 0 && (!u || n_samples < 3)) return fail(c, NWE_ERR_INVALID, "importance sampling needs u and n_samples >= 3");
+    CHECK(c, check_sampling(!c, t_vals, one_minus_t, n_samples, u, n_importance));
     c->ns = n_samples; c->ni = n_importance;
     if (c->host_only) return NWE_OK;
     ON_DEVICE(c);
@@ -960,7 +861,7 @@ int nwe_render_tiled(nwe_ctx* const* ctxs, int n_ctx, const float* c2w, int n_po
     for (int i = 0; i < n_ctx; ++i)
         if (!ctxs[i] || ctxs[i]->host_only) return fail(c0, NWE_ERR_INVALID, "nwe_render_tiled: null or host-only context");
     Camera m{c2w, n_poses, H, W, fx, fy, cx, cy, near, far, 0, H};
-    TRY(check_camera(c0, m, "bad pose / image"));
+    CHECK(c0, check_camera(m, kCameraOfTiled));
     m.row_end = 0;   // from here on the rows of one tile
     hipStream_t stream0 = (hipStream_t)stream_;
     DeviceGuard guard;
@@ -994,10 +895,10 @@ int nwe_render_tiled(nwe_ctx* const* ctxs, int n_ctx, const float* c2w, int n_po
 
 int nwe_create_rays(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near,
                     float far, int row_begin, int row_end, float* rays_out_dev, void* stream_) {
-    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
+    CHECK(c, check_on_device(c && !c->host_only));
     const Camera m{c2w, n_poses, H, W, fx, fy, cx, cy, near, far, row_begin, row_end};
     if (!rays_out_dev) return fail(c, NWE_ERR_INVALID, "bad pose / image / row range");   // no output: the refusal of no poses
-    TRY(check_camera(c, m, "bad pose / image / row range", "far < near: nwe_render_rays needs near <= far on every ray"));
+    CHECK(c, check_camera(m, kCameraOfCreateRays));
     hipStream_t stream = (hipStream_t)stream_;
     ON_DEVICE(c);
     Slot& slot = c->rays_slot;   // not a slot of the ring: nwe_last_kernel_ms / _launch_parts keep describing the last render
@@ -1013,26 +914,8 @@ int nwe_create_rays(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, flo
 
 int nwe_query_points(nwe_ctx* c, int which, const float* points_dev, int64_t n_points, const float* dirs_dev, int64_t points_per_dir,
                      int precision, const nwe_point_outputs* out, void* stream_) {
-    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
-    if (!out) return fail(c, NWE_ERR_INVALID, "null outputs");
-    if (out->struct_bytes != sizeof(nwe_point_outputs))
-        return fail(c, NWE_ERR_INVALID, "nwe_point_outputs.struct_bytes != sizeof(nwe_point_outputs): the caller was built against another version of include/nwe.h");
-    if (which != NWE_NET_COARSE && which != NWE_NET_FINE) return fail(c, NWE_ERR_INVALID, "which must be 0 or 1");
-    if (n_points < 0 || n_points > INT32_MAX) return fail(c, NWE_ERR_INVALID, "bad n_points (negative, or more than 2^31 - 1)");
-    if (points_per_dir < 1) return fail(c, NWE_ERR_INVALID, "points_per_dir must be at least 1");
-    if (!points_dev && n_points > 0) return fail(c, NWE_ERR_INVALID, "null points");
-    if (!out->raw && !out->sigma) return fail(c, NWE_ERR_INVALID, "neither raw nor sigma requested");
-    if (precision != NWE_PREC_F16X3 && precision != NWE_PREC_F16X1 && precision != NWE_PREC_F32)
-        return fail(c, NWE_ERR_INVALID, "unknown precision");
+    CHECK(c, check_query(MaybeContext(c).p, which, points_dev, n_points, dirs_dev, points_per_dir, precision, out));
     const NetState& net = c->net[which];
-    if (!net.set) return fail(c, NWE_ERR_STATE, which == NWE_NET_COARSE ? "coarse network not set" : "fine network not set");
-    if (net.in_dir == 0 && dirs_dev)
-        return fail(c, NWE_ERR_INVALID, "the network takes no view directions (nwe_set_network_no_view_dirs): dirs_dev must be null");
-    if (net.in_dir != 0 && !dirs_dev && out->raw)
-        return fail(c, NWE_ERR_INVALID, "raw output of a network with view directions needs dirs_dev (only sigma does not depend on the direction)");
-    if (precision != NWE_PREC_F32 && !net.mfma_ok)
-        return fail(c, NWE_ERR_UNSUPPORTED,
-                    "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
     if (n_points == 0) return NWE_OK;
     hipStream_t stream = (hipStream_t)stream_;
     ON_DEVICE(c);
@@ -1056,22 +939,16 @@ int nwe_query_points(nwe_ctx* c, int which, const float* points_dev, int64_t n_p
 
 float nwe_last_query_ms(nwe_ctx* c) {
     if (!c || c->host_only || c->last_query < 0 || !c->query_slots[c->last_query].used) return -1.f;
-    const Slot& s = c->query_slots[c->last_query];
-    DeviceGuard guard;
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipEventSynchronize(s.ev1);
-    float ms = -1.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, s.ev0, s.ev1);
-    if (e != hipSuccess) { c->err = std::string("nwe_last_query_ms: ") + hipGetErrorString(e); (void)hipGetLastError(); return -1.f; }
-    return ms;
+    return elapsed_ms(c, c->query_slots[c->last_query], "nwe_last_query_ms");
 }
 
 int nwe_debug_set_query_steps(nwe_ctx* c, int steps) { return set_on(steps < 0 || steps > kQueryMaxSteps ? nullptr : c, [&] { c->query_steps = steps; }); }
 
 int nwe_render_rays(nwe_ctx* c, const float* rays_dev, int64_t n_rays, int precision, const nwe_outputs* out, void* stream) {
     HookReset hooks{c};   // every return below, refusals included, consumes the one-shot hooks
-    TRY(check_ready(c, out, precision, false));
-    if (n_rays < 0 || n_rays > INT32_MAX || (!rays_dev && n_rays > 0)) return fail(c, NWE_ERR_INVALID, "bad rays (null, or more than 2^31 - 1)");
+    const MaybeContext desc(c);
+    CHECK(c, check_ready(desc.p, out, precision, false));
+    CHECK(c, check_ray_count(n_rays, true, !rays_dev));
     if (n_rays == 0) return NWE_OK;
     ON_DEVICE(c);
     RenderSlot& slot = c->slots[c->next_slot];
@@ -1082,7 +959,7 @@ int nwe_render_rays(nwe_ctx* c, const float* rays_dev, int64_t n_rays, int preci
     a.z_fine_in = c->dbg_z_fine; a.raw_in_c = c->dbg_raw_c; a.raw_in_f = c->dbg_raw_f; a.w_in = c->dbg_w;
     a.t_rand = c->trn_t; a.noise_c = c->trn_nc; a.noise_f = c->trn_nf; a.u_rand = c->trn_u;
     a.out = *out;
-    return launch(c, slot, a, precision, (hipStream_t)stream);
+    return launch(c, desc.d, slot, a, precision, (hipStream_t)stream);
 }
 
 int nwe_to8b(nwe_ctx* c, const float* rgb_dev, uint8_t* out_dev, int64_t n, void* stream) {
@@ -1096,14 +973,7 @@ int nwe_to8b(nwe_ctx* c, const float* rgb_dev, uint8_t* out_dev, int64_t n, void
 
 float nwe_last_kernel_ms(nwe_ctx* c) {
     const RenderSlot* s = c ? last_render(c) : nullptr;
-    if (!s) return -1.f;
-    DeviceGuard guard;
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipEventSynchronize(s->ev1);
-    float ms = -1.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, s->ev0, s->ev1);
-    if (e != hipSuccess) { c->err = std::string("nwe_last_kernel_ms: ") + hipGetErrorString(e); (void)hipGetLastError(); return -1.f; }
-    return ms;
+    return s ? elapsed_ms(c, *s, "nwe_last_kernel_ms") : -1.f;
 }
 
 int nwe_last_launch_parts(nwe_ctx* c, float* ms2, int64_t* rays2) {
@@ -1188,7 +1058,8 @@ unsigned nwe_debug_queue_grid(unsigned items) { return queue_grid(items); }
 int nwe_debug_plan(nwe_ctx* c, int n_poses, int H, int W, int row_begin, int row_end, int64_t n_rays, const nwe_outputs* out,
                    unsigned hooks, int precision, int cus, nwe_plan_report* report) {
     const bool pinhole = n_rays < 0;
-    TRY(check_ready(c, out, precision, pinhole, true));
+    const MaybeContext desc(c);
+    CHECK(c, check_ready(desc.p, out, precision, pinhole, true));
     if (!report || report->struct_bytes != sizeof(nwe_plan_report))
         return fail(c, NWE_ERR_INVALID, "nwe_plan_report.struct_bytes != sizeof(nwe_plan_report): the caller was built against another version of include/nwe.h");
     if (cus < 1) return fail(c, NWE_ERR_INVALID, "cus must be at least 1");
@@ -1198,19 +1069,18 @@ int nwe_debug_plan(nwe_ctx* c, int n_poses, int H, int W, int row_begin, int row
     RenderArgs a = {};
     if (pinhole) {
         const Camera m{&somewhere, n_poses, H, W, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f, row_begin, row_end};
-        TRY(check_camera(c, m));
+        CHECK(c, check_camera(m));
         a = camera_args(m, &somewhere);
-        if (a.n_rays > INT32_MAX) return fail(c, NWE_ERR_INVALID, "more than 2^31 - 1 rays in one call");
     } else {
-        if (n_rays > INT32_MAX) return fail(c, NWE_ERR_INVALID, "bad rays (null, or more than 2^31 - 1)");
         a.rays = &somewhere; a.n_rays = n_rays; a.W = 1; a.rows = 1;
         if (hooks & NWE_PLAN_HOOK_COARSE_WEIGHTS) a.w_in = &somewhere;
         if (hooks & NWE_PLAN_HOOK_OTHER) a.z_fine_in = &somewhere;
     }
+    CHECK(c, check_ray_count(a.n_rays, !pinhole));
     a.out = *out;
     context_args(c, a);
     if (a.n_rays <= 0) return NWE_OK;   // the call launches nothing
-    const CallPlan p = plan_call(describe_call(c, a, precision), cus);
+    const CallPlan p = plan_call(describe_call(desc.d, a, precision), cus);
     c->last_packet_blocks = p.blocks ? 1 : 0;
     report->separate = p.separate; report->share = p.share; report->full = p.full; report->coarse_launch = p.coarse_launch;
     report->may_queue = p.may_queue; report->need_side = p.need_side; report->need_evals = p.need_evals;
@@ -1275,39 +1145,39 @@ int nwe_debug_set_stamps(nwe_ctx* c, unsigned long long* per_wave_dev) { return 
 int nwe_set_white_background(nwe_ctx* c, int on) { return set_on(c, [&] { c->white_bkgd = on ? 1 : 0; }); }
 int nwe_set_early_termination(nwe_ctx* c, float min_transmittance) {
     if (!c) return NWE_ERR_INVALID;
-    if (!(min_transmittance >= 0.f && min_transmittance < 1.f)) return fail(c, NWE_ERR_INVALID, "min_transmittance must be in [0, 1) (0 = off)");
+    CHECK(c, check_early_termination(min_transmittance));
     c->min_trans = min_transmittance > 0.f ? min_transmittance : 0.f;
     return NWE_OK;
 }
 float nwe_get_early_termination(const nwe_ctx* c) { return c ? c->min_trans : -1.f; }
 int nwe_set_shared_coarse(nwe_ctx* c, int k) {
     if (!c) return NWE_ERR_INVALID;
-    if (k < 1 || k > 16) return fail(c, NWE_ERR_INVALID, "shared_coarse k must be in 1..16 (1 = off)");
+    CHECK(c, check_shared_coarse(k));
     c->share_k = k;
     return NWE_OK;
 }
 int nwe_get_shared_coarse(const nwe_ctx* c) { return c ? c->share_k : -1; }
 int nwe_set_separate_passes(nwe_ctx* c, int on) {
     if (!c) return NWE_ERR_INVALID;
-    if (on != 0 && on != 1) return fail(c, NWE_ERR_INVALID, "separate_passes must be 0 or 1 (0 = off)");
+    CHECK(c, check_separate_passes(on));
     c->separate = on;
     return NWE_OK;
 }
 int nwe_get_separate_passes(const nwe_ctx* c) { return c ? c->separate : -1; }
 int nwe_set_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* res, const uint32_t* bits, int bits_on_device) {
-    TRY(check_occupancy_box(c, lo, hi, res));
-    if (!bits) return fail(c, NWE_ERR_INVALID, "occupancy: null bits");
-    if (bits_on_device && c->host_only) return fail(c, NWE_ERR_INVALID, "occupancy: a host-only context takes its bits from the host");
-    std::vector<uint32_t> words((size_t)occ_words((int64_t)res[0] * res[1] * res[2]));
+    if (!c) return NWE_ERR_INVALID;
+    CHECK(c, check_set_grid(kOccupancyGrid, lo, hi, res, bits, bits_on_device != 0, c->host_only));
+    const GridBox box(lo, hi, res);
+    std::vector<uint32_t> words((size_t)occ_words(box.cells));
     if (c->host_only) {
         std::memcpy(words.data(), bits, words.size() * sizeof(uint32_t));
-        return install_occupancy(c, lo, hi, res, std::move(words));
+        return install_occupancy(c, box, std::move(words));
     }
     ON_DEVICE(c);
     TRY(wait_for_launches(c));   // a queued launch still reads the old grid
     if (bits_on_device) HIPCHK(c, hipMemcpy(words.data(), bits, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     else std::memcpy(words.data(), bits, words.size() * sizeof(uint32_t));
-    return install_occupancy(c, lo, hi, res, std::move(words));
+    return install_occupancy(c, box, std::move(words));
 }
 
 int nwe_clear_occupancy(nwe_ctx* c) {
@@ -1322,15 +1192,9 @@ int nwe_clear_occupancy(nwe_ctx* c) {
 
 int nwe_get_occupancy(const nwe_ctx* c, float* lo, float* hi, int* res, float* inv, int64_t* occupied_cells) {
     if (!c) return NWE_ERR_INVALID;
-    const Occupancy& g = c->occ;
-    if (!g.set) return NWE_ERR_STATE;   // no grid is set: the outputs stay untouched (and so does the error text of a const context)
-    for (int i = 0; i < 3; ++i) {
-        if (lo) lo[i] = g.lo[i];
-        if (hi) hi[i] = g.hi[i];
-        if (res) res[i] = g.res[i];
-        if (inv) inv[i] = g.inv[i];
-    }
-    if (occupied_cells) *occupied_cells = g.occupied;
+    if (!c->occ.set) return NWE_ERR_STATE;   // no grid is set: the outputs stay untouched (and so does the error text of a const context)
+    c->occ.box.read(lo, hi, res, inv);
+    if (occupied_cells) *occupied_cells = c->occ.occupied;
     return NWE_OK;
 }
 
@@ -1342,51 +1206,25 @@ int nwe_occupancy_copy(const nwe_ctx* c, uint32_t* host_words, int64_t n_words) 
 
 int nwe_build_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int* res, int probes, float threshold, int dilate,
                         int precision, void* stream_) {
-    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
-    TRY(check_occupancy_box(c, lo, hi, res));
-    if (probes < 1 || probes > 4) return fail(c, NWE_ERR_INVALID, "occupancy: probes must be in 1..4");
-    if (dilate < 0 || dilate > 2) return fail(c, NWE_ERR_INVALID, "occupancy: dilate must be in 0..2");
-    if (threshold != threshold) return fail(c, NWE_ERR_INVALID, "occupancy: the threshold must not be NaN");
-    if (precision != NWE_PREC_F16X3 && precision != NWE_PREC_F16X1 && precision != NWE_PREC_F32)
-        return fail(c, NWE_ERR_INVALID, "unknown precision");
-    if (!c->net[0].set && !c->net[1].set) return fail(c, NWE_ERR_STATE, "occupancy: no network is set");
-    for (const NetState& n : c->net)
-        if (n.set && precision != NWE_PREC_F32 && !n.mfma_ok)
-            return fail(c, NWE_ERR_UNSUPPORTED,
-                        "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
+    CHECK(c, check_build_occupancy(MaybeContext(c).p, lo, hi, res, probes, threshold, dilate, precision));
     hipStream_t stream = (hipStream_t)stream_;
     ON_DEVICE(c);
     TRY(wait_for_launches(c));   // the build ends in a new grid: a queued launch still reads the old one
-    OccBuild b = {};
-    for (int i = 0; i < 3; ++i) {
-        b.lo[i] = lo[i]; b.res[i] = res[i];
-        b.step[i] = (float)(((double)hi[i] - (double)lo[i]) / (double)res[i]);
-    }
-    b.probes = probes;
-    const int per_cell = probes * probes * probes;
-    const int64_t cells = (int64_t)res[0] * res[1] * res[2], words = occ_words(cells);
+    const GridBox box(lo, hi, res);
+    const Lattice l = probe_lattice(box, probes);
+    const int64_t words = occ_words(box.cells);
     // the probes of a chunk of cells and their sigma in a scratch buffer the context keeps: 2^20 points (16 MB) at the most
-    const int chunk_cells = (int)std::min<int64_t>(cells, std::max(1, (1 << 20) / per_cell));
-    HIPCHK(c, c->d_occ_scratch.reserve((size_t)chunk_cells * per_cell * 4));
+    HIPCHK(c, c->d_occ_scratch.reserve((size_t)l.chunk_cells * l.per_cell * 4));
     HIPCHK(c, c->d_occ_tmp.reserve((size_t)words * 2));
     float* points = c->d_occ_scratch.get();
-    float* sigma = points + (size_t)chunk_cells * per_cell * 3;
+    float* sigma = points + (size_t)l.chunk_cells * l.per_cell * 3;
     uint32_t* buf[2] = {c->d_occ_tmp.get(), c->d_occ_tmp.get() + words};
     HIPCHK(c, hipMemsetAsync(buf[0], 0, (size_t)words * sizeof(uint32_t), stream));
-    for (const NetState& n : c->net) {
-        if (!n.set) continue;
-        for (int64_t first = 0; first < cells; first += chunk_cells) {
-            const int count = (int)std::min<int64_t>(chunk_cells, cells - first);
-            const int64_t n_points = (int64_t)count * per_cell;
-            launch_occ_probe_points(b, first, count, points, stream);
-            QueryArgs q = {};   // the sigma-only query of nwe_query_points: no directions, the density trunk alone where it is built
-            q.points = points; q.sigma = sigma; q.n_points = (int)n_points; q.points_per_dir = 1; q.density_only = 1;
-            if (precision == NWE_PREC_F32) launch_query_f32(q, n.f32, c->query_steps, c->cus, stream);
-            else if (!launch_query_mfma(q, n.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
-                return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
-            launch_occ_reduce_bits(sigma, first, count, per_cell, threshold, buf[0], stream);
-        }
-    }
+    for (const NetState& n : c->net)   // a cell is occupied where either network says so
+        if (n.set)
+            TRY(query_lattice(c, n, l, box.cells, points, precision, stream, [&](int64_t) { return sigma; }, [&](const float* s, int64_t first, int count) {
+                launch_occ_reduce_bits(s, first, count, l.per_cell, threshold, buf[0], stream);
+            }));
     int cur = 0;
     for (int d = 0; d < dilate; ++d, cur ^= 1)
         launch_occ_dilate(buf[cur], buf[cur ^ 1], res, stream);
@@ -1394,16 +1232,16 @@ int nwe_build_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int*
     std::vector<uint32_t> host((size_t)words);
     HIPCHK(c, hipMemcpyAsync(host.data(), buf[cur], (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIPCHK(c, hipStreamSynchronize(stream));
-    return install_occupancy(c, lo, hi, res, std::move(host));
+    return install_occupancy(c, box, std::move(host));
 }
 
 int nwe_set_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, const float* sigma, int on_device) {
-    TRY(check_coarse_grid_box(c, lo, hi, res));
-    if (!sigma) return fail(c, NWE_ERR_INVALID, "coarse grid: null sigma");
-    if (on_device && c->host_only) return fail(c, NWE_ERR_INVALID, "coarse grid: a host-only context takes its values from the host");
-    const size_t cells = (size_t)res[0] * res[1] * res[2];
+    if (!c) return NWE_ERR_INVALID;
+    CHECK(c, check_set_grid(kCoarseGrid, lo, hi, res, sigma, on_device != 0, c->host_only));
+    const GridBox box(lo, hi, res);
+    const size_t cells = (size_t)box.cells;
     if (c->host_only) {
-        install_coarse_grid(c, lo, hi, res, std::vector<float>(sigma, sigma + cells));
+        install_coarse_grid(c, box, std::vector<float>(sigma, sigma + cells));
         return NWE_OK;
     }
     ON_DEVICE(c);
@@ -1411,7 +1249,7 @@ int nwe_set_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int*
     c->cgrid = CoarseGridState{};   // a failing upload leaves no grid rather than the old box over new values
     HIPCHK(c, c->d_cgrid.reserve(cells));
     HIPCHK(c, hipMemcpy(c->d_cgrid.get(), sigma, cells * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    install_coarse_grid(c, lo, hi, res, {});
+    install_coarse_grid(c, box, {});
     return NWE_OK;
 }
 
@@ -1427,21 +1265,15 @@ int nwe_clear_coarse_grid(nwe_ctx* c) {
 
 int nwe_get_coarse_grid(const nwe_ctx* c, float* lo, float* hi, int* res, float* inv) {
     if (!c) return NWE_ERR_INVALID;
-    const CoarseGridState& g = c->cgrid;
-    if (!g.set) return NWE_ERR_STATE;   // no grid is set: the outputs stay untouched (and so does the error text of a const context)
-    for (int i = 0; i < 3; ++i) {
-        if (lo) lo[i] = g.lo[i];
-        if (hi) hi[i] = g.hi[i];
-        if (res) res[i] = g.res[i];
-        if (inv) inv[i] = g.inv[i];
-    }
+    if (!c->cgrid.set) return NWE_ERR_STATE;   // no grid is set: the outputs stay untouched (and so does the error text of a const context)
+    c->cgrid.box.read(lo, hi, res, inv);
     return NWE_OK;
 }
 
 int nwe_coarse_grid_copy(nwe_ctx* c, float* host_values, int64_t n_values) {
     if (!c) return NWE_ERR_INVALID;
     if (!c->cgrid.set) return NWE_ERR_STATE;
-    if (!host_values || n_values != c->cgrid.cells) return fail(c, NWE_ERR_INVALID, "coarse grid: the copy needs rx * ry * rz values");
+    if (!host_values || n_values != c->cgrid.box.cells) return fail(c, NWE_ERR_INVALID, "coarse grid: the copy needs rx * ry * rz values");
     if (c->host_only) return copy_out(&c->cgrid.host, host_values, n_values);
     ON_DEVICE(c);
     HIPCHK(c, hipMemcpy(host_values, c->d_cgrid.get(), (size_t)n_values * sizeof(float), hipMemcpyDeviceToHost));
@@ -1449,59 +1281,38 @@ int nwe_coarse_grid_copy(nwe_ctx* c, float* host_values, int64_t n_values) {
 }
 
 int nwe_bake_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, int precision, void* stream_) {
-    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
-    TRY(check_coarse_grid_box(c, lo, hi, res));
-    if (precision != NWE_PREC_F16X3 && precision != NWE_PREC_F16X1 && precision != NWE_PREC_F32)
-        return fail(c, NWE_ERR_INVALID, "unknown precision");
-    const NetState& n = c->net[NWE_NET_COARSE];
-    if (!n.set) return fail(c, NWE_ERR_STATE, "coarse grid: the coarse network is not set");
-    if (precision != NWE_PREC_F32 && !n.mfma_ok)
-        return fail(c, NWE_ERR_UNSUPPORTED,
-                    "no MFMA kernel for this network shape (have widths 128 and 256 with depth 6 or 8 and the skip after layer 4, or depth 4 without, 63 + 27 or, without view directions, 63 inputs); use NWE_PREC_F32");
+    CHECK(c, check_bake_coarse_grid(MaybeContext(c).p, lo, hi, res, precision));
     hipStream_t stream = (hipStream_t)stream_;
     ON_DEVICE(c);
     TRY(wait_for_launches(c));   // the bake ends in a new grid: a queued launch still reads the old one
     c->cgrid = CoarseGridState{};   // a failing bake leaves no grid
-    OccBuild b = {};   // the probes = 1 lattice of nwe_build_occupancy: the cells' centres
-    for (int i = 0; i < 3; ++i) {
-        b.lo[i] = lo[i]; b.res[i] = res[i];
-        b.step[i] = (float)(((double)hi[i] - (double)lo[i]) / (double)res[i]);
-    }
-    b.probes = 1;
-    const int64_t cells = (int64_t)res[0] * res[1] * res[2];
-    const int chunk_cells = (int)std::min<int64_t>(cells, 1 << 20);   // the centres of a chunk in the scratch buffer: 12 MB at the most
-    HIPCHK(c, c->d_occ_scratch.reserve((size_t)chunk_cells * 3));
-    HIPCHK(c, c->d_cgrid.reserve((size_t)cells));
-    float* points = c->d_occ_scratch.get();
-    for (int64_t first = 0; first < cells; first += chunk_cells) {
-        const int count = (int)std::min<int64_t>(chunk_cells, cells - first);
-        launch_occ_probe_points(b, first, count, points, stream);
-        QueryArgs q = {};   // the sigma-only query of nwe_query_points, straight into the grid
-        q.points = points; q.sigma = c->d_cgrid.get() + first; q.n_points = count; q.points_per_dir = 1; q.density_only = 1;
-        if (precision == NWE_PREC_F32) launch_query_f32(q, n.f32, c->query_steps, c->cus, stream);
-        else if (!launch_query_mfma(q, n.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
-            return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
-    }
+    const GridBox box(lo, hi, res);
+    const Lattice l = probe_lattice(box, 1);   // the cells' centres, a chunk of them in the scratch buffer: 12 MB at the most
+    HIPCHK(c, c->d_occ_scratch.reserve((size_t)l.chunk_cells * 3));
+    HIPCHK(c, c->d_cgrid.reserve((size_t)box.cells));
+    float* grid = c->d_cgrid.get();   // the sigma of a chunk goes straight into the grid
+    TRY(query_lattice(c, c->net[NWE_NET_COARSE], l, box.cells, c->d_occ_scratch.get(), precision, stream,
+                      [&](int64_t first) { return grid + first; }, [](const float*, int64_t, int) {}));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(stream));
-    install_coarse_grid(c, lo, hi, res, {});
+    install_coarse_grid(c, box, {});
     return NWE_OK;
 }
 
 int nwe_coarse_grid_weights(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near,
                             float far, int row_begin, int row_end, float* sigma_out_dev, float* weights_out_dev, void* stream_) {
-    if (!c || c->host_only) return fail(c, NWE_ERR_STATE, "needs a device context");
+    CHECK(c, check_on_device(c && !c->host_only));
     if (!c->cgrid.set) return fail(c, NWE_ERR_STATE, "coarse grid: no grid is set (nwe_set_coarse_grid, nwe_bake_coarse_grid)");
     if (c->ns <= 0) return fail(c, NWE_ERR_STATE, "nwe_set_sampling has not been called");
     const Camera m{c2w, n_poses, H, W, fx, fy, cx, cy, near, far, row_begin, row_end};
-    TRY(check_camera(c, m));
+    CHECK(c, check_camera(m));
     hipStream_t stream = (hipStream_t)stream_;
     ON_DEVICE(c);
     Slot& slot = c->rays_slot;   // not a slot of the ring, like nwe_create_rays: the timing calls keep describing the last render
     TRY(prepare_slot(c, slot));
     TRY(upload_poses(c, slot, c2w, n_poses, stream));
     RenderArgs a = camera_args(m, slot.poses.get());
-    if (a.n_rays > INT32_MAX) return fail(c, NWE_ERR_INVALID, "more than 2^31 - 1 rays in one call");
+    CHECK(c, check_ray_count(a.n_rays, false));
     context_args(c, a);
     if (a.n_rays == 0 || (!sigma_out_dev && !weights_out_dev)) return NWE_OK;
     return record_launch(c, slot, stream, [&]() -> int {

@@ -44,8 +44,6 @@ bool mfma_variant_built(int D, int W, int skip, int form, int variant);
 // precomputed rays, no stamps (is_lean, nwe_mfma_render.h)
 bool mfma_is_lean(const RenderArgs& a);
 
-int mfma_max_samples();      // n_samples the MFMA kernel's per-wave LDS buffers are sized for
-
 // ---- point query (nwe_query_points): run_network at arbitrary points ----
 // Kernel arguments of a query launch (by value).  n_points is below 2^31 (the ABI refuses more), points_per_dir is at least 1
 // and clamped to n_points by the launcher, so row and direction indices are 32-bit; offsets are formed in 64 bits.

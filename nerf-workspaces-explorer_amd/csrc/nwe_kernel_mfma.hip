@@ -81,8 +81,6 @@ bool mfma_variant_built(int D, int W, int skip, int form, int variant) {
 
 bool mfma_is_lean(const RenderArgs& a) { return is_lean(a); }
 
-int mfma_max_samples() { return kSplitMaxSamples; }
-
 bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& nf, bool three_pass, const PassPlan& p,
                         const LaunchResources& res, hipStream_t stream, LaunchReport* out) {
     if (!p.ok) return false;

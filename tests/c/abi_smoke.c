@@ -45,6 +45,41 @@ int main(void) {
     float t[4] = {0.f, 1.f / 3, 2.f / 3, 1.f}, omt[4] = {1.f, 2.f / 3, 1.f / 3, 0.f};
     CHECK(nwe_set_sampling(ctx, t, omt, 4, NULL, 0) == NWE_OK);
     CHECK(nwe_set_sampling(ctx, t, omt, 1, NULL, 0) == NWE_ERR_UNSUPPORTED);
+    /* refusals decided in csrc/nwe_check.cpp, by code and text: a setter's range, the grids' one box check with its two maxima, and
+     * the modes' table through nwe_debug_plan, which a host-only context serves */
+    {
+        const float lo[3] = {-1.f, -1.f, -1.f}, hi[3] = {1.f, 1.f, 1.f};
+        const int res[3] = {2, 3, 4}, res513[3] = {2, 3, 513};
+        const uint32_t bits[97] = {0xffffffu};
+        float sigma[24] = {0.f};
+        CHECK(nwe_set_coarse_grid(ctx, lo, hi, res513, sigma, 0) == NWE_ERR_INVALID);
+        CHECK(strcmp(nwe_last_error(ctx), "coarse grid: the resolution must be in 1..512 on every axis") == 0);
+        CHECK(nwe_set_occupancy(ctx, lo, hi, res513, bits, 0) == NWE_OK && nwe_clear_occupancy(ctx) == NWE_OK);   /* 3078 cells, 97 words */
+        CHECK(nwe_set_occupancy(ctx, lo, lo, res, bits, 0) == NWE_ERR_INVALID);
+        CHECK(strcmp(nwe_last_error(ctx), "occupancy: the box must have lo < hi on every axis") == 0);
+        CHECK(nwe_set_occupancy(ctx, lo, hi, res, bits, 1) == NWE_ERR_INVALID);
+        CHECK(strcmp(nwe_last_error(ctx), "occupancy: a host-only context takes its bits from the host") == 0);
+        CHECK(nwe_set_occupancy(ctx, lo, hi, res, bits, 0) == NWE_OK);
+        CHECK(nwe_set_shared_coarse(ctx, 17) == NWE_ERR_INVALID && strcmp(nwe_last_error(ctx), "shared_coarse k must be in 1..16 (1 = off)") == 0);
+        CHECK(nwe_set_shared_coarse(ctx, 2) == NWE_OK);
+        nwe_outputs lean;
+        memset(&lean, 0, sizeof lean);
+        lean.struct_bytes = sizeof lean;
+        nwe_plan_report report;
+        memset(&report, 0, sizeof report);
+        report.struct_bytes = sizeof report;
+        CHECK(nwe_debug_plan(ctx, 1, 1, 8, 0, 1, -1, &lean, 0, NWE_PREC_F16X3, 256, &report) == NWE_ERR_UNSUPPORTED);
+        CHECK(strcmp(nwe_last_error(ctx), "an occupancy grid is set (nwe_set_occupancy, 2 x 3 x 4): it is not built together with the shared coarse "
+                                          "pass (nwe_set_shared_coarse, k = 2); switch one of them off") == 0);
+        CHECK(nwe_set_shared_coarse(ctx, 1) == NWE_OK);
+        CHECK(nwe_debug_plan(ctx, 1, 1, 8, 0, 1, 8, &lean, 0, NWE_PREC_F16X3, 256, &report) == NWE_ERR_UNSUPPORTED);
+        CHECK(strcmp(nwe_last_error(ctx), "an occupancy grid is set (nwe_set_occupancy, 2 x 3 x 4): nwe_render_rays, its hooks and its training "
+                                          "tables do not read the grid; call nwe_clear_occupancy for this call") == 0);
+        CHECK(nwe_debug_plan(ctx, 1, 1, 8, 0, 1, -1, &lean, 0, NWE_PREC_F16X3, 256, &report) == NWE_OK && report.main.active);
+        CHECK(nwe_clear_occupancy(ctx) == NWE_OK);
+        CHECK(nwe_debug_plan(ctx, 1, 1, 8, 0, 1, (int64_t)1 << 31, &lean, 0, NWE_PREC_F16X3, 256, &report) == NWE_ERR_INVALID);
+        CHECK(strcmp(nwe_last_error(ctx), "bad rays (null, or more than 2^31 - 1)") == 0);
+    }
     nwe_outputs out;
     memset(&out, 0, sizeof out);
     out.struct_bytes = sizeof out;

@@ -291,11 +291,13 @@ def _dilate(bits):
 
 
 @pytest.mark.parametrize("both", [False, True], ids=["one_network", "both_networks"])
-@pytest.mark.parametrize("res,probes", [((5, 7, 9), 2), ((16, 16, 16), 1), ((5, 7, 9), 3)])
+@pytest.mark.parametrize("res,probes", [((5, 7, 9), 2), ((16, 16, 16), 1), ((5, 7, 9), 3), ((17, 31, 33), 4)])
 @pytest.mark.parametrize("precision", ["f16x3", "f32"])
 def test_build_occupancy_equals_its_numpy_restatement(precision, res, probes, both):
     """query_points sigma at the same probe points, threshold, NaN -> occupied, dilation 0 / 1 / 2: exact, since a query row
-    depends on its point alone.  The threshold is the median of the cells' largest sigma, so that both kinds of cell exist."""
+    depends on its point alone.  The threshold is the median of the cells' largest sigma, so that both kinds of cell exist.
+    17 x 31 x 33 at probes 4: 17 391 cells of 64 probes, which the build walks as one full chunk of 16 384 cells (2^20 points) and
+    a ragged one of 1 007."""
     sd_c, sd_f, cfg = G.scene("fog192")[:3]
     sd_f = dict(sd_f)
     r = nwe_amd.Renderer(0)
