@@ -558,6 +558,90 @@ int nwe_coarse_grid_weights(nwe_ctx *ctx, const float *c2w, int n_poses, int H, 
                             float near, float far, int row_begin, int row_end, float *sigma_out_dev, float *weights_out_dev,
                             void *stream);
 
+/* Radiance grid, opt-in: a context may hold ONE radiance grid; none (the default) changes nothing.  A grid is an axis-aligned box
+ * lo[3] < hi[3] in world coordinates, a resolution res = (rx, ry, rz), each axis 1..512, and rx * ry * rz rows of four fp32 values
+ * (rgb_raw[3], sigma_raw) - the network's raw output, before the sigmoid and the ReLU - at the cell centres, in the layout of a
+ * [rx, ry, rz, 4] array, z fastest and the four channels innermost: what handler.run_network returns at handler.grid_centres.
+ * Why: a preview frame without the networks.  nwe_render_grid renders a frame by running the reference pipeline with run_network
+ * replaced by a trilinear lookup in BOTH passes: no MFMA, no weight stream, a kernel bound by its gathers.  It is an entry point of
+ * its own: it reads none of the modes, and nwe_render, nwe_render_rays, nwe_debug_plan and nwe_plan_report neither read the grid
+ * nor refuse because of it.
+ * The rule of nwe_render_grid, for each ray and each sample of EITHER pass:
+ *   - the depths and points are the ones every kernel forms: coarse near * (1 - t) + far * t from the context's tables, the
+ *     importance samples of sample_pdf on weights[1:-1], the merge of the two ascending lists, p = o + d * z, multiply then add,
+ *     before the division by 10;
+ *   - the grid coordinate, the inside test, the indices and the fraction are exactly those of the coarse grid above
+ *     (nwe_set_coarse_grid, steps 2 to 4): g_c = (p_c - lo_c) * inv_c - 0.5f in three separately rounded operations, with
+ *     inv_c = (float)r_c / (hi_c - lo_c) formed once on the host in fp32 (nwe_get_radiance_grid reports it); a point is outside when
+ *     any p_c is not finite, or g_c < -0.5f, or g_c > r_c - 0.5f; i0 = floorf(g_c), and i0 and i0 + 1 are clamped to 0 .. r_c - 1;
+ *   - INSIDE the box each of the four channels is interpolated on its own: the eight taps along z, then y, then x, each
+ *     interpolation a + (b - a) * f in three separately rounded fp32 operations, no FMA (tests/radiance_grid.py restates it in
+ *     numpy float32 to the same bits).  A non-finite grid value propagates in its channel;
+ *   - OUTSIDE the box the row is (0, 0, 0, 0);
+ *   - the row stands where run_network's row stands (nerf/models/model_utils.py:13-30): raw2outputs follows on the coarse samples,
+ *     then sample_pdf, sort and raw2outputs on the n_samples + n_importance fine samples (handler.py:203-268), all of it computed
+ *     with the device code the render kernels composite and sample with;
+ *   - with n_importance == 0 the only pass is the output, as in nwe_render;
+ *   - nwe_set_white_background is honoured.  Nothing else of the context is read: early termination, shared coarse pass, separate
+ *     passes, occupancy grid, coarse grid, decomposition, work queue, colour skip, packet blocks, stamps, the one-shot hooks and
+ *     the training tables are neither used nor cleared.
+ * So a ray's outputs depend on the ray, the grid and the sampling tables, and on nothing else: row tiles and pose batches are
+ * bit-identical to the whole call.  Flags: the rgb / depth / acc bits; the coarse bits are never raised.
+ * It is an approximation.  Its size is the trilinear error of the network's raw output at the grid's resolution, plus whatever
+ * the bake did to the view dependence: a grid holds one row per cell, so one direction, or a mean over directions, for all views.
+ * A successful nwe_set_network / nwe_set_network_no_view_dirs of EITHER network clears the grid; a refused one leaves it.  The grid
+ * calls below wait for this context's launches in flight, like nwe_set_sampling.
+ *   nwe_set_radiance_grid    copies the rows (from the host or - on_device != 0 - the context's device) into a buffer the context
+ *                            owns; a host-only context keeps them on the host.  Refused by name (NWE_ERR_INVALID): null pointers,
+ *                            a box that is not finite or not lo < hi on every axis (or so thin that inv is not finite), a
+ *                            resolution outside the domain.  If the device allocation fails (at 512^3 the grid is 2 GiB) the call
+ *                            returns NWE_ERR_HIP and no grid is left set.
+ *   nwe_clear_radiance_grid  no grid.
+ *   nwe_get_radiance_grid    the grid's box, resolution and the fp32 inv the kernel multiplies by; any pointer may be null.
+ *                            NWE_ERR_STATE (and nothing written) when no grid is set.
+ *   nwe_radiance_grid_copy   the rows, n_values = 4 * rx * ry * rz, to the host.
+ *   nwe_bake_radiance_grid   the raw output of network `which` at the cell centres (the probes = 1 arithmetic of nwe_build_occupancy
+ *                            and handler.grid_centres), through the raw path of nwe_query_points in `precision`, in chunks through
+ *                            the scratch buffer the context keeps, straight into the context's grid.  Every cell is evaluated with
+ *                            the ONE direction dir3_host[3] (host memory), used as given; NULL for a network set without view
+ *                            directions.  Synchronous: queued on `stream` and waited for.  Refused: a host-only context
+ *                            (NWE_ERR_STATE); the box and resolution as above, `which`, an unknown precision (NWE_ERR_INVALID); the
+ *                            network not set (NWE_ERR_STATE); a direction for a network without view directions or none for one
+ *                            with (NWE_ERR_INVALID); an MFMA precision for a shape without a query kernel (NWE_ERR_UNSUPPORTED, the
+ *                            query's own message).
+ *   nwe_render_grid          the frame: the rows [row_begin, row_end) of n_poses pinhole views with the arguments of nwe_render,
+ *                            into DEVICE buffers.  Needs a grid and nwe_set_sampling, and no network.  Refuses in this order,
+ *                            before anything is queued: a NULL context; NULL out, a wrong struct_bytes, none of rgb / depth / acc /
+ *                            the diagnostics requested (NWE_ERR_INVALID); the camera and the ray count as nwe_render refuses them;
+ *                            no grid set, sampling not set (NWE_ERR_STATE); last, a host-only context (NWE_ERR_STATE) - so every
+ *                            refusal in front of it can be asked of a host-only context.  Zero rays is NWE_OK and launches
+ *                            nothing.  Asynchronous on `stream`; its launches have an event ring of their own, four in flight,
+ *                            like the query's, which the waits of nwe_set_network / nwe_set_sampling and of the grid calls cover.
+ *                            It moves none of nwe_last_kernel_ms, nwe_last_launch_parts, nwe_debug_last_plan,
+ *                            nwe_last_ray_evaluations, nwe_last_coarse_launch and nwe_last_query_ms.
+ *   nwe_last_grid_ms         the device time of the most recent nwe_render_grid launch that was recorded; blocks until it has
+ *                            finished, like nwe_last_kernel_ms; < 0 if there was none. */
+typedef struct nwe_grid_outputs {
+    uint64_t struct_bytes;  /* = sizeof(nwe_grid_outputs) */
+    float *rgb;             /* [R,3] */
+    float *depth;           /* [R]   */
+    float *acc;             /* [R]   */
+    /* diagnostics, each may be NULL */
+    float *weights_coarse;  /* [R, n_samples] */
+    float *z_fine;          /* [R, S]      S = n_samples + n_importance: the depths of the output pass */
+    float *raw_fine;        /* [R, S, 4]   the interpolated rows of the output pass */
+    uint32_t *flags;        /* [1]    NWE_FLAG_RGB / _DEPTH / _ACC, OR-ed (caller zeroes it) */
+} nwe_grid_outputs;
+int nwe_set_radiance_grid(nwe_ctx *ctx, const float *lo, const float *hi, const int *res, const float *raw, int on_device);
+int nwe_clear_radiance_grid(nwe_ctx *ctx);
+int nwe_get_radiance_grid(const nwe_ctx *ctx, float *lo, float *hi, int *res, float *inv);
+int nwe_radiance_grid_copy(nwe_ctx *ctx, float *host_values, int64_t n_values);
+int nwe_bake_radiance_grid(nwe_ctx *ctx, const float *lo, const float *hi, const int *res, int which, const float *dir3_host,
+                           int precision, void *stream);
+int nwe_render_grid(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near,
+                    float far, int row_begin, int row_end, const nwe_grid_outputs *out, void *stream);
+float nwe_last_grid_ms(nwe_ctx *ctx);
+
 /* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
  * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1 without separate
  * passes, n_importance == 0, or a call armed with nwe_debug_set_coarse_weights).  Under separate passes with k = 1 it is the

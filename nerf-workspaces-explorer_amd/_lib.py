@@ -32,6 +32,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_set_occupancy", "nwe_clear_occupancy", "nwe_get_occupancy", "nwe_occupancy_copy", "nwe_build_occupancy",
            "nwe_set_coarse_grid", "nwe_clear_coarse_grid", "nwe_get_coarse_grid", "nwe_coarse_grid_copy", "nwe_bake_coarse_grid",
            "nwe_coarse_grid_weights",
+           "nwe_set_radiance_grid", "nwe_clear_radiance_grid", "nwe_get_radiance_grid", "nwe_radiance_grid_copy", "nwe_bake_radiance_grid",
+           "nwe_render_grid", "nwe_last_grid_ms",
            "nwe_debug_set_packet_blocks", "nwe_debug_last_packet_blocks", "nwe_debug_packet_pixels")
 
 
@@ -52,6 +54,17 @@ class PointOutputs(C.Structure):
 
     def __init__(self, **kw):
         super().__init__(struct_bytes=C.sizeof(PointOutputs), **kw)
+
+
+GRID_OUTPUT_FIELDS = ("rgb", "depth", "acc", "weights_coarse", "z_fine", "raw_fine", "flags")
+
+
+class GridOutputs(C.Structure):
+    """nwe_grid_outputs of nwe_render_grid."""
+    _fields_ = [("struct_bytes", C.c_uint64)] + [(name, C.c_void_p) for name in GRID_OUTPUT_FIELDS]
+
+    def __init__(self, **kw):
+        super().__init__(struct_bytes=C.sizeof(GridOutputs), **kw)
 
 
 PLAN_HOOK_COARSE_WEIGHTS, PLAN_HOOK_OTHER = 1, 2
@@ -160,6 +173,13 @@ def load() -> C.CDLL:
         "nwe_coarse_grid_copy": (I, [P, P, I64]),
         "nwe_bake_coarse_grid": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), I, P]),
         "nwe_coarse_grid_weights": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, P, P, P]),
+        "nwe_set_radiance_grid": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), P, I]),
+        "nwe_clear_radiance_grid": (I, [P]),
+        "nwe_get_radiance_grid": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), C.POINTER(F)]),
+        "nwe_radiance_grid_copy": (I, [P, P, I64]),
+        "nwe_bake_radiance_grid": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), I, C.POINTER(F), I, P]),
+        "nwe_render_grid": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, C.POINTER(GridOutputs), P]),
+        "nwe_last_grid_ms": (F, [P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

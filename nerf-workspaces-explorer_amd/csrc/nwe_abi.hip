@@ -104,7 +104,7 @@ struct GridBox {
             inv[i] = (float)res[i] / (hi[i] - lo[i]);   // fp32, once: what the kernels multiply by (nwe_get_occupancy / _coarse_grid report it)
         }
     }
-    // nwe_get_occupancy, nwe_get_coarse_grid: every pointer may be null
+    // nwe_get_occupancy, nwe_get_coarse_grid, nwe_get_radiance_grid: every pointer may be null
     void read(float* lo_, float* hi_, int* res_, float* inv_) const {
         for (int i = 0; i < 3; ++i) {
             if (lo_) lo_[i] = lo[i];
@@ -133,6 +133,10 @@ struct CoarseGridState {
     std::vector<float> host;
 };
 
+// The radiance grid of a context (nwe_set_radiance_grid, nwe_bake_radiance_grid): four values per cell, kept like the coarse
+// grid's - on a device context in d_rgrid only (up to 512^3 rows, 2 GiB), on a host-only context in `host`.
+using RadianceGridState = CoarseGridState;
+
 thread_local std::string g_create_error;
 
 }  // namespace
@@ -155,6 +159,10 @@ struct nwe_ctx {
     Slot query_slots[kSlots];
     int next_query = 0, last_query = -1;
     int query_steps = 0;      // nwe_debug_set_query_steps: 0 = automatic
+    // nwe_render_grid: a ring of its own as well, so that a grid frame moves none of the render launches' or the query's reports;
+    // last_grid: the most recent grid launch that was recorded (nwe_last_grid_ms)
+    Slot grid_slots[kSlots];
+    int next_grid = 0, last_grid = -1;
     const float* dbg_z_fine = nullptr;
     const float *dbg_raw_c = nullptr, *dbg_raw_f = nullptr, *dbg_w = nullptr;   // nwe_debug_set_raw / _coarse_weights, one call
     int fold = 1;             // nwe_debug_set_fold: read by nwe_set_network
@@ -178,6 +186,8 @@ struct nwe_ctx {
     DevBuf<float> d_occ_scratch;              // nwe_build_occupancy: probe points and their sigma, one chunk
     CoarseGridState cgrid;    // nwe_set_coarse_grid / nwe_bake_coarse_grid: cgrid.set = a grid is set
     DevBuf<float> d_cgrid;                    // its values on the device; nwe_bake_coarse_grid's cell centres go through d_occ_scratch
+    RadianceGridState rgrid;  // nwe_set_radiance_grid / nwe_bake_radiance_grid: rgrid.set = a grid is set
+    DevBuf<float> d_rgrid;                    // its rows on the device; nwe_bake_radiance_grid's cell centres go through d_occ_scratch
     int decomposition = -1;   // nwe_debug_set_decomposition
     int work_queue = -1;      // nwe_debug_set_work_queue; a new context takes NWE_WORK_QUEUE=0|1 from the environment
     bool backfill = true;     // the hybrid plan's second launch on the slot's own stream; NWE_WORK_QUEUE_BACKFILL=0: behind the first
@@ -224,8 +234,8 @@ ContextDesc describe_context(const nwe_ctx* c) {
     for (int i = 0; i < 2; ++i) d.net[i] = c->net[i];
     d.ns = c->ns; d.ni = c->ni; d.host_only = c->host_only;
     d.min_trans = c->min_trans; d.share_k = c->share_k; d.separate = c->separate != 0;
-    d.occ.set = c->occ.set; d.cgrid.set = c->cgrid.set;
-    for (int i = 0; i < 3; ++i) { d.occ.res[i] = c->occ.box.res[i]; d.cgrid.res[i] = c->cgrid.box.res[i]; }
+    d.occ.set = c->occ.set; d.cgrid.set = c->cgrid.set; d.rgrid.set = c->rgrid.set;
+    for (int i = 0; i < 3; ++i) { d.occ.res[i] = c->occ.box.res[i]; d.cgrid.res[i] = c->cgrid.box.res[i]; d.rgrid.res[i] = c->rgrid.box.res[i]; }
     d.stamps = c->stamps != nullptr;
     d.decomposition = c->decomposition; d.queue_mode = c->work_queue;
     d.backfill = c->backfill; d.tail = c->tail; d.packet_blocks = c->packet_blocks;
@@ -304,6 +314,8 @@ int wait_for_launches(nwe_ctx* c) {
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     if (c->rays_slot.used) HIPCHK(c, hipEventSynchronize(c->rays_slot.ev1));
     for (Slot& s : c->query_slots)   // a query streams the weights of its network throughout
+        if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
+    for (Slot& s : c->grid_slots)    // a grid frame reads the sampling tables and the radiance grid
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     return NWE_OK;
 }
@@ -664,6 +676,7 @@ int set_network(nwe_ctx* c, int which, const NetShape& shape, const float* const
     n.set = true;
     c->occ.set = false;   // a grid describes the networks it was made for (include/nwe.h); the wait above covers its readers
     if (which == NWE_NET_COARSE) c->cgrid = CoarseGridState{};   // the coarse density grid describes the coarse network
+    c->rgrid = RadianceGridState{};   // the radiance grid was baked from a network of this context: either upload clears it
     return NWE_OK;
 }
 
@@ -716,13 +729,54 @@ int install_occupancy(nwe_ctx* c, const GridBox& box, std::vector<uint32_t>&& wo
 
 // ---- coarse density grid (nwe_set_coarse_grid, nwe_bake_coarse_grid) ----
 
-// The box, the resolution and inv of a new grid; the values are in place (d_cgrid or g.host) when this is called.
-void install_coarse_grid(nwe_ctx* c, const GridBox& box, std::vector<float>&& host) {
+// The box, the resolution and inv of a new grid of values - the coarse density grid or the radiance grid; the values are in place
+// (the grid's device buffer or g.host) when this is called.
+void install_grid(CoarseGridState& slot, const GridBox& box, std::vector<float>&& host) {
     CoarseGridState g;
     g.box = box;
     g.host = std::move(host);
     g.set = true;
-    c->cgrid = std::move(g);
+    slot = std::move(g);
+}
+void install_coarse_grid(nwe_ctx* c, const GridBox& box, std::vector<float>&& host) { install_grid(c->cgrid, box, std::move(host)); }
+
+// nwe_set_* of a grid of values, `per_cell` floats a cell, behind its checks: the one path of both such grids.
+int set_values_grid(nwe_ctx* c, CoarseGridState& slot, DevBuf<float>& dev, const GridBox& box, int per_cell, const float* values, bool on_device) {
+    const size_t count = (size_t)box.cells * per_cell;
+    if (c->host_only) {
+        install_grid(slot, box, std::vector<float>(values, values + count));
+        return NWE_OK;
+    }
+    ON_DEVICE(c);
+    TRY(wait_for_launches(c));   // a queued launch still reads the old grid
+    slot = CoarseGridState{};    // a failing allocation or upload leaves no grid rather than the old box over new values
+    HIPCHK(c, dev.reserve(count));
+    HIPCHK(c, hipMemcpy(dev.get(), values, count * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    install_grid(slot, box, {});
+    return NWE_OK;
+}
+int clear_values_grid(nwe_ctx* c, CoarseGridState& slot) {
+    if (!c->host_only && slot.set) {
+        ON_DEVICE(c);
+        TRY(wait_for_launches(c));
+    }
+    slot = CoarseGridState{};
+    return NWE_OK;
+}
+int copy_values_grid(nwe_ctx* c, const CoarseGridState& slot, const DevBuf<float>& dev, float* host_values, int64_t n_values) {
+    if (c->host_only) return copy_out(&slot.host, host_values, n_values);
+    ON_DEVICE(c);
+    HIPCHK(c, hipMemcpy(host_values, dev.get(), (size_t)n_values * sizeof(float), hipMemcpyDeviceToHost));
+    return NWE_OK;
+}
+
+// The context's radiance grid as its kernel takes it.
+RadianceGrid radiance_grid_args(const nwe_ctx* ctx) {
+    RadianceGrid g = {};
+    const GridBox& box = ctx->rgrid.box;
+    for (int i = 0; i < 3; ++i) { g.lo[i] = box.lo[i]; g.inv[i] = box.inv[i]; g.res[i] = box.res[i]; }
+    g.rows = reinterpret_cast<const float4*>(ctx->d_rgrid.get());
+    return g;
 }
 
 // ---- the probe lattice of a box: what nwe_build_occupancy asks the networks at, and - probes = 1, the cells' centres - what
@@ -1238,29 +1292,12 @@ int nwe_build_occupancy(nwe_ctx* c, const float* lo, const float* hi, const int*
 int nwe_set_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, const float* sigma, int on_device) {
     if (!c) return NWE_ERR_INVALID;
     CHECK(c, check_set_grid(kCoarseGrid, lo, hi, res, sigma, on_device != 0, c->host_only));
-    const GridBox box(lo, hi, res);
-    const size_t cells = (size_t)box.cells;
-    if (c->host_only) {
-        install_coarse_grid(c, box, std::vector<float>(sigma, sigma + cells));
-        return NWE_OK;
-    }
-    ON_DEVICE(c);
-    TRY(wait_for_launches(c));   // a queued launch still reads the old grid
-    c->cgrid = CoarseGridState{};   // a failing upload leaves no grid rather than the old box over new values
-    HIPCHK(c, c->d_cgrid.reserve(cells));
-    HIPCHK(c, hipMemcpy(c->d_cgrid.get(), sigma, cells * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    install_coarse_grid(c, box, {});
-    return NWE_OK;
+    return set_values_grid(c, c->cgrid, c->d_cgrid, GridBox(lo, hi, res), 1, sigma, on_device != 0);
 }
 
 int nwe_clear_coarse_grid(nwe_ctx* c) {
     if (!c) return NWE_ERR_INVALID;
-    if (!c->host_only && c->cgrid.set) {
-        ON_DEVICE(c);
-        TRY(wait_for_launches(c));
-    }
-    c->cgrid = CoarseGridState{};
-    return NWE_OK;
+    return clear_values_grid(c, c->cgrid);
 }
 
 int nwe_get_coarse_grid(const nwe_ctx* c, float* lo, float* hi, int* res, float* inv) {
@@ -1274,10 +1311,7 @@ int nwe_coarse_grid_copy(nwe_ctx* c, float* host_values, int64_t n_values) {
     if (!c) return NWE_ERR_INVALID;
     if (!c->cgrid.set) return NWE_ERR_STATE;
     if (!host_values || n_values != c->cgrid.box.cells) return fail(c, NWE_ERR_INVALID, "coarse grid: the copy needs rx * ry * rz values");
-    if (c->host_only) return copy_out(&c->cgrid.host, host_values, n_values);
-    ON_DEVICE(c);
-    HIPCHK(c, hipMemcpy(host_values, c->d_cgrid.get(), (size_t)n_values * sizeof(float), hipMemcpyDeviceToHost));
-    return NWE_OK;
+    return copy_values_grid(c, c->cgrid, c->d_cgrid, host_values, n_values);
 }
 
 int nwe_bake_coarse_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, int precision, void* stream_) {
@@ -1319,6 +1353,92 @@ int nwe_coarse_grid_weights(nwe_ctx* c, const float* c2w, int n_poses, int H, in
         launch_coarse_grid_weights(a, coarse_grid_args(c), nullptr, sigma_out_dev, weights_out_dev, stream);
         return NWE_OK;
     });
+}
+
+int nwe_set_radiance_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, const float* raw, int on_device) {
+    if (!c) return NWE_ERR_INVALID;
+    CHECK(c, check_set_grid(kRadianceGrid, lo, hi, res, raw, on_device != 0, c->host_only));
+    return set_values_grid(c, c->rgrid, c->d_rgrid, GridBox(lo, hi, res), 4, raw, on_device != 0);
+}
+
+int nwe_clear_radiance_grid(nwe_ctx* c) {
+    if (!c) return NWE_ERR_INVALID;
+    return clear_values_grid(c, c->rgrid);
+}
+
+int nwe_get_radiance_grid(const nwe_ctx* c, float* lo, float* hi, int* res, float* inv) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!c->rgrid.set) return NWE_ERR_STATE;   // no grid is set: the outputs stay untouched (and so does the error text of a const context)
+    c->rgrid.box.read(lo, hi, res, inv);
+    return NWE_OK;
+}
+
+int nwe_radiance_grid_copy(nwe_ctx* c, float* host_values, int64_t n_values) {
+    if (!c) return NWE_ERR_INVALID;
+    if (!c->rgrid.set) return NWE_ERR_STATE;
+    if (!host_values || n_values != 4 * c->rgrid.box.cells) return fail(c, NWE_ERR_INVALID, "radiance grid: the copy needs 4 * rx * ry * rz values");
+    return copy_values_grid(c, c->rgrid, c->d_rgrid, host_values, n_values);
+}
+
+int nwe_bake_radiance_grid(nwe_ctx* c, const float* lo, const float* hi, const int* res, int which, const float* dir3_host, int precision,
+                           void* stream_) {
+    CHECK(c, check_bake_radiance_grid(MaybeContext(c).p, lo, hi, res, which, dir3_host, precision));
+    hipStream_t stream = (hipStream_t)stream_;
+    ON_DEVICE(c);
+    TRY(wait_for_launches(c));   // the bake ends in a new grid: a queued launch still reads the old one
+    c->rgrid = RadianceGridState{};   // a failing bake leaves no grid
+    const NetState& n = c->net[which];
+    const GridBox box(lo, hi, res);
+    const Lattice l = probe_lattice(box, 1);   // the cells' centres, a chunk of them in the scratch buffer, the direction behind them
+    HIPCHK(c, c->d_occ_scratch.reserve((size_t)l.chunk_cells * 3 + 3));
+    HIPCHK(c, c->d_rgrid.reserve((size_t)box.cells * 4));
+    float* points = c->d_occ_scratch.get();
+    float* dir = dir3_host ? points + (size_t)l.chunk_cells * 3 : nullptr;
+    if (dir) HIPCHK(c, hipMemcpyAsync(dir, dir3_host, 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+    for (int64_t first = 0; first < box.cells; first += l.chunk_cells) {   // the rows of a chunk go straight into the grid
+        const int count = (int)std::min<int64_t>(l.chunk_cells, box.cells - first);
+        launch_occ_probe_points(l.b, first, count, points, stream);
+        QueryArgs q = {};
+        q.points = points; q.dirs = dir; q.raw = c->d_rgrid.get() + first * 4; q.n_points = count; q.points_per_dir = count;
+        if (precision == NWE_PREC_F32) launch_query_f32(q, n.f32, c->query_steps, c->cus, stream);
+        else if (!launch_query_mfma(q, n.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
+            return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(stream));
+    install_grid(c->rgrid, box, {});
+    return NWE_OK;
+}
+
+int nwe_render_grid(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near, float far,
+                    int row_begin, int row_end, const nwe_grid_outputs* out, void* stream_) {
+    const Camera m{c2w, n_poses, H, W, fx, fy, cx, cy, near, far, row_begin, row_end};
+    CHECK(c, check_render_grid(MaybeContext(c).p, out, m));
+    hipStream_t stream = (hipStream_t)stream_;
+    ON_DEVICE(c);
+    Slot& slot = c->grid_slots[c->next_grid];   // not a slot of the render ring (see nwe_create_rays)
+    TRY(prepare_slot(c, slot));
+    TRY(upload_poses(c, slot, c2w, n_poses, stream));
+    RenderArgs a = camera_args(m, slot.poses.get());
+    if (a.n_rays == 0) return NWE_OK;
+    a.white_bkgd = c->white_bkgd;   // nothing else of the context: the sampling tables and counts, no mode
+    a.t_vals = c->d_t.get(); a.omt_vals = a.t_vals + kMaxSamples; a.u_vals = a.omt_vals + kMaxSamples;
+    a.n_samples = c->ns; a.n_importance = c->ni;
+    a.out.struct_bytes = sizeof(nwe_outputs);
+    a.out.rgb = out->rgb; a.out.depth = out->depth; a.out.acc = out->acc; a.out.flags = out->flags;
+    a.out.weights_coarse = out->weights_coarse; a.out.z_fine = out->z_fine; a.out.raw_fine = out->raw_fine;
+    TRY(record_launch(c, slot, stream, [&]() -> int {
+        launch_radiance_grid_render(a, radiance_grid_args(c), stream);
+        return NWE_OK;
+    }));
+    c->last_grid = (int)(&slot - c->grid_slots);
+    c->next_grid = (c->last_grid + 1) % nwe_ctx::kSlots;
+    return NWE_OK;
+}
+
+float nwe_last_grid_ms(nwe_ctx* c) {
+    if (!c || c->host_only || c->last_grid < 0 || !c->grid_slots[c->last_grid].used) return -1.f;
+    return elapsed_ms(c, c->grid_slots[c->last_grid], "nwe_last_grid_ms");
 }
 
 int nwe_set_train_tables(nwe_ctx* c, const float* t_rand_dev, const float* noise_coarse_dev, const float* noise_fine_dev, const float* u_sorted_dev) {

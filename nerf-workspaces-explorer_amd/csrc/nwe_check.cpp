@@ -260,6 +260,7 @@ Refusal check_query(const ContextDesc* d, int which, const float* points, int64_
 // occupancy: 1024^3 = 2^30 cells at the most, so a cell's index and the probes of a chunk stay below 2^31
 const GridKind kOccupancyGrid = {"occupancy", 1024, false, "bits", "bits"};
 const GridKind kCoarseGrid = {"coarse grid", 512, true, "sigma", "values"};
+const GridKind kRadianceGrid = {"radiance grid", 512, true, "rows", "rows"};
 
 Refusal check_grid_box(const GridKind& kind, const float* lo, const float* hi, const int* res) {
     const std::string word = std::string(kind.word) + ": ";
@@ -305,6 +306,34 @@ Refusal check_bake_coarse_grid(const ContextDesc* d, const float* lo, const floa
     if (!n.set) return state("coarse grid: the coarse network is not set");
     if (precision != NWE_PREC_F32 && !n.mfma_ok) return no_mfma_kernel();
     return {};
+}
+
+Refusal check_bake_radiance_grid(const ContextDesc* d, const float* lo, const float* hi, const int* res, int which, const float* dir3,
+                                 int precision) {
+    if (Refusal r = check_on_device(d && !d->host_only)) return r;
+    if (Refusal r = check_grid_box(kRadianceGrid, lo, hi, res)) return r;
+    if (which != NWE_NET_COARSE && which != NWE_NET_FINE) return invalid("which must be 0 or 1");
+    if (Refusal r = check_precision(precision)) return r;
+    const NetDesc& n = d->net[which];
+    if (!n.set) return state(which == NWE_NET_COARSE ? "radiance grid: the coarse network is not set" : "radiance grid: the fine network is not set");
+    if (n.in_dir == 0 && dir3) return invalid("the network takes no view directions (nwe_set_network_no_view_dirs): dir3_host must be null");
+    if (n.in_dir != 0 && !dir3) return invalid("radiance grid: the rows of a network with view directions need dir3_host");
+    if (precision != NWE_PREC_F32 && !n.mfma_ok) return no_mfma_kernel();
+    return {};
+}
+
+Refusal check_render_grid(const ContextDesc* d, const nwe_grid_outputs* out, const Camera& m) {
+    if (!d) return invalid("null context");
+    if (!out) return invalid("null outputs");
+    if (out->struct_bytes != sizeof(nwe_grid_outputs))
+        return invalid("nwe_grid_outputs.struct_bytes != sizeof(nwe_grid_outputs): the caller was built against another version of include/nwe.h");
+    if (!out->rgb && !out->depth && !out->acc && !out->weights_coarse && !out->z_fine && !out->raw_fine)
+        return invalid("none of rgb / depth / acc / weights_coarse / z_fine / raw_fine requested");
+    if (Refusal r = check_camera(m)) return r;
+    if (Refusal r = check_ray_count((int64_t)m.n_poses * (m.row_end - m.row_begin) * m.W, false)) return r;
+    if (!d->rgrid.set) return state("radiance grid: no grid is set (nwe_set_radiance_grid, nwe_bake_radiance_grid)");
+    if (d->ns <= 0) return state("nwe_set_sampling has not been called");
+    return check_on_device(!d->host_only);
 }
 
 }  // namespace nwe

@@ -40,6 +40,7 @@ struct ContextDesc {
     int share_k = 1;                 // nwe_set_shared_coarse: 1 = off
     bool separate = false;           // nwe_set_separate_passes
     GridDesc occ, cgrid;             // nwe_set_occupancy, nwe_set_coarse_grid
+    GridDesc rgrid;                  // nwe_set_radiance_grid: read by nwe_render_grid alone, no mode of a render call
     bool stamps = false;             // a stamp buffer is armed (nwe_debug_set_stamps)
     // read by the planner alone
     int decomposition = -1, queue_mode = -1;
@@ -82,9 +83,9 @@ Refusal check_separate_passes(int on);
 Refusal check_query(const ContextDesc* d, int which, const float* points, int64_t n_points, const float* dirs, int64_t points_per_dir,
                     int precision, const nwe_point_outputs* out);
 
-// ---- the two grids ----
+// ---- the grids ----
 
-// What tells the occupancy grid's refusals from the coarse density grid's.
+// What tells the refusals of the occupancy grid, the coarse density grid and the radiance grid apart.
 struct GridKind {
     const char* word;       // opens every text
     int max_res;            // per axis
@@ -92,15 +93,21 @@ struct GridKind {
     const char* values;     // what nwe_set_* calls its array when it is null ...
     const char* from_host;  // ... and when a host-only context is told that it lies on a device
 };
-extern const GridKind kOccupancyGrid, kCoarseGrid;
+extern const GridKind kOccupancyGrid, kCoarseGrid, kRadianceGrid;
 
 // Null pointers, a box that is not finite or not lo < hi on every axis, a resolution outside 1 .. max_res per axis.
 Refusal check_grid_box(const GridKind& kind, const float* lo, const float* hi, const int* res);
-// nwe_set_occupancy, nwe_set_coarse_grid: the box, then the array.
+// nwe_set_occupancy, nwe_set_coarse_grid, nwe_set_radiance_grid: the box, then the array.
 Refusal check_set_grid(const GridKind& kind, const float* lo, const float* hi, const int* res, const void* values, bool on_device, bool host_only);
 // nwe_build_occupancy, nwe_bake_coarse_grid: what they refuse before they need their device.
 Refusal check_build_occupancy(const ContextDesc* d, const float* lo, const float* hi, const int* res, int probes, float threshold, int dilate,
                               int precision);
 Refusal check_bake_coarse_grid(const ContextDesc* d, const float* lo, const float* hi, const int* res, int precision);
+// nwe_bake_radiance_grid: the same, and the direction rules of the query for the one direction of the bake.
+Refusal check_bake_radiance_grid(const ContextDesc* d, const float* lo, const float* hi, const int* res, int which, const float* dir3,
+                                 int precision);
+// nwe_render_grid, in the order it refuses in: the context, the outputs, the camera, the ray count, grid and sampling, and last -
+// so that everything in front can be asked of a host-only context - the device.
+Refusal check_render_grid(const ContextDesc* d, const nwe_grid_outputs* out, const Camera& m);
 
 }  // namespace nwe

@@ -102,6 +102,20 @@ struct CoarseGrid {
 // [n_samples][n_rays] (the consumer's, sample-major), sigma and weights [n_rays][n_samples]; each may be null.
 void launch_coarse_grid_weights(const RenderArgs& a, const CoarseGrid& g, float* table, float* sigma, float* weights, hipStream_t stream);
 
+// ---- radiance grid (nwe_set_radiance_grid, nwe_render_grid; nwe_radiance_grid.hip) ----
+// The radiance grid of a context as its kernel reads it (by value): the box as CoarseGrid holds it; rows = res[0] * res[1] * res[2]
+// rows (rgb_raw[3], sigma_raw) at the cell centres, z fastest, on the device (16-byte aligned: a device allocation).
+struct RadianceGrid {
+    float lo[3], inv[3];
+    int res[3];
+    int pad;
+    const float4* rows;
+};
+constexpr int kGridThreads = 64;   // rays of a workgroup of radiance_grid_render_kernel: one wave
+// One thread per ray of `a` (pinhole rays: a.poses, the camera, the sampling tables and counts, a.white_bkgd), both passes from
+// the grid; a.out: rgb / depth / acc / flags and the diagnostics weights_coarse / z_fine / raw_fine, each may be null.
+void launch_radiance_grid_render(const RenderArgs& a, const RadianceGrid& g, hipStream_t stream);
+
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);
 

@@ -52,8 +52,15 @@ class NeRFReplicaInferenceHandler:
     def __init__(self, office_name: str, ckpt_path: str, device: int = 0, precision: str = "auto",
                  devices: Optional[Sequence[int]] = None, early_termination: float = 0.0, shared_coarse: int = 1,
                  separate_passes: Optional[bool] = None, occupancy: Optional[Mapping[str, object]] = None,
-                 baked_coarse: Optional[Mapping[str, object]] = None) -> None:
-        """``baked_coarse``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128, one int or
+                 baked_coarse: Optional[Mapping[str, object]] = None,
+                 radiance_grid: Optional[Mapping[str, object]] = None) -> None:
+        """``radiance_grid``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128, one int or
+        three), "which" ("fine") and "view_dir" (None: the mean over the six axis directions): initialize_models() bakes the
+        network's raw output into a radiance grid over the box (bake_radiance_grid), from which ``render_grid`` and
+        ``render_coordinates(preview="grid")`` render preview frames without running a network - an approximation; no other
+        frame reads the grid.  The environment variable NWE_RADIANCE_GRID = "res" overrides the resolution over the box given
+        here, for the same two-argument callers; without a box there is no grid.  One device only: not with ``devices``.
+        ``baked_coarse``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128, one int or
         three): initialize_models() bakes the coarse network's density into a grid over the box (Renderer.bake_coarse_grid) and
         frames take their coarse weights from it instead of running the coarse network - an approximation, off by default.
         The environment variable NWE_BAKED_COARSE = "res" overrides the resolution over the box given here, for the same
@@ -137,6 +144,21 @@ class NeRFReplicaInferenceHandler:
                 raise ValueError("a baked coarse pass is not supported together with early_termination > 0, shared_coarse > 1, "
                                  "separate_passes or an occupancy grid")
             self._baked_coarse = grid
+        self._radiance_grid = None
+        if radiance_grid is not None:
+            unknown = set(radiance_grid) - {"lo", "hi", "resolution", "which", "view_dir"}
+            if unknown or "lo" not in radiance_grid or "hi" not in radiance_grid:
+                raise ValueError(f"radiance_grid needs 'lo' and 'hi' and may hold resolution, which, view_dir; got {sorted(radiance_grid)}")
+            grid = {"resolution": 128, "which": "fine", "view_dir": None}
+            grid.update(radiance_grid)
+            env = os.environ.get("NWE_RADIANCE_GRID", "").strip()
+            if env != "":
+                if not env.isdigit():
+                    raise ValueError("NWE_RADIANCE_GRID must be a resolution (one integer)")
+                grid["resolution"] = int(env)
+            if self._devices:
+                raise ValueError("a radiance grid is rendered by one device: it is not supported together with devices")
+            self._radiance_grid = grid
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -229,6 +251,8 @@ class NeRFReplicaInferenceHandler:
             self.build_occupancy(**self._occupancy)
         if self._baked_coarse is not None:
             self.bake_coarse_grid(**self._baked_coarse)
+        if self._radiance_grid is not None:
+            self.bake_radiance_grid(**self._radiance_grid)
 
     def _need_renderer(self) -> Renderer:
         if self._renderer is None:
@@ -273,15 +297,23 @@ class NeRFReplicaInferenceHandler:
         return out
 
     def render_coordinates(self, init_coordinates: COORD, coordinates: COORD, *, out: Optional[np.ndarray] = None,
-                           preview: bool = False) -> np.ndarray:
+                           preview=False) -> np.ndarray:
         """handler.py:166-185: uint8 [H,W,3], C-contiguous (Qt wraps ``image.data`` with stride 3*W,
         application/app.py:339-340).
 
         Frame hand-off: ``to8b`` (model_utils.py:9, truncating) runs on the device, the 3 bytes/pixel image goes through
         a pinned staging buffer kept by the handler, and lands either in a fresh array (the reference's behaviour) or in
         ``out``, a caller-owned uint8 [H,W,3] array such as the one a GUI image wraps.  ``preview=True`` renders the coarse
-        pass only (Ns samples through the coarse net, a quarter of the work) for a fast first image."""
+        pass only (Ns samples through the coarse net, a quarter of the work) for a fast first image; ``preview="grid"`` renders
+        from the radiance grid (render_grid: no network runs) and raises a RuntimeError when none is set."""
         r = self._need_renderer()
+        from_grid = isinstance(preview, str)
+        if from_grid:
+            if preview != "grid":
+                raise ValueError("preview must be False, True or 'grid'")
+            if getattr(r, "radiance_grid", None) is None:
+                raise RuntimeError('preview="grid" needs a radiance grid: call bake_radiance_grid(lo, hi, resolution) first')
+            preview = False
         camera_pose = get_camera_poses_from_list_of_coordinates(init_coordinates, [coordinates])   # :170
         H, W = self._img_h, self._img_w
         if out is not None and (out.dtype != np.uint8 or out.shape != (H, W, 3) or not out.flags.c_contiguous):
@@ -289,7 +321,7 @@ class NeRFReplicaInferenceHandler:
         if preview and self._n_importance > 0:
             r.set_sampling(self._n_samples, 0)
         try:
-            res = self.render_batch(camera_pose.numpy(), H, W, outputs=("rgb",))
+            res = (self.render_grid_batch if from_grid else self.render_batch)(camera_pose.numpy(), H, W, outputs=("rgb",))
         finally:
             if preview and self._n_importance > 0:
                 r.set_sampling(self._n_samples, self._n_importance)
@@ -402,6 +434,70 @@ class NeRFReplicaInferenceHandler:
 
     def clear_coarse_grid(self) -> None:
         self._need_renderer().clear_coarse_grid()
+
+    _AXIS_DIRECTIONS = ((1., 0., 0.), (-1., 0., 0.), (0., 1., 0.), (0., -1., 0.), (0., 0., 1.), (0., 0., -1.))
+
+    def _grid_renderer(self) -> Renderer:
+        r = self._need_renderer()
+        if isinstance(r, TiledRenderer):
+            raise NotImplementedError("the radiance grid is rendered by one device (a grid frame is a few milliseconds): not with devices")
+        return r
+
+    def bake_radiance_grid(self, lo: Sequence[float], hi: Sequence[float], resolution=128, which="fine",
+                           view_dir: Optional[Sequence[float]] = None, precision: Optional[str] = None, chunk: int = 1 << 20) -> None:
+        """Bakes the raw output of the ``which`` network at the cell centres of the box lo..hi into the renderer's radiance grid;
+        ``render_grid`` and ``render_coordinates(preview="grid")`` then render from it.  A given ``view_dir`` (three floats, used as
+        given) is the one direction every cell is evaluated with (Renderer.bake_radiance_grid).  ``view_dir=None`` on a network with
+        view directions bakes the mean of the raw rows over the six axis directions +x, -x, +y, -y, +z, -z: six queries through
+        run_network, summed in float32 in that order and divided by 6 (sigma_raw does not depend on the direction); on a network
+        without view directions it is the network's row."""
+        r = self._grid_renderer()
+        w, auto = self._query_net(which)
+        precision = precision or auto
+        if view_dir is not None or not self._use_view_dirs:
+            r.bake_radiance_grid(lo, hi, resolution, w, view_dir, precision)
+            return
+        res3 = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(v) for v in resolution)
+        if len(res3) != 3 or min(res3) < 1 or len(lo) != 3 or len(hi) != 3:
+            raise ValueError("bake_radiance_grid needs lo, hi of three coordinates and a resolution of one or three positive ints")
+        total = res3[0] * res3[1] * res3[2]
+        raw = torch.empty((total, 4), dtype=torch.float32, device=r.device)
+        for start in range(0, total, int(chunk)):
+            count = min(int(chunk), total - start)
+            pts = self.grid_centres(lo, hi, res3, start, count, device=r.device)[None]      # [1, count, 3]: one direction for all
+            acc = None
+            for d in self._AXIS_DIRECTIONS:
+                row = self.run_network(pts, torch.tensor([d], dtype=torch.float32, device=r.device), which=w, precision=precision)[0]
+                acc = row if acc is None else acc + row
+            raw[start:start + count] = acc / 6.0
+        r.set_radiance_grid(raw.reshape(res3 + (4,)), lo, hi)
+
+    def clear_radiance_grid(self) -> None:
+        self._need_renderer().clear_radiance_grid()
+
+    @property
+    def radiance_grid(self):
+        """The renderer's radiance grid (Renderer.radiance_grid), None without one."""
+        return getattr(self._need_renderer(), "radiance_grid", None)
+
+    def render_grid(self, camera_pose, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
+                    outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+        """``render`` from the radiance grid (Renderer.render_grid): no network runs."""
+        res = self.render_grid_batch(np.asarray(camera_pose, dtype=np.float32).reshape(1, 4, 4), H, W, rows=rows, outputs=outputs)
+        return {k: v[0] for k, v in res.items()}
+
+    def render_grid_batch(self, poses, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
+                          outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+        """``render_batch`` from the radiance grid: [B,4,4] poses -> tensors with leading [B, h, W], one launch."""
+        r = self._grid_renderer()
+        H = self._img_h if H is None else H
+        W = self._img_w if W is None else W
+        fx, fy, cx, cy = pinhole_intrinsics(H, W)
+        poses = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4)
+        r0, r1 = rows if rows is not None else (0, H)
+        res = r.render_grid(poses, H, W, fx=fx, fy=fy, cx=cx, cy=cy, near=self._depth_close_bound, far=self._depth_far_bound,
+                            rows=(r0, r1), outputs=outputs)
+        return {k: v if k == "flags" else v.reshape((poses.shape[0], r1 - r0, W) + tuple(v.shape[1:])) for k, v in res.items()}
 
     @property
     def coarse_grid(self):

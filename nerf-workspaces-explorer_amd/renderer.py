@@ -551,6 +551,112 @@ class Renderer:
         self._check(rc, "nwe_coarse_grid_weights")
         return res
 
+    # -- radiance grid ----------------------------------------------------------------------------
+    def set_radiance_grid(self, raw, lo: Sequence[float], hi: Sequence[float], resolution=None) -> None:
+        """Opt-in radiance grid (include/nwe.h): ``raw`` holds the network's raw output (rgb_raw[3], sigma_raw) at the cell centres
+        of the box lo..hi, a float32 [rx, ry, rz, 4] array (numpy, or a torch tensor on any device; what handler.run_network returns
+        at handler.grid_centres) or a flat array with ``resolution`` given.  ``render_grid`` renders frames from it without a
+        network; no other call reads it.  ``set_network`` of either network clears the grid."""
+        if resolution is None:
+            if len(raw.shape) != 4 or raw.shape[3] != 4:
+                raise ValueError(f"the radiance grid needs an [rx, ry, rz, 4] array or a resolution, got {tuple(raw.shape)}")
+            resolution = tuple(raw.shape[:3])
+        lo3, hi3, res3, res = self._occupancy_box(lo, hi, resolution)
+        on_device = isinstance(raw, torch.Tensor) and self.device is not None and raw.device == self.device
+        if on_device:
+            values = raw.detach().to(torch.float32).contiguous()
+            n, ptr = values.numel(), values.data_ptr()
+        else:
+            if isinstance(raw, torch.Tensor):
+                raw = raw.detach().cpu().numpy()
+            values = np.ascontiguousarray(np.asarray(raw, dtype=np.float32))
+            n, ptr = values.size, values.ctypes.data
+        if min(res) > 0 and n != 4 * res[0] * res[1] * res[2]:
+            raise ValueError(f"the radiance grid needs {4 * res[0] * res[1] * res[2]} values for resolution {res}, got {n}")
+        if on_device:
+            torch.cuda.current_stream(self.device).synchronize()   # the copy inside is not ordered with torch's stream
+        self._check(self._lib.nwe_set_radiance_grid(self._ctx, lo3, hi3, res3, ptr if n else None, 1 if on_device else 0), "nwe_set_radiance_grid")
+
+    def bake_radiance_grid(self, lo: Sequence[float], hi: Sequence[float], resolution, which: int = _lib.NET_FINE,
+                           view_dir: Optional[Sequence[float]] = None, precision: str = "f16x3") -> None:
+        """Bakes the grid from network ``which`` (nwe_bake_radiance_grid): its raw output at the cell centres, every cell with the one
+        direction ``view_dir`` (three floats, used as given; None for networks without view directions)."""
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"unknown precision {precision!r}")
+        lo3, hi3, res3, _ = self._occupancy_box(lo, hi, resolution)
+        dir3 = None
+        if view_dir is not None:
+            if len(view_dir) != 3:
+                raise ValueError("view_dir must hold three coordinates")
+            dir3 = (C.c_float * 3)(*[float(v) for v in view_dir])
+        stream = None
+        if self.device is not None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.nwe_bake_radiance_grid(self._ctx, lo3, hi3, res3, int(which), dir3, _lib.PRECISIONS[precision], stream),
+                    "nwe_bake_radiance_grid")
+
+    def clear_radiance_grid(self) -> None:
+        self._check(self._lib.nwe_clear_radiance_grid(self._ctx), "nwe_clear_radiance_grid")
+
+    @property
+    def radiance_grid(self) -> Optional[Dict[str, object]]:
+        """None, or the grid: "lo", "hi", "resolution" and "inv" (the fp32 factors the kernel multiplies by)."""
+        lo, hi, res, inv = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_int * 3)(), (C.c_float * 3)()
+        if self._lib.nwe_get_radiance_grid(self._ctx, lo, hi, res, inv) != _lib.NWE_OK:
+            return None
+        return {"lo": tuple(lo), "hi": tuple(hi), "resolution": tuple(res), "inv": np.array(list(inv), dtype=np.float32)}
+
+    def radiance_grid_values(self) -> Optional[np.ndarray]:
+        """The grid's rows as a float32 [rx, ry, rz, 4] array on the host, None without one."""
+        g = self.radiance_grid
+        if g is None:
+            return None
+        rx, ry, rz = g["resolution"]
+        values = np.empty(rx * ry * rz * 4, dtype=np.float32)
+        self._check(self._lib.nwe_radiance_grid_copy(self._ctx, values.ctypes.data, values.size), "nwe_radiance_grid_copy")
+        return values.reshape(rx, ry, rz, 4)
+
+    def render_grid(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
+                    rows: Optional[Tuple[int, int]] = None, outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+        """A frame from the radiance grid (nwe_render_grid): rows [rows[0], rows[1]) of each pose, both passes of the pipeline with
+        the trilinear lookup in run_network's place; no network is needed or read.  ``outputs``: a choice of "rgb", "depth", "acc"
+        and the diagnostics "weights_coarse" [R, n_samples], "z_fine" [R, S] and "raw_fine" [R, S, 4] (S = n_samples +
+        n_importance, the output pass); "flags" is always returned."""
+        outputs = tuple(outputs)
+        unknown = set(outputs) - set(_lib.GRID_OUTPUT_FIELDS[:-1])
+        if unknown:
+            raise ValueError(f"unknown grid outputs {sorted(unknown)}; have {_lib.GRID_OUTPUT_FIELDS[:-1]}")
+        poses = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(-1, 4, 4))
+        r0, r1 = rows if rows is not None else (0, H)
+        o = _lib.GridOutputs()
+        if self.device is None:   # a host-only context: the ABI's own refusals, nothing allocated
+            for name in outputs:
+                setattr(o, name, 1)   # never written: every path of a host-only context refuses
+            self._check(self._lib.nwe_render_grid(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, r0, r1,
+                                                  C.byref(o), None), "nwe_render_grid")
+            raise RuntimeError("nwe_render_grid: a host-only context rendered")   # not reached
+        n_rays = poses.shape[0] * max(r1 - r0, 0) * W
+        S = self.n_samples + self.n_importance
+        shapes = {"rgb": (n_rays, 3), "depth": (n_rays,), "acc": (n_rays,), "weights_coarse": (n_rays, self.n_samples),
+                  "z_fine": (n_rays, S), "raw_fine": (n_rays, S, 4)}
+        with torch.cuda.device(self.device):
+            # at least one element each: an empty tensor has no pointer, and a call of zero rays still says what it asks for
+            bufs = {name: torch.empty(max(int(np.prod(shapes[name])), 1), dtype=torch.float32, device=self.device) for name in outputs}
+            res = {name: bufs[name][:int(np.prod(shapes[name]))].view(shapes[name]) for name in outputs}
+            res["flags"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            for name in _lib.GRID_OUTPUT_FIELDS:
+                setattr(o, name, (bufs[name] if name in bufs else res[name]).data_ptr() if name in res else None)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self._lib.nwe_render_grid(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, r0, r1,
+                                           C.byref(o), stream)
+        self._check(rc, "nwe_render_grid")
+        return res
+
+    def last_grid_ms(self) -> Optional[float]:
+        """Device time of the last ``render_grid`` launch in ms (blocks until it has finished), None if there was none."""
+        ms = float(self._lib.nwe_last_grid_ms(self._ctx))
+        return ms if ms >= 0 else None
+
     def last_coarse_launch(self) -> Optional[Tuple[float, int]]:
         """(ms, rays) of the coarse (producer) launch of the last render, None if it had none (k = 1 without separate passes,
         n_importance == 0)."""
