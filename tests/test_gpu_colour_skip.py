@@ -3,7 +3,9 @@
 In the pass that produces the outputs, a wave whose 32 rays all have sigma_raw <= 0 at a sample leaves out the colour layers of
 that evaluation: the sample weighs 0 on every ray.  The unit is (packet of 32 consecutive rays, sample) in both work
 decompositions.  The small frames of the other GPU tests never take the path - their 32 consecutive rays span the whole field of
-view - so the rays here are coherent: a few rows of the 800-wide benchmark frame under the benchmark's pose.
+view - so the rays here are coherent: a few rows of the 800-wide benchmark frame under the benchmark's pose.  This file takes the
+path in the plain and tail kernels at 8x256 and 4x128 (tests/test_gpu_packet_blocks.py likewise); the terminating, occupancy and
+sharing kernels, and the plain kernels of 4x256 and 8x128, take it in tests/test_gpu_hollow_variants.py.
 
 Predictions come from the kernel's own sigma: raw_fine (raw_coarse without importance sampling) of the FULL instantiation of
 the same call, which never takes the path.  Every comparison is torch.equal."""
