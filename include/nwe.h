@@ -642,6 +642,64 @@ int nwe_render_grid(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, f
                     float far, int row_begin, int row_end, const nwe_grid_outputs *out, void *stream);
 float nwe_last_grid_ms(nwe_ctx *ctx);
 
+/* Sparse frame, opt-in: the radiance grid above as a PROPOSAL, the network only where the proposal sees weight.  An entry point of
+ * its own, as nwe_render_grid is: it reads none of the modes, and no other call, plan, report or refusal knows of it.
+ * The rule of nwe_render_sparse, for each ray of the call:
+ *   1. Proposal.  The depths, points, grid rows, coarse weights, sample_pdf, merge and the output pass are exactly those of
+ *      nwe_render_grid on the context's radiance grid and sampling tables, computed with the same device arithmetic.  S = the sample
+ *      count of the output pass: n_samples + n_importance, or n_samples when n_importance == 0.  z[s], row_grid[s], w_grid[s]: its
+ *      depths, its interpolated rows and the weights its compositing returns.
+ *   2. Selection.  hit[s] = !(w_grid[s] <= min_weight): a NaN weight is a hit, and any min_weight < 0 hits every sample.
+ *      selected[s] = the OR of hit over s - dilate .. s + dilate, clipped to 0 .. S - 1.
+ *   3. Evaluation.  Every selected sample is evaluated with network `which` through the raw path of nwe_query_points in `precision`
+ *      (the launcher call nwe_bake_radiance_grid makes), at the fp32 point p = o + d * z[s], multiply then add, with the ray's
+ *      normalised view direction; no direction for a network set without view directions.  It does not go through nwe_query_points:
+ *      nwe_last_query_ms and the query's event ring do not move.
+ *   4. Output.  row[s] = the network's row where selected[s], row_grid[s] elsewhere; raw2outputs over row[.], z[.] in order, with
+ *      nwe_set_white_background honoured.  Flags: the rgb / depth / acc bits only.
+ * The network is not consulted outside the grid's box: a sample outside it has a zero row and a zero weight, so a ray whose samples
+ * all lie outside has no hit (unless min_weight < 0) and renders as nwe_render_grid renders it.  Choose the box to hold the scene.
+ * Nothing else of the context is read: no mode, hook, training table, occupancy or coarse grid.  A ray's outputs depend on the ray,
+ * the grid, the sampling tables, the network and the two parameters only, so row tiles, pose batches and the chunks below are
+ * bit-identical to the whole call.
+ * SYNCHRONOUS: the call is queued on `stream` and waited for, as the bakes are.  The number of selected points is known only on the
+ * device; it is read back once per chunk (a pinned word, a stream synchronisation) so that the query launch gets its n_points.
+ * The call walks its rays in chunks of at most 2^22 / S rays (at least one), which bounds its scratch - depths, grid rows, mask,
+ * compacted points, directions and query rows, about 60 bytes per sample - to about 256 MiB; the scratch is the context's own,
+ * grow-only.  A chunk with no selected sample launches no query.
+ * Refuses in this order, before anything is queued: a NULL context; NULL out, a wrong struct_bytes, none of rgb / depth / acc / the
+ * diagnostics requested; the camera and the ray count as nwe_render refuses them; `which` not 0 or 1; an unknown precision; a NaN
+ * min_weight; dilate outside 0 .. 8 (NWE_ERR_INVALID); no radiance grid; sampling not set; network `which` not set (NWE_ERR_STATE);
+ * a host-only context (NWE_ERR_STATE); last, an MFMA precision for a shape without a query kernel (NWE_ERR_UNSUPPORTED, the
+ * query's own message).  Zero rays is NWE_OK and launches nothing.
+ * It moves none of nwe_last_kernel_ms, nwe_last_launch_parts, nwe_debug_last_plan, nwe_last_ray_evaluations,
+ * nwe_last_coarse_launch, nwe_last_query_ms and nwe_last_grid_ms; its launches have an event ring of their own, which the waits of
+ * nwe_set_network / nwe_set_sampling and of the grid calls cover.
+ *   nwe_debug_set_sparse_chunk  test hook: the rays of a chunk; 0 = the default, otherwise at least 1 and never more than the default.
+ *   nwe_last_sparse_ms          the device span of the most recent nwe_render_sparse call that ran, first launch to last, the
+ *                               read-backs between included; < 0 if there was none.
+ *   nwe_last_sparse_samples     out[0] = the samples that call selected, out[1] = its rays * S; NWE_ERR_STATE (and nothing written)
+ *                               if there was none. */
+typedef struct nwe_sparse_outputs {
+    uint64_t struct_bytes;  /* = sizeof(nwe_sparse_outputs) */
+    float *rgb;             /* [R,3] */
+    float *depth;           /* [R]   */
+    float *acc;             /* [R]   */
+    /* diagnostics, each may be NULL */
+    float *weights_coarse;  /* [R, n_samples] */
+    float *z_fine;          /* [R, S]      the depths of the output pass */
+    float *weights_grid;    /* [R, S]      w_grid */
+    uint8_t *selected;      /* [R, S]      0 / 1 */
+    float *raw_fine;        /* [R, S, 4]   the rows that were composited */
+    uint32_t *flags;        /* [1]    NWE_FLAG_RGB / _DEPTH / _ACC, OR-ed (caller zeroes it) */
+} nwe_sparse_outputs;
+int nwe_render_sparse(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near,
+                      float far, int row_begin, int row_end, int which, int precision, float min_weight, int dilate,
+                      const nwe_sparse_outputs *out, void *stream);
+int nwe_debug_set_sparse_chunk(nwe_ctx *ctx, int rays);
+float nwe_last_sparse_ms(nwe_ctx *ctx);
+int nwe_last_sparse_samples(nwe_ctx *ctx, int64_t *out2);
+
 /* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
  * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1 without separate
  * passes, n_importance == 0, or a call armed with nwe_debug_set_coarse_weights).  Under separate passes with k = 1 it is the

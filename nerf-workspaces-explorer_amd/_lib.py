@@ -34,6 +34,7 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_coarse_grid_weights",
            "nwe_set_radiance_grid", "nwe_clear_radiance_grid", "nwe_get_radiance_grid", "nwe_radiance_grid_copy", "nwe_bake_radiance_grid",
            "nwe_render_grid", "nwe_last_grid_ms",
+           "nwe_render_sparse", "nwe_debug_set_sparse_chunk", "nwe_last_sparse_ms", "nwe_last_sparse_samples",
            "nwe_debug_set_packet_blocks", "nwe_debug_last_packet_blocks", "nwe_debug_packet_pixels")
 
 
@@ -65,6 +66,17 @@ class GridOutputs(C.Structure):
 
     def __init__(self, **kw):
         super().__init__(struct_bytes=C.sizeof(GridOutputs), **kw)
+
+
+SPARSE_OUTPUT_FIELDS = ("rgb", "depth", "acc", "weights_coarse", "z_fine", "weights_grid", "selected", "raw_fine", "flags")
+
+
+class SparseOutputs(C.Structure):
+    """nwe_sparse_outputs of nwe_render_sparse."""
+    _fields_ = [("struct_bytes", C.c_uint64)] + [(name, C.c_void_p) for name in SPARSE_OUTPUT_FIELDS]
+
+    def __init__(self, **kw):
+        super().__init__(struct_bytes=C.sizeof(SparseOutputs), **kw)
 
 
 PLAN_HOOK_COARSE_WEIGHTS, PLAN_HOOK_OTHER = 1, 2
@@ -180,6 +192,10 @@ def load() -> C.CDLL:
         "nwe_bake_radiance_grid": (I, [P, C.POINTER(F), C.POINTER(F), C.POINTER(I), I, C.POINTER(F), I, P]),
         "nwe_render_grid": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, C.POINTER(GridOutputs), P]),
         "nwe_last_grid_ms": (F, [P]),
+        "nwe_render_sparse": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, I, I, F, I, C.POINTER(SparseOutputs), P]),
+        "nwe_debug_set_sparse_chunk": (I, [P, I]),
+        "nwe_last_sparse_ms": (F, [P]),
+        "nwe_last_sparse_samples": (I, [P, C.POINTER(I64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

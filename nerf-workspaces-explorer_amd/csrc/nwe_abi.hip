@@ -163,6 +163,15 @@ struct nwe_ctx {
     // last_grid: the most recent grid launch that was recorded (nwe_last_grid_ms)
     Slot grid_slots[kSlots];
     int next_grid = 0, last_grid = -1;
+    // nwe_render_sparse: one more ring of its own; last_sparse: the most recent sparse call that ran (nwe_last_sparse_ms), what it
+    // selected of how many samples (nwe_last_sparse_samples); the chunks' scratch, grow-only, the device word the scan leaves a
+    // chunk's total in (behind the scratch's tables) and the pinned word it is read back through
+    Slot sparse_slots[kSlots];
+    int next_sparse = 0, last_sparse = -1;
+    int64_t sparse_selected = 0, sparse_total = 0;
+    int sparse_chunk = 0;     // nwe_debug_set_sparse_chunk: 0 = the default
+    DevBuf<uint8_t> d_sparse_scratch;
+    Owned<void*, hipHostFree> sparse_word;
     const float* dbg_z_fine = nullptr;
     const float *dbg_raw_c = nullptr, *dbg_raw_f = nullptr, *dbg_w = nullptr;   // nwe_debug_set_raw / _coarse_weights, one call
     int fold = 1;             // nwe_debug_set_fold: read by nwe_set_network
@@ -316,6 +325,8 @@ int wait_for_launches(nwe_ctx* c) {
     for (Slot& s : c->query_slots)   // a query streams the weights of its network throughout
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     for (Slot& s : c->grid_slots)    // a grid frame reads the sampling tables and the radiance grid
+        if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
+    for (Slot& s : c->sparse_slots)  // a sparse frame reads all of it; it has been waited for, unless it failed half way
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     return NWE_OK;
 }
@@ -1439,6 +1450,98 @@ int nwe_render_grid(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, flo
 float nwe_last_grid_ms(nwe_ctx* c) {
     if (!c || c->host_only || c->last_grid < 0 || !c->grid_slots[c->last_grid].used) return -1.f;
     return elapsed_ms(c, c->grid_slots[c->last_grid], "nwe_last_grid_ms");
+}
+
+int nwe_render_sparse(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near, float far,
+                      int row_begin, int row_end, int which, int precision, float min_weight, int dilate, const nwe_sparse_outputs* out,
+                      void* stream_) {
+    const Camera m{c2w, n_poses, H, W, fx, fy, cx, cy, near, far, row_begin, row_end};
+    CHECK(c, check_render_sparse(MaybeContext(c).p, out, m, which, precision, min_weight, dilate));
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t n_rays = (int64_t)n_poses * (row_end - row_begin) * W;
+    if (n_rays == 0) return NWE_OK;
+    ON_DEVICE(c);
+    Slot& slot = c->sparse_slots[c->next_sparse];   // not a slot of the render ring (see nwe_create_rays)
+    TRY(prepare_slot(c, slot));
+    TRY(upload_poses(c, slot, c2w, n_poses, stream));
+    RenderArgs a = camera_args(m, slot.poses.get());
+    a.white_bkgd = c->white_bkgd;   // nothing else of the context: the sampling tables and counts, no mode
+    a.t_vals = c->d_t.get(); a.omt_vals = a.t_vals + kMaxSamples; a.u_vals = a.omt_vals + kMaxSamples;
+    a.n_samples = c->ns; a.n_importance = c->ni;
+    a.out.struct_bytes = sizeof(nwe_outputs);
+    a.out.rgb = out->rgb; a.out.depth = out->depth; a.out.acc = out->acc; a.out.flags = out->flags;
+    const NetState& net = c->net[which];
+    const int S = c->ns + c->ni;
+    // the rays of a chunk: 2^22 / S, which the test hook may lower; the scratch is laid out for that many
+    int64_t cap = std::max<int64_t>(1, kSparseChunkSamples / S);
+    if (c->sparse_chunk > 0) cap = std::min<int64_t>(cap, c->sparse_chunk);
+    cap = std::min(cap, n_rays);
+    const size_t M = (size_t)cap * S;
+    size_t bytes = 0;
+    const auto take = [&](size_t n) { const size_t at = bytes; bytes += (n + 255) / 256 * 256; return at; };
+    const size_t at_grid = take(M * 16), at_rows = take(M * 16), at_z = take(M * 4), at_points = take(M * 12), at_dirs = take(M * 12),
+                 at_offsets = take((size_t)cap * 4), at_total = take(4), at_mask = take(M);
+    HIPCHK(c, c->d_sparse_scratch.reserve(bytes));   // grow-only; nothing of an earlier call still reads it: the call is synchronous
+    if (!c->sparse_word) HIPCHK(c, hipHostMalloc(&c->sparse_word.h, sizeof(uint32_t), hipHostMallocDefault));
+    uint8_t* const base = c->d_sparse_scratch.get();
+    volatile uint32_t* const word = static_cast<uint32_t*>(c->sparse_word.h);
+    SparseChunk k = {};
+    k.S = S; k.min_weight = min_weight; k.dilate = dilate;
+    k.row_grid = reinterpret_cast<float4*>(base + at_grid); k.rows = reinterpret_cast<const float4*>(base + at_rows);
+    k.z = reinterpret_cast<float*>(base + at_z); k.points = reinterpret_cast<float*>(base + at_points);
+    k.dirs = net.in_dir != 0 ? reinterpret_cast<float*>(base + at_dirs) : nullptr;
+    k.offsets = reinterpret_cast<uint32_t*>(base + at_offsets); k.total = reinterpret_cast<uint32_t*>(base + at_total);
+    k.mask = base + at_mask;
+    k.weights_coarse = out->weights_coarse; k.z_fine = out->z_fine; k.weights_grid = out->weights_grid; k.raw_fine = out->raw_fine;
+    k.selected = out->selected;
+    const RadianceGrid grid = radiance_grid_args(c);
+    int64_t selected = 0;
+    const int rc = record_launch(c, slot, stream, [&]() -> int {
+        for (int64_t first = 0; first < n_rays; first += cap) {
+            k.first = first; k.count = (int)std::min<int64_t>(cap, n_rays - first);
+            launch_sparse_mark(a, grid, k, stream);
+            launch_sparse_scan(k, stream);
+            launch_sparse_emit(a, k, stream);
+            HIPCHK(c, hipGetLastError());
+            // the one read-back of the chunk: the query's launch needs its n_points on the host
+            HIPCHK(c, hipMemcpyAsync(c->sparse_word.h, k.total, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(c, hipStreamSynchronize(stream));
+            const uint32_t n_points = *word;
+            if ((uint64_t)n_points > (uint64_t)k.count * S) return fail(c, NWE_ERR_HIP, "sparse frame: the chunk's point count is out of range");
+            selected += n_points;
+            if (n_points > 0) {   // the raw path of nwe_query_points, one direction per point; a chunk with nothing selected launches no query
+                QueryArgs q = {};
+                q.points = k.points; q.dirs = k.dirs; q.raw = reinterpret_cast<float*>(base + at_rows); q.n_points = (int)n_points; q.points_per_dir = 1;
+                if (precision == NWE_PREC_F32) launch_query_f32(q, net.f32, c->query_steps, c->cus, stream);
+                else if (!launch_query_mfma(q, net.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
+                    return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
+            }
+            launch_sparse_composite(a, k, stream);
+        }
+        return NWE_OK;
+    });
+    // synchronous, on every path: nothing of the call may still run, or read the scratch, when it returns
+    const hipError_t waited = hipStreamSynchronize(stream);
+    if (rc) return rc;
+    HIPCHK(c, waited);
+    c->last_sparse = (int)(&slot - c->sparse_slots);
+    c->next_sparse = (c->last_sparse + 1) % nwe_ctx::kSlots;
+    c->sparse_selected = selected; c->sparse_total = n_rays * S;
+    return NWE_OK;
+}
+
+int nwe_debug_set_sparse_chunk(nwe_ctx* c, int rays) { return set_on(rays < 0 ? nullptr : c, [&] { c->sparse_chunk = rays; }); }
+
+float nwe_last_sparse_ms(nwe_ctx* c) {
+    if (!c || c->host_only || c->last_sparse < 0 || !c->sparse_slots[c->last_sparse].used) return -1.f;
+    return elapsed_ms(c, c->sparse_slots[c->last_sparse], "nwe_last_sparse_ms");
+}
+
+int nwe_last_sparse_samples(nwe_ctx* c, int64_t* out2) {
+    if (!c || !out2) return NWE_ERR_INVALID;
+    if (c->last_sparse < 0) return NWE_ERR_STATE;
+    out2[0] = c->sparse_selected; out2[1] = c->sparse_total;
+    return NWE_OK;
 }
 
 int nwe_set_train_tables(nwe_ctx* c, const float* t_rand_dev, const float* noise_coarse_dev, const float* noise_fine_dev, const float* u_sorted_dev) {

@@ -336,4 +336,27 @@ Refusal check_render_grid(const ContextDesc* d, const nwe_grid_outputs* out, con
     return check_on_device(!d->host_only);
 }
 
+Refusal check_render_sparse(const ContextDesc* d, const nwe_sparse_outputs* out, const Camera& m, int which, int precision, float min_weight,
+                            int dilate) {
+    if (!d) return invalid("null context");
+    if (!out) return invalid("null outputs");
+    if (out->struct_bytes != sizeof(nwe_sparse_outputs))
+        return invalid("nwe_sparse_outputs.struct_bytes != sizeof(nwe_sparse_outputs): the caller was built against another version of include/nwe.h");
+    if (!out->rgb && !out->depth && !out->acc && !out->weights_coarse && !out->z_fine && !out->weights_grid && !out->selected && !out->raw_fine)
+        return invalid("none of rgb / depth / acc / weights_coarse / z_fine / weights_grid / selected / raw_fine requested");
+    if (Refusal r = check_camera(m)) return r;
+    if (Refusal r = check_ray_count((int64_t)m.n_poses * (m.row_end - m.row_begin) * m.W, false)) return r;
+    if (which != NWE_NET_COARSE && which != NWE_NET_FINE) return invalid("which must be 0 or 1");
+    if (Refusal r = check_precision(precision)) return r;
+    if (min_weight != min_weight) return invalid("sparse frame: min_weight must not be NaN");
+    if (dilate < 0 || dilate > kSparseMaxDilate) return invalid("sparse frame: dilate must be in 0..8");
+    if (!d->rgrid.set) return state("sparse frame: no radiance grid is set (nwe_set_radiance_grid, nwe_bake_radiance_grid)");
+    if (d->ns <= 0) return state("nwe_set_sampling has not been called");
+    const NetDesc& net = d->net[which];
+    if (!net.set) return state(which == NWE_NET_COARSE ? "sparse frame: the coarse network is not set" : "sparse frame: the fine network is not set");
+    if (Refusal r = check_on_device(!d->host_only)) return r;
+    if (precision != NWE_PREC_F32 && !net.mfma_ok) return no_mfma_kernel();
+    return {};
+}
+
 }  // namespace nwe

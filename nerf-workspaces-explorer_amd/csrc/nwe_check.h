@@ -109,5 +109,10 @@ Refusal check_bake_radiance_grid(const ContextDesc* d, const float* lo, const fl
 // nwe_render_grid, in the order it refuses in: the context, the outputs, the camera, the ray count, grid and sampling, and last -
 // so that everything in front can be asked of a host-only context - the device.
 Refusal check_render_grid(const ContextDesc* d, const nwe_grid_outputs* out, const Camera& m);
+// nwe_render_sparse, in the order it refuses in: the context, the outputs, the camera, the ray count, `which`, the precision, the two
+// parameters, grid, sampling and network, the device, and last the query's refusal of a shape without an MFMA kernel.
+Refusal check_render_sparse(const ContextDesc* d, const nwe_sparse_outputs* out, const Camera& m, int which, int precision, float min_weight,
+                            int dilate);
+constexpr int kSparseMaxDilate = 8;
 
 }  // namespace nwe

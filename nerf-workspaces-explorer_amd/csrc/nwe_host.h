@@ -116,6 +116,38 @@ constexpr int kGridThreads = 64;   // rays of a workgroup of radiance_grid_rende
 // the grid; a.out: rgb / depth / acc / flags and the diagnostics weights_coarse / z_fine / raw_fine, each may be null.
 void launch_radiance_grid_render(const RenderArgs& a, const RadianceGrid& g, hipStream_t stream);
 
+// ---- sparse frame (nwe_render_sparse; nwe_sparse.hip) ----
+constexpr int64_t kSparseChunkSamples = (int64_t)1 << 22;   // samples of a chunk at the most: rays * S
+// One chunk of a sparse call: rays [first, first + count) of the call `a` describes (camera, tables, counts, white_bkgd, a.n_rays =
+// the whole call's).  The [count, S] tables are stored SAMPLE-major, element (s, r) at s * count + r, so that the threads of a
+// wave, one per ray, read and write consecutive addresses as they walk their samples.  The compacted lists are ray-major: the
+// selected samples of ray r, in sample order, start at offsets[r].
+struct SparseChunk {
+    int64_t first;          // first ray of the chunk within the call
+    int count;              // its rays
+    int S;                  // samples of the output pass
+    float min_weight;
+    int dilate;
+    float* z;               // [S][count]
+    float4* row_grid;       // [S][count]
+    uint8_t* mask;          // [S][count]  selected, 0 / 1
+    uint32_t* offsets;      // [count] the rays' selected counts (mark), then their exclusive scan (scan)
+    uint32_t* total;        // [1]  the chunk's selected samples (scan)
+    float* points;          // [N, 3]  N <= count * S
+    float* dirs;            // [N, 3]  or null: a network without view directions
+    const float4* rows;     // [N]     the query's rows at `points`
+    // the call's outputs, indexed by the ray of the CALL; each may be null
+    float *weights_coarse, *z_fine, *weights_grid, *raw_fine;
+    uint8_t* selected;
+};
+// mark: the proposal of every ray of the chunk (z, row_grid, the mask, the counts; weights_coarse / weights_grid straight to the
+// caller); scan: counts -> offsets and the total; emit: points and directions of the selected samples; composite: the mix, store_ray
+// into a.out, the other diagnostics and the flags.
+void launch_sparse_mark(const RenderArgs& a, const RadianceGrid& g, const SparseChunk& c, hipStream_t stream);
+void launch_sparse_scan(const SparseChunk& c, hipStream_t stream);
+void launch_sparse_emit(const RenderArgs& a, const SparseChunk& c, hipStream_t stream);
+void launch_sparse_composite(const RenderArgs& a, const SparseChunk& c, hipStream_t stream);
+
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);
 

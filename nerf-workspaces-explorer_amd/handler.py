@@ -53,8 +53,14 @@ class NeRFReplicaInferenceHandler:
                  devices: Optional[Sequence[int]] = None, early_termination: float = 0.0, shared_coarse: int = 1,
                  separate_passes: Optional[bool] = None, occupancy: Optional[Mapping[str, object]] = None,
                  baked_coarse: Optional[Mapping[str, object]] = None,
-                 radiance_grid: Optional[Mapping[str, object]] = None) -> None:
-        """``radiance_grid``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128, one int or
+                 radiance_grid: Optional[Mapping[str, object]] = None,
+                 sparse_fine: Optional[Mapping[str, object]] = None) -> None:
+        """``sparse_fine``: a mapping with optional "min_weight" (1e-3), "dilate" (1) and "which" ("fine"): with it
+        ``render_coordinates(preview=False)`` draws its frame through ``render_sparse_batch`` - the radiance grid as a proposal,
+        the network only at the samples the grid gives weight (Renderer.render_sparse) - an approximation, off by default.  It
+        needs ``radiance_grid`` too (a ValueError otherwise).  The environment variable NWE_SPARSE_FINE = "min_weight[,dilate]"
+        overrides the two, and switches the option on for a caller that gave a radiance grid.
+        ``radiance_grid``: a mapping with the box "lo", "hi" (world coordinates) and optionally "resolution" (128, one int or
         three), "which" ("fine") and "view_dir" (None: the mean over the six axis directions): initialize_models() bakes the
         network's raw output into a radiance grid over the box (bake_radiance_grid), from which ``render_grid`` and
         ``render_coordinates(preview="grid")`` render preview frames without running a network - an approximation; no other
@@ -159,6 +165,9 @@ class NeRFReplicaInferenceHandler:
             if self._devices:
                 raise ValueError("a radiance grid is rendered by one device: it is not supported together with devices")
             self._radiance_grid = grid
+        self._sparse_fine = self.parse_sparse_fine(sparse_fine, os.environ.get("NWE_SPARSE_FINE", ""))
+        if self._sparse_fine is not None and self._radiance_grid is None:
+            raise ValueError("sparse_fine needs a radiance grid as its proposal: give radiance_grid={'lo': ..., 'hi': ...} too")
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -191,6 +200,37 @@ class NeRFReplicaInferenceHandler:
         self._fx, self._fy, self._cx, self._cy = pinhole_intrinsics(self._img_h, self._img_w)
         self._renderer: Optional[Renderer] = None
         self._stage: Optional[torch.Tensor] = None   # pinned uint8 [H,W,3] staging buffer for render_coordinates
+
+    @staticmethod
+    def parse_sparse_fine(sparse_fine: Optional[Mapping[str, object]], env: str = "") -> Optional[Dict[str, object]]:
+        """The ``sparse_fine`` option with its defaults, NWE_SPARSE_FINE = "min_weight[,dilate]" (``env``) laid over it; None when
+        neither is given."""
+        env = [v.strip() for v in env.split(",") if v.strip() != ""]
+        if sparse_fine is None and not env:
+            return None
+        opt = {"min_weight": 1e-3, "dilate": 1, "which": "fine"}
+        if sparse_fine is not None:
+            unknown = set(sparse_fine) - set(opt)
+            if unknown:
+                raise ValueError(f"sparse_fine may hold min_weight, dilate, which; got {sorted(sparse_fine)}")
+            opt.update(sparse_fine)
+        if len(env) > 2:
+            raise ValueError("NWE_SPARSE_FINE must be min_weight[,dilate]")
+        try:
+            if env:
+                opt["min_weight"] = float(env[0])
+            if len(env) > 1:
+                opt["dilate"] = int(env[1])
+        except ValueError:
+            raise ValueError("NWE_SPARSE_FINE must be min_weight[,dilate]") from None
+        if isinstance(opt["min_weight"], bool) or not isinstance(opt["min_weight"], (int, float)) or opt["min_weight"] != opt["min_weight"]:
+            raise ValueError("sparse_fine: min_weight must be a number, not NaN")
+        if isinstance(opt["dilate"], bool) or not isinstance(opt["dilate"], int) or not 0 <= opt["dilate"] <= 8:
+            raise ValueError("sparse_fine: dilate must be an integer in 0..8")
+        if opt["which"] not in ("coarse", "fine"):
+            raise ValueError("sparse_fine: which must be 'coarse' or 'fine'")
+        opt["min_weight"] = float(opt["min_weight"])
+        return opt
 
     # ------------------------------------------------------------------------------------------------
     def set_sampling(self, n_samples: int, n_importance: int) -> None:
@@ -321,7 +361,12 @@ class NeRFReplicaInferenceHandler:
         if preview and self._n_importance > 0:
             r.set_sampling(self._n_samples, 0)
         try:
-            res = (self.render_grid_batch if from_grid else self.render_batch)(camera_pose.numpy(), H, W, outputs=("rgb",))
+            if from_grid:
+                res = self.render_grid_batch(camera_pose.numpy(), H, W, outputs=("rgb",))
+            elif self._sparse_fine is not None and not preview:
+                res = self.render_sparse_batch(camera_pose.numpy(), H, W, outputs=("rgb",), **self._sparse_fine)
+            else:
+                res = self.render_batch(camera_pose.numpy(), H, W, outputs=("rgb",))
         finally:
             if preview and self._n_importance > 0:
                 r.set_sampling(self._n_samples, self._n_importance)
@@ -498,6 +543,40 @@ class NeRFReplicaInferenceHandler:
         res = r.render_grid(poses, H, W, fx=fx, fy=fy, cx=cx, cy=cy, near=self._depth_close_bound, far=self._depth_far_bound,
                             rows=(r0, r1), outputs=outputs)
         return {k: v if k == "flags" else v.reshape((poses.shape[0], r1 - r0, W) + tuple(v.shape[1:])) for k, v in res.items()}
+
+    def _sparse_renderer(self) -> Renderer:
+        r = self._need_renderer()
+        if isinstance(r, TiledRenderer):
+            raise NotImplementedError("the sparse frame is rendered by one device (TiledRenderer has no sparse frame): not with devices")
+        return r
+
+    def render_sparse(self, camera_pose, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
+                      which="fine", precision: Optional[str] = None, min_weight: float = 1e-3, dilate: int = 1,
+                      outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+        """``render`` as a sparse frame (Renderer.render_sparse): the ``which`` network only where the radiance grid sees weight."""
+        res = self.render_sparse_batch(np.asarray(camera_pose, dtype=np.float32).reshape(1, 4, 4), H, W, rows=rows, which=which,
+                                       precision=precision, min_weight=min_weight, dilate=dilate, outputs=outputs)
+        return {k: v[0] for k, v in res.items()}
+
+    def render_sparse_batch(self, poses, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
+                            which="fine", precision: Optional[str] = None, min_weight: float = 1e-3, dilate: int = 1,
+                            outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+        """``render_batch`` as a sparse frame: [B,4,4] poses -> tensors with leading [B, h, W].  ``precision`` None: the
+        handler's own, "auto" resolved for the ``which`` network as run_network does."""
+        r = self._sparse_renderer()
+        w, auto = self._query_net(which)
+        H = self._img_h if H is None else H
+        W = self._img_w if W is None else W
+        fx, fy, cx, cy = pinhole_intrinsics(H, W)
+        poses = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4)
+        r0, r1 = rows if rows is not None else (0, H)
+        res = r.render_sparse(poses, H, W, fx=fx, fy=fy, cx=cx, cy=cy, near=self._depth_close_bound, far=self._depth_far_bound,
+                              rows=(r0, r1), which=w, precision=precision or auto, min_weight=min_weight, dilate=dilate, outputs=outputs)
+        return {k: v if k == "flags" else v.reshape((poses.shape[0], r1 - r0, W) + tuple(v.shape[1:])) for k, v in res.items()}
+
+    def last_sparse_samples(self):
+        """(selected, total) samples of the last sparse frame (Renderer.last_sparse_samples), None if there was none."""
+        return self._sparse_renderer().last_sparse_samples()
 
     @property
     def coarse_grid(self):

@@ -657,6 +657,65 @@ class Renderer:
         ms = float(self._lib.nwe_last_grid_ms(self._ctx))
         return ms if ms >= 0 else None
 
+    # -- sparse frame -----------------------------------------------------------------------------
+    def render_sparse(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
+                      rows: Optional[Tuple[int, int]] = None, which: int = _lib.NET_FINE, precision: str = "f16x3",
+                      min_weight: float = 1e-3, dilate: int = 1,
+                      outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+        """A sparse frame (nwe_render_sparse): the radiance grid's frame as a proposal, network ``which`` at the samples of the
+        output pass whose proposed weight is above ``min_weight`` (and ``dilate`` neighbours on either side), the grid's rows at
+        the others.  Synchronous.  ``outputs``: a choice of "rgb", "depth", "acc" and the diagnostics "weights_coarse"
+        [R, n_samples], "z_fine" [R, S], "weights_grid" [R, S], "selected" [R, S] (uint8) and "raw_fine" [R, S, 4] (S = n_samples +
+        n_importance, the output pass); "flags" is always returned."""
+        outputs = tuple(outputs)
+        unknown = set(outputs) - set(_lib.SPARSE_OUTPUT_FIELDS[:-1])
+        if unknown:
+            raise ValueError(f"unknown sparse outputs {sorted(unknown)}; have {_lib.SPARSE_OUTPUT_FIELDS[:-1]}")
+        poses = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(-1, 4, 4))
+        r0, r1 = rows if rows is not None else (0, H)
+        o = _lib.SparseOutputs()
+        tail = (r0, r1, int(which), _lib.PRECISIONS[precision], float(min_weight), int(dilate))
+        if self.device is None:   # a host-only context: the ABI's own refusals, nothing allocated
+            for name in outputs:
+                setattr(o, name, 1)   # never written: every path of a host-only context refuses
+            self._check(self._lib.nwe_render_sparse(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail,
+                                                    C.byref(o), None), "nwe_render_sparse")
+            raise RuntimeError("nwe_render_sparse: a host-only context rendered")   # not reached
+        n_rays = poses.shape[0] * max(r1 - r0, 0) * W
+        S = self.n_samples + self.n_importance
+        shapes = {"rgb": (n_rays, 3), "depth": (n_rays,), "acc": (n_rays,), "weights_coarse": (n_rays, self.n_samples),
+                  "z_fine": (n_rays, S), "weights_grid": (n_rays, S), "selected": (n_rays, S), "raw_fine": (n_rays, S, 4)}
+        with torch.cuda.device(self.device):
+            # at least one element each: an empty tensor has no pointer, and a call of zero rays still says what it asks for
+            bufs = {name: torch.empty(max(int(np.prod(shapes[name])), 1), dtype=torch.uint8 if name == "selected" else torch.float32,
+                                      device=self.device) for name in outputs}
+            res = {name: bufs[name][:int(np.prod(shapes[name]))].view(shapes[name]) for name in outputs}
+            res["flags"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            for name in _lib.SPARSE_OUTPUT_FIELDS:
+                setattr(o, name, (bufs[name] if name in bufs else res[name]).data_ptr() if name in res else None)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self._lib.nwe_render_sparse(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail,
+                                             C.byref(o), stream)
+        self._check(rc, "nwe_render_sparse")
+        return res
+
+    def last_sparse_ms(self) -> Optional[float]:
+        """Device span of the last ``render_sparse`` call in ms, None if there was none."""
+        ms = float(self._lib.nwe_last_sparse_ms(self._ctx))
+        return ms if ms >= 0 else None
+
+    def last_sparse_samples(self) -> Optional[Tuple[int, int]]:
+        """(selected, total) samples of the last ``render_sparse`` call, None if there was none."""
+        out = (C.c_int64 * 2)()
+        if self._lib.nwe_last_sparse_samples(self._ctx, out) != _lib.NWE_OK:
+            return None
+        return int(out[0]), int(out[1])
+
+    def debug_set_sparse_chunk(self, rays: int) -> None:
+        """Test hook (nwe_debug_set_sparse_chunk): the rays of a chunk of ``render_sparse``; 0 restores the default."""
+        if self._lib.nwe_debug_set_sparse_chunk(self._ctx, int(rays)) != _lib.NWE_OK:
+            raise ValueError("the sparse chunk must be 0 (the default) or a number of rays of at least 1")
+
     def last_coarse_launch(self) -> Optional[Tuple[float, int]]:
         """(ms, rays) of the coarse (producer) launch of the last render, None if it had none (k = 1 without separate passes,
         n_importance == 0)."""

@@ -80,3 +80,60 @@ def dense_fog(state: Dict[str, np.ndarray], sigma: float = 3.0, spread: float = 
     of the rays of a room-sized frame above 1e-2 to the end while their neighbours stop - workgroups in which some rays
     stop and some never do."""
     return thin_fog(state, sigma, spread)
+
+
+def _room_trunk(state: Dict[str, np.ndarray], half_extent: float, slope: float) -> Dict[str, np.ndarray]:
+    """The six wall units of `room` in the trunk of a copy of `state`: hidden units 0..5 of every `_pts_linears` layer."""
+    out = {k: v.copy() for k, v in state.items()}
+    in_xyz = out["_pts_linears.0.weight"].shape[1]
+    W = out["_pts_linears.0.weight"].shape[0]
+    depth = sum(1 for k in out if k.startswith("_pts_linears.") and k.endswith(".weight"))
+    if W < 8:
+        raise ValueError("room needs a trunk of at least 8 units: six of them are the walls")
+    w0, b0 = out["_pts_linears.0.weight"], out["_pts_linears.0.bias"]
+    for axis in range(3):
+        for k, sign in enumerate((1.0, -1.0)):
+            unit = 2 * axis + k
+            w0[unit] = 0.0
+            w0[unit, axis] = np.float32(sign * 10.0 * slope)      # the identity slot of gamma(x) holds x / 10
+            b0[unit] = np.float32(-slope * half_extent)
+    for i in range(1, depth):
+        w, b = out[f"_pts_linears.{i}.weight"], out[f"_pts_linears.{i}.bias"]
+        first = w.shape[1] - W          # in_xyz at the layer behind the skip (cat([input_pts, h])), else 0
+        assert first in (0, in_xyz)
+        w[:, first:first + 6] = 0.0     # no other unit reads the six
+        w[:6] = 0.0
+        b[:6] = 0.0
+        for unit in range(6):
+            w[unit, first + unit] = 1.0  # relu(1 * h) = h: the unit copies itself
+    return out
+
+
+def room(state: Dict[str, np.ndarray], half_extent: float = 3.0, slope: float = 1.0, gain: float = 8.0, floor: float = -2.0,
+         spread: float = 0.01) -> Dict[str, np.ndarray]:
+    """Copy of `state` with an empty interior and walls at +-`half_extent` on all three axes, built exactly, without training.
+
+    Six hidden units, indices 0..5, are reserved.  In `_pts_linears.0` unit 2a + k reads only the identity slot a of gamma(x) and
+    gives relu(slope * (+-x_a - half_extent)): the distance behind a wall.  Every later trunk layer copies the six and lets no
+    other unit read them; `_feature_linear` ignores them; `_alpha_linear` weighs them with `gain` and everything else with
+    `spread` times its random weights, with bias `floor`.  So sigma_raw ~ floor < 0 inside the room - empty space, where the fogs
+    of this module have density everywhere - and rises linearly behind a wall.  The colours stay the random network's."""
+    out = _room_trunk(state, half_extent, slope)
+    out["_feature_linear.weight"][:, :6] = 0.0
+    alpha = (out["_alpha_linear.weight"] * np.float32(spread)).astype(np.float32)
+    alpha[0, :6] = np.float32(gain)
+    out["_alpha_linear.weight"] = alpha
+    out["_alpha_linear.bias"] = np.full_like(out["_alpha_linear.bias"], floor)
+    return out
+
+
+def room_output(state: Dict[str, np.ndarray], half_extent: float = 3.0, slope: float = 1.0, gain: float = 8.0, floor: float = -2.0,
+                spread: float = 0.01) -> Dict[str, np.ndarray]:
+    """`room` for a use_view_dirs=False network: row 3 of `_output_linear` is the density, the other rows ignore the six units."""
+    out = _room_trunk(state, half_extent, slope)
+    w = out["_output_linear.weight"]
+    w[3] = (w[3] * np.float32(spread)).astype(np.float32)
+    w[:, :6] = 0.0
+    w[3, :6] = np.float32(gain)
+    out["_output_linear.bias"][3] = np.float32(floor)
+    return out
