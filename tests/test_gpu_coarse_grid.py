@@ -6,6 +6,9 @@ sigma, bit for bit.  The frame is then the ordinary call fed those weights, bit 
 tiling and pose batch.  Parity with the oracle composed with the restated grid holds on every ray of the scene that
 tests/test_coarse_grid_host.py vetted, at the project's parity tolerances (rgb 1e-4, depth 1e-4 * far, acc 1e-4; 1e-3 for
 f16x1).  "Bit for bit" lets a NaN equal a NaN whatever its sign and payload: an inf - inf of the host and of the GPU differ there.
+The last test bakes across the border of the bake's chunks of 2^20 cells; tests/test_gpu_grid_sizes.py bakes beyond 2^20 cells too,
+beside the radiance bake and with the query run whole and split, and looks the grid up along an axis of 512 cells, which no grid
+that is looked up here has. The same file covers the sparse frame's chunks beyond one scan tile and its default chunk.
 """
 import numpy as np
 import pytest

@@ -6,6 +6,9 @@ bit; the frame against the ordinary machinery (nwe_render_rays under f32) fed th
 tiles, pose batches and streams give the whole call's bits.  Parity with the oracle composed with the restated grid holds on every
 ray of the scene that tests/test_radiance_grid_host.py vetted, at the project's parity tolerances (rgb 1e-4, depth 1e-4 * far,
 acc 1e-4).  "Bit for bit" lets a NaN equal a NaN whatever its sign and payload: an inf - inf of the host and of the GPU differ there.
+The grids here are small: 13 824 cells at the most.  A bake beyond 2^20 cells - nwe_bake_radiance_grid walks the
+cells in chunks of that many - and the lookup along an axis of 512 cells are covered by tests/test_gpu_grid_sizes.py, which also
+covers the sparse frame's chunks beyond one scan tile and its default chunk.
 """
 import math
 

@@ -7,6 +7,9 @@ machinery (nwe_render_rays under f32) fed the call's weights, rows and depths.  
 min_weight = -1 it is nwe_render's under a baked coarse pass.  Chunks, row tiles, pose batches and streams give the whole call's
 bits, and the call moves nothing of the other calls' reports.  Parity with the composed oracle holds on the room scene at the
 project's tolerances.  "Bit for bit" lets a NaN equal a NaN whatever its sign and payload.
+The frames here have at most 481 rays a chunk (700 under the hook).  Chunks beyond one scan tile of 1024 rays, the default chunk
+of 2^22 / S rays that splits a call, the scratch buffer grown and reused, and a grid axis of 512 cells under the proposal's
+lookup are covered by tests/test_gpu_grid_sizes.py; so are the bakes beyond 2^20 cells.
 """
 import numpy as np
 import pytest
