@@ -676,8 +676,8 @@ float nwe_last_grid_ms(nwe_ctx *ctx);
  * nwe_last_coarse_launch, nwe_last_query_ms and nwe_last_grid_ms; its launches have an event ring of their own, which the waits of
  * nwe_set_network / nwe_set_sampling and of the grid calls cover.
  *   nwe_debug_set_sparse_chunk  test hook: the rays of a chunk; 0 = the default, otherwise at least 1 and never more than the default.
- *   nwe_last_sparse_ms          the device span of the most recent nwe_render_sparse call that ran, first launch to last, the
- *                               read-backs between included; < 0 if there was none.
+ *   nwe_last_sparse_ms          the device span of the most recent sparse call that ran (this one or nwe_render_sparse_async
+ *                               below), first launch to last, the read-backs between included; < 0 if there was none.
  *   nwe_last_sparse_samples     out[0] = the samples that call selected, out[1] = its rays * S; NWE_ERR_STATE (and nothing written)
  *                               if there was none. */
 typedef struct nwe_sparse_outputs {
@@ -699,6 +699,37 @@ int nwe_render_sparse(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W,
 int nwe_debug_set_sparse_chunk(nwe_ctx *ctx, int rays);
 float nwe_last_sparse_ms(nwe_ctx *ctx);
 int nwe_last_sparse_samples(nwe_ctx *ctx, int64_t *out2);
+
+/* The sparse frame, ASYNCHRONOUS, opt-in: nwe_render_sparse's arguments, rule, refusals (the same check: codes, texts and order, all
+ * before anything is queued; zero rays is NWE_OK) and bits - every output and nwe_last_sparse_samples equal those of
+ * nwe_render_sparse on the same context and arguments - but the call queues everything and returns, as nwe_render, nwe_render_grid
+ * and nwe_query_points do.  The point count of a chunk stays on the device: the query kernels of this call read it there
+ * (query_mfma_counted_kernel, query_f32_counted_kernel: a launch sized for the chunk's samples whose workgroups walk the packets
+ * below the count in strides of the grid, and return at once where there is none).  A chunk with nothing selected therefore still
+ * launches a query, whose workgroups all return.
+ * In the steady state the call makes no read-back, no stream or event synchronisation and no blocking copy.  It waits on the host
+ * only where it must: when the context's scratch has to grow, and when all four slots of the sparse ring are in flight - for the
+ * sparse launches that still use them (nwe_debug_last_sparse_host_waits counts these waits).
+ * One stream, one chunk buffer: the chunks, their size (2^22 / S rays; nwe_debug_set_sparse_chunk lowers it here too) and the
+ * scratch are the synchronous call's, and a chunk follows the one before it in stream order.  (A second buffer with the odd chunks
+ * on a side stream was measured and dropped: DESIGN.md 5.9.)  No hipGraph, no stream priorities.
+ * Ordering: the call first makes `stream` wait, on the device, for the end of the previous sparse call of either kind, so two calls on
+ * two streams never share the scratch.  nwe_set_network*, nwe_set_sampling, nwe_set_radiance_grid, nwe_clear_radiance_grid, the
+ * bakes, nwe_render_sparse and nwe_destroy wait for it.  The outputs and the pose array (if pinned) must stay valid until `stream`
+ * has passed the call.
+ * Reports: nwe_last_sparse_ms and nwe_last_sparse_samples describe the most recent sparse call of either kind; after an
+ * asynchronous call they wait for its end event (the tally is copied into a pinned word of the call's slot behind the last chunk).
+ * No other report moves, exactly as for nwe_render_sparse.
+ *   nwe_debug_last_sparse_host_waits  test hook: how many times the most recent sparse call of either kind made the host wait for
+ *                                     the device: its chunks + 1 for nwe_render_sparse, 0 for a warmed asynchronous call; -1 if
+ *                                     there was none.
+ *   nwe_debug_query_counted_grid      the workgroups of a counted query launch (no context needed): min(ceil(capacity / packet),
+ *                                     8 cus), or ceil(ceil(capacity / packet) / forced_steps) under nwe_debug_set_query_steps. */
+int nwe_render_sparse_async(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near,
+                            float far, int row_begin, int row_end, int which, int precision, float min_weight, int dilate,
+                            const nwe_sparse_outputs *out, void *stream);
+int nwe_debug_last_sparse_host_waits(nwe_ctx *ctx);
+unsigned nwe_debug_query_counted_grid(int64_t capacity, int packet, int forced_steps, int cus);
 
 /* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
  * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1 without separate

@@ -35,6 +35,7 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_set_radiance_grid", "nwe_clear_radiance_grid", "nwe_get_radiance_grid", "nwe_radiance_grid_copy", "nwe_bake_radiance_grid",
            "nwe_render_grid", "nwe_last_grid_ms",
            "nwe_render_sparse", "nwe_debug_set_sparse_chunk", "nwe_last_sparse_ms", "nwe_last_sparse_samples",
+           "nwe_render_sparse_async", "nwe_debug_last_sparse_host_waits", "nwe_debug_query_counted_grid",
            "nwe_debug_set_packet_blocks", "nwe_debug_last_packet_blocks", "nwe_debug_packet_pixels")
 
 
@@ -196,6 +197,9 @@ def load() -> C.CDLL:
         "nwe_debug_set_sparse_chunk": (I, [P, I]),
         "nwe_last_sparse_ms": (F, [P]),
         "nwe_last_sparse_samples": (I, [P, C.POINTER(I64)]),
+        "nwe_render_sparse_async": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, I, I, F, I, C.POINTER(SparseOutputs), P]),
+        "nwe_debug_last_sparse_host_waits": (I, [P]),
+        "nwe_debug_query_counted_grid": (C.c_uint, [I64, I, I, I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -61,6 +61,13 @@ struct Slot {
     bool used = false;
 };
 
+// A slot of the sparse ring.  An asynchronous call (nwe_render_sparse_async) leaves its selected samples in `tally` on the device -
+// one add per chunk - and, behind its last chunk, in the pinned `word`, which nwe_last_sparse_samples reads once ev1 has passed.
+struct SparseSlot : Slot {
+    DevBuf<unsigned long long> tally;
+    Owned<void*, hipHostFree> word;
+};
+
 // A slot of the render ring: what its launch reports and the device resources its plan asks for (CallPlan, nwe_plan.h).
 struct RenderSlot : Slot {
     Event ev_mid;   // between the two launches of the hybrid plan
@@ -166,9 +173,14 @@ struct nwe_ctx {
     // nwe_render_sparse: one more ring of its own; last_sparse: the most recent sparse call that ran (nwe_last_sparse_ms), what it
     // selected of how many samples (nwe_last_sparse_samples); the chunks' scratch, grow-only, the device word the scan leaves a
     // chunk's total in (behind the scratch's tables) and the pinned word it is read back through
-    Slot sparse_slots[kSlots];
+    // nwe_render_sparse_async shares the ring, the scratch and the reports: sparse_async says which kind the last call was (its
+    // selected samples are then in the slot's pinned word), sparse_host_waits how often it made the host wait
+    // (nwe_debug_last_sparse_host_waits)
+    SparseSlot sparse_slots[kSlots];
     int next_sparse = 0, last_sparse = -1;
     int64_t sparse_selected = 0, sparse_total = 0;
+    bool sparse_async = false;
+    int sparse_host_waits = -1;
     int sparse_chunk = 0;     // nwe_debug_set_sparse_chunk: 0 = the default
     DevBuf<uint8_t> d_sparse_scratch;
     Owned<void*, hipHostFree> sparse_word;
@@ -315,6 +327,17 @@ int record_launch(nwe_ctx* c, Slot& s, hipStream_t stream, Queue&& queue) {
     return NWE_OK;
 }
 
+// The sparse calls in flight, on whatever streams they are: a synchronous one has been waited for unless it failed half way, an
+// asynchronous one ends in its slot's ev1.  *waits counts the slots that had not finished yet.
+int wait_for_sparse(nwe_ctx* c, int* waits) {
+    for (SparseSlot& s : c->sparse_slots) {
+        if (!s.used) continue;
+        if (waits && hipEventQuery(s.ev1) != hipSuccess) { ++*waits; (void)hipGetLastError(); }
+        HIPCHK(c, hipEventSynchronize(s.ev1));
+    }
+    return NWE_OK;
+}
+
 // nwe_set_sampling and nwe_set_network change device memory that a queued launch reads (the sampling tables are copied
 // into LDS by every workgroup as it starts, the weights are streamed throughout): wait for this context's own launches,
 // on whatever streams they are.  Costs nothing when nothing is in flight.
@@ -326,9 +349,7 @@ int wait_for_launches(nwe_ctx* c) {
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     for (Slot& s : c->grid_slots)    // a grid frame reads the sampling tables and the radiance grid
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
-    for (Slot& s : c->sparse_slots)  // a sparse frame reads all of it; it has been waited for, unless it failed half way
-        if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
-    return NWE_OK;
+    return wait_for_sparse(c, nullptr);   // a sparse frame reads all of it
 }
 
 // The one-shot hooks of nwe_render_rays (nwe_debug_set_fine_depths / _raw / _coarse_weights, nwe_set_train_tables) are
@@ -1461,7 +1482,8 @@ int nwe_render_sparse(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, f
     const int64_t n_rays = (int64_t)n_poses * (row_end - row_begin) * W;
     if (n_rays == 0) return NWE_OK;
     ON_DEVICE(c);
-    Slot& slot = c->sparse_slots[c->next_sparse];   // not a slot of the render ring (see nwe_create_rays)
+    TRY(wait_for_sparse(c, nullptr));   // an asynchronous call in flight still uses the scratch
+    SparseSlot& slot = c->sparse_slots[c->next_sparse];   // not a slot of the render ring (see nwe_create_rays)
     TRY(prepare_slot(c, slot));
     TRY(upload_poses(c, slot, c2w, n_poses, stream));
     RenderArgs a = camera_args(m, slot.poses.get());
@@ -1496,6 +1518,7 @@ int nwe_render_sparse(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, f
     k.selected = out->selected;
     const RadianceGrid grid = radiance_grid_args(c);
     int64_t selected = 0;
+    int host_waits = 0;
     const int rc = record_launch(c, slot, stream, [&]() -> int {
         for (int64_t first = 0; first < n_rays; first += cap) {
             k.first = first; k.count = (int)std::min<int64_t>(cap, n_rays - first);
@@ -1506,6 +1529,7 @@ int nwe_render_sparse(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, f
             // the one read-back of the chunk: the query's launch needs its n_points on the host
             HIPCHK(c, hipMemcpyAsync(c->sparse_word.h, k.total, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             HIPCHK(c, hipStreamSynchronize(stream));
+            ++host_waits;
             const uint32_t n_points = *word;
             if ((uint64_t)n_points > (uint64_t)k.count * S) return fail(c, NWE_ERR_HIP, "sparse frame: the chunk's point count is out of range");
             selected += n_points;
@@ -1527,7 +1551,97 @@ int nwe_render_sparse(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, f
     c->last_sparse = (int)(&slot - c->sparse_slots);
     c->next_sparse = (c->last_sparse + 1) % nwe_ctx::kSlots;
     c->sparse_selected = selected; c->sparse_total = n_rays * S;
+    c->sparse_async = false; c->sparse_host_waits = host_waits + 1;
     return NWE_OK;
+}
+
+int nwe_render_sparse_async(nwe_ctx* c, const float* c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near, float far,
+                            int row_begin, int row_end, int which, int precision, float min_weight, int dilate, const nwe_sparse_outputs* out,
+                            void* stream_) {
+    const Camera m{c2w, n_poses, H, W, fx, fy, cx, cy, near, far, row_begin, row_end};
+    CHECK(c, check_render_sparse(MaybeContext(c).p, out, m, which, precision, min_weight, dilate));
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t n_rays = (int64_t)n_poses * (row_end - row_begin) * W;
+    if (n_rays == 0) return NWE_OK;
+    ON_DEVICE(c);
+    const NetState& net = c->net[which];
+    const int S = c->ns + c->ni;
+    // the chunks and the scratch of the synchronous call: 2^22 / S rays, which the test hook may lower
+    int64_t cap = std::max<int64_t>(1, kSparseChunkSamples / S);
+    if (c->sparse_chunk > 0) cap = std::min<int64_t>(cap, c->sparse_chunk);
+    cap = std::min(cap, n_rays);
+    const size_t M = (size_t)cap * S;
+    size_t bytes = 0;
+    const auto take = [&](size_t n) { const size_t at = bytes; bytes += (n + 255) / 256 * 256; return at; };
+    const size_t at_grid = take(M * 16), at_rows = take(M * 16), at_z = take(M * 4), at_points = take(M * 12), at_dirs = take(M * 12),
+                 at_offsets = take((size_t)cap * 4), at_total = take(4), at_mask = take(M);
+    int host_waits = 0;
+    // the host waits only here: for every sparse call in flight if the scratch has to grow (growing drops it), and for the call that
+    // used this slot of the ring four calls ago, normally long finished
+    if (bytes > c->d_sparse_scratch.cap) {
+        TRY(wait_for_sparse(c, &host_waits));
+        HIPCHK(c, c->d_sparse_scratch.reserve(bytes));
+    }
+    SparseSlot& slot = c->sparse_slots[c->next_sparse];
+    if (slot.used && hipEventQuery(slot.ev1) != hipSuccess) { ++host_waits; (void)hipGetLastError(); }
+    TRY(prepare_slot(c, slot));
+    HIPCHK(c, slot.tally.reserve(1));
+    if (!slot.word) HIPCHK(c, hipHostMalloc(&slot.word.h, sizeof(unsigned long long), hipHostMallocDefault));
+    // on the device: behind the previous sparse call of either kind, whose chunks use the same scratch, on whatever stream it ran
+    if (c->last_sparse >= 0 && c->sparse_slots[c->last_sparse].used) HIPCHK(c, hipStreamWaitEvent(stream, c->sparse_slots[c->last_sparse].ev1, 0));
+    TRY(upload_poses(c, slot, c2w, n_poses, stream));
+    RenderArgs a = camera_args(m, slot.poses.get());
+    a.white_bkgd = c->white_bkgd;   // nothing else of the context: the sampling tables and counts, no mode
+    a.t_vals = c->d_t.get(); a.omt_vals = a.t_vals + kMaxSamples; a.u_vals = a.omt_vals + kMaxSamples;
+    a.n_samples = c->ns; a.n_importance = c->ni;
+    a.out.struct_bytes = sizeof(nwe_outputs);
+    a.out.rgb = out->rgb; a.out.depth = out->depth; a.out.acc = out->acc; a.out.flags = out->flags;
+    uint8_t* const base = c->d_sparse_scratch.get();
+    SparseChunk k = {};
+    k.S = S; k.min_weight = min_weight; k.dilate = dilate;
+    k.row_grid = reinterpret_cast<float4*>(base + at_grid); k.rows = reinterpret_cast<const float4*>(base + at_rows);
+    k.z = reinterpret_cast<float*>(base + at_z); k.points = reinterpret_cast<float*>(base + at_points);
+    k.dirs = net.in_dir != 0 ? reinterpret_cast<float*>(base + at_dirs) : nullptr;
+    k.offsets = reinterpret_cast<uint32_t*>(base + at_offsets); k.total = reinterpret_cast<uint32_t*>(base + at_total);
+    k.mask = base + at_mask;
+    k.weights_coarse = out->weights_coarse; k.z_fine = out->z_fine; k.weights_grid = out->weights_grid; k.raw_fine = out->raw_fine;
+    k.selected = out->selected;
+    const RadianceGrid grid = radiance_grid_args(c);
+    unsigned long long* const tally = slot.tally.get();
+    const int rc = record_launch(c, slot, stream, [&]() -> int {
+        HIPCHK(c, hipMemsetAsync(tally, 0, sizeof(unsigned long long), stream));
+        for (int64_t first = 0; first < n_rays; first += cap) {   // the one buffer is reused in stream order
+            k.first = first; k.count = (int)std::min<int64_t>(cap, n_rays - first);
+            launch_sparse_mark(a, grid, k, stream);
+            launch_sparse_scan(k, stream);
+            launch_sparse_emit(a, k, stream);
+            launch_sparse_tally(k, tally, stream);
+            // the counted query: sized for the chunk's samples, it reads the scan's total on the device
+            QueryArgs q = {};
+            q.points = k.points; q.dirs = k.dirs; q.raw = reinterpret_cast<float*>(base + at_rows); q.n_points = k.count * S; q.points_per_dir = 1;
+            if (precision == NWE_PREC_F32) launch_query_f32_counted(q, k.total, net.f32, c->query_steps, c->cus, stream);
+            else if (!launch_query_mfma_counted(q, k.total, net.mf, precision == NWE_PREC_F16X3, c->query_steps, c->cus, stream))
+                return fail(c, NWE_ERR_UNSUPPORTED, "no MFMA query kernel in this build for this network shape; use NWE_PREC_F32");
+            launch_sparse_composite(a, k, stream);
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipMemcpyAsync(slot.word.h, tally, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        return NWE_OK;
+    });
+    if (rc) {   // a call that failed half way leaves nothing running, as the synchronous one
+        (void)hipStreamSynchronize(stream);
+        return rc;
+    }
+    c->last_sparse = (int)(&slot - c->sparse_slots);
+    c->next_sparse = (c->last_sparse + 1) % nwe_ctx::kSlots;
+    c->sparse_total = n_rays * S;
+    c->sparse_async = true; c->sparse_host_waits = host_waits;
+    return NWE_OK;
+}
+
+int nwe_debug_last_sparse_host_waits(nwe_ctx* c) { return c && c->last_sparse >= 0 ? c->sparse_host_waits : -1; }
+unsigned nwe_debug_query_counted_grid(int64_t capacity, int packet, int forced_steps, int cus) {
+    return query_counted_grid(capacity, packet, forced_steps, cus);
 }
 
 int nwe_debug_set_sparse_chunk(nwe_ctx* c, int rays) { return set_on(rays < 0 ? nullptr : c, [&] { c->sparse_chunk = rays; }); }
@@ -1540,6 +1654,13 @@ float nwe_last_sparse_ms(nwe_ctx* c) {
 int nwe_last_sparse_samples(nwe_ctx* c, int64_t* out2) {
     if (!c || !out2) return NWE_ERR_INVALID;
     if (c->last_sparse < 0) return NWE_ERR_STATE;
+    if (c->sparse_async) {   // the tally is in the slot's pinned word once the call's end event has passed
+        const SparseSlot& slot = c->sparse_slots[c->last_sparse];
+        ON_DEVICE(c);
+        HIPCHK(c, hipEventSynchronize(slot.ev1));
+        c->sparse_selected = (int64_t)*static_cast<volatile unsigned long long*>(slot.word.h);
+        c->sparse_async = false;   // read once
+    }
     out2[0] = c->sparse_selected; out2[1] = c->sparse_total;
     return NWE_OK;
 }

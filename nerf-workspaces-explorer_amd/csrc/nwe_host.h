@@ -59,20 +59,16 @@ struct QueryArgs {
     int density_only;       // launch-uniform: raw is null, so the colour layers may be left out where the shape has that path
 };
 
-constexpr int kQueryPacket = 128;      // points per step of query_mfma_kernel (32 per wave)
-constexpr int kQueryPacketF32 = 16;    // ... of query_f32_kernel
-constexpr int kQueryMaxSteps = 256;    // steps per workgroup at the most: one packet workgroup's worth of evaluations of the bench frame (64 + 192 samples)
-
-// Steps per workgroup of a query of `packets` packets; forced (nwe_debug_set_query_steps) > 0 overrides the rule.
-// The rule: a workgroup holds a CU by itself, so a launch runs in rounds of one workgroup per CU.  A large query gets EIGHT
-// workgroups per CU - the last round, in which CUs idle once their workgroup is done, is then an eighth of the launch at the
-// most - and as many steps per workgroup as that leaves, up to kQueryMaxSteps: steps = clamp(packets / (8 CUs), 1, 256).
-// The prologue a workgroup amortises over its steps is small (one bias table, ~10 KB from L2, and a barrier: a few per cent
-// of ONE step), so a query of up to 8 CUs packets runs one step per workgroup and spreads as widely as it can.
-int query_steps(int64_t packets, int forced, int cus);
+// kQueryPacket, kQueryPacketF32, kQueryMaxSteps, query_steps and query_counted_grid: nwe_plan.h (HIP-free)
 void launch_query_f32(const QueryArgs& a, const NetF32& net, int forced_steps, int cus, hipStream_t stream);
 // false: no query kernel for the network's shape (the shapes of mfma_supported), or its stream does not fit the instantiation
 bool launch_query_mfma(const QueryArgs& a, const NetMfma& net, bool three_pass, int forced_steps, int cus, hipStream_t stream);
+// The counted forms (nwe_render_sparse_async): a.n_points is a CAPACITY, the point count is the device word `count`, which the
+// kernels read as they start - min(*count, capacity) - so nothing of the launch depends on a value the host would have to wait
+// for.  The grid is query_counted_grid's (nwe_plan.h); a.steps is not read.
+void launch_query_f32_counted(const QueryArgs& a, const uint32_t* count, const NetF32& net, int forced_steps, int cus, hipStream_t stream);
+bool launch_query_mfma_counted(const QueryArgs& a, const uint32_t* count, const NetMfma& net, bool three_pass, int forced_steps, int cus,
+                               hipStream_t stream);
 
 // ---- nwe_build_occupancy (nwe_occupancy.hip) ----
 // The box of a build as its kernels read it: per axis lo and step = (float)(((double)hi - (double)lo) / res), the step of
@@ -147,6 +143,8 @@ void launch_sparse_mark(const RenderArgs& a, const RadianceGrid& g, const Sparse
 void launch_sparse_scan(const SparseChunk& c, hipStream_t stream);
 void launch_sparse_emit(const RenderArgs& a, const SparseChunk& c, hipStream_t stream);
 void launch_sparse_composite(const RenderArgs& a, const SparseChunk& c, hipStream_t stream);
+// nwe_render_sparse_async (nwe_sparse_async.hip): *tally += *c.total, behind the chunk's scan on `stream`
+void launch_sparse_tally(const SparseChunk& c, unsigned long long* tally, hipStream_t stream);
 
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);

@@ -10,7 +10,7 @@ namespace nwe {
     NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantPlain) NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantTerm)   \
     NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantShare) NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantOcc)    \
     NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantTail)                                                                \
-    NWE_EXTERN_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_)
+    NWE_EXTERN_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_) NWE_EXTERN_SHAPE_QUERY_COUNTED_LAUNCHER(W_, D_, SKIP_, FORM_)
 NWE_SHAPES(NWE_DECLARE_SHAPE)
 #undef NWE_DECLARE_SHAPE
 
@@ -33,6 +33,7 @@ constexpr bool kQueryLinked = true;
 #endif
 
 using QueryLauncher = void (*)(QueryArgs, const NetMfma&, bool, unsigned, hipStream_t);
+using QueryCountedLauncher = void (*)(QueryArgs, const NetMfma&, const uint32_t*, bool, unsigned, hipStream_t);
 
 template <int W, int D, int SKIP, int FORM, int VARIANT>
 constexpr RenderLauncher render_launcher() {
@@ -44,20 +45,26 @@ constexpr QueryLauncher query_launcher() {
     if constexpr (kQueryLinked) return launch_one_query<W, D, SKIP, FORM>;
     else return nullptr;
 }
+template <int W, int D, int SKIP, int FORM>
+constexpr QueryCountedLauncher query_counted_launcher() {
+    if constexpr (kQueryLinked) return launch_one_query_counted<W, D, SKIP, FORM>;
+    else return nullptr;
+}
 
 // One row per built shape: what identifies it, the chunks of its weight stream (the kernel copies that many bias rows), its
-// render launcher per variant and its query launcher.  A null launcher: not built.
+// render launcher per variant and its two query launchers.  A null launcher: not built.
 struct ShapeRow {
     int W, D, skip, form, n_chunks;
     RenderLauncher render[kVariants];
     QueryLauncher query;
+    QueryCountedLauncher query_counted;
 };
 #define NWE_SHAPE_ROW(W_, D_, SKIP_, FORM_)                                                                                  \
     {W_, D_, SKIP_, FORM_, Shape<W_, D_>::n_chunks(FORM_),                                                                   \
      {render_launcher<W_, D_, SKIP_, FORM_, kVariantPlain>(), render_launcher<W_, D_, SKIP_, FORM_, kVariantTerm>(),         \
       render_launcher<W_, D_, SKIP_, FORM_, kVariantShare>(), render_launcher<W_, D_, SKIP_, FORM_, kVariantOcc>(),          \
       render_launcher<W_, D_, SKIP_, FORM_, kVariantTail>()},                                                               \
-     query_launcher<W_, D_, SKIP_, FORM_>()},
+     query_launcher<W_, D_, SKIP_, FORM_>(), query_counted_launcher<W_, D_, SKIP_, FORM_>()},
 static_assert(kVariantPlain == 0 && kVariantTerm == 1 && kVariantShare == 2 && kVariantOcc == 3 && kVariantTail == 4 && kVariants == 5,
               "a row lists its launchers in the order of Variant");
 static const ShapeRow kShapes[] = {NWE_SHAPES(NWE_SHAPE_ROW)};
@@ -134,12 +141,6 @@ bool launch_render_mfma(const RenderArgs& a, const NetMfma& nc, const NetMfma& n
 
 // ---- point query (nwe_query_points) ----
 
-int query_steps(int64_t packets, int forced, int cus) {
-    if (forced > 0) return forced < kQueryMaxSteps ? forced : kQueryMaxSteps;
-    const int64_t steps = packets / (8 * (int64_t)cus);   // the rule: nwe_host.h
-    return (int)(steps < 1 ? 1 : (steps > kQueryMaxSteps ? kQueryMaxSteps : steps));
-}
-
 bool launch_query_mfma(const QueryArgs& a_in, const NetMfma& net, bool three_pass, int forced_steps, int cus, hipStream_t stream) {
     const ShapeRow* shape = find_shape(net.D, net.W, net.skip, net.form);
     if (!shape || !shape->query || net.n_chunks != shape->n_chunks) return false;   // the kernel copies n_chunks bias rows
@@ -148,6 +149,17 @@ bool launch_query_mfma(const QueryArgs& a_in, const NetMfma& net, bool three_pas
     const int64_t packets = ((int64_t)a.n_points + kQueryPacket - 1) / kQueryPacket;
     a.steps = query_steps(packets, forced_steps, cus);
     shape->query(a, net, three_pass, (unsigned)((packets + a.steps - 1) / a.steps), stream);
+    return true;
+}
+
+bool launch_query_mfma_counted(const QueryArgs& a_in, const uint32_t* count, const NetMfma& net, bool three_pass, int forced_steps, int cus,
+                               hipStream_t stream) {
+    const ShapeRow* shape = find_shape(net.D, net.W, net.skip, net.form);
+    if (!shape || !shape->query_counted || net.n_chunks != shape->n_chunks) return false;   // the kernel copies n_chunks bias rows
+    if (a_in.n_points <= 0) return true;
+    QueryArgs a = a_in;
+    a.steps = 0;   // not read: the walk is strided over the grid
+    shape->query_counted(a, net, count, three_pass, query_counted_grid(a.n_points, kQueryPacket, forced_steps, cus), stream);
     return true;
 }
 

@@ -71,60 +71,54 @@ __global__ void __launch_bounds__(256) query_mfma_kernel(QueryArgs a, NetMfma ne
     for (int step = 0; step < a.steps; ++step) {
         const int64_t first = ((int64_t)item * a.steps + step) * kQueryPacket;   // of the workgroup's packet
         if (first >= n) break;   // workgroup-uniform
-        {   // start streaming chunks 0 and 1 (layer 0, tiles 0 and 1): they fly while the point is loaded and encoded
-            wk.start(net.stream, bias);
-            wk.begin(S::N_L0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < S::N_L0; ++i) wk.piece(i);
-            wk.begin(S::N_L0, 1, 1);
-#pragma unroll
-            for (int i = 0; i < S::N_L0; ++i) wk.piece(i);
-        }
-        const int64_t idx = first + wave * kRaysPerWave + (lane & 31);
-        const bool live = idx < n && half == 0;          // this lane stores the outputs of its point
-        const int row = (int)(idx < n ? idx : n - 1);    // a lane past the call's points computes the last one along
-        const float* p = a.points + (int64_t)row * 3;
-        const float px = p[0], py = p[1], pz = p[2];
-        if constexpr (FORM != kFormNoViewDirs) {
-            // gamma(d) of this step's points into the wave's OWN slots (model_utils.py:23-25 embeds the direction of every
-            // point).  No barrier guards the write: the slots are private to the wave - slot address = f(wave, lane) - so the only
-            // earlier accesses are this wave's own reads in the previous step's mlp_eval, and LDS serves the accesses of one
-            // wave in the order it issued them; the reads of this step's mlp_eval are issued behind the write likewise (and
-            // behind the lgkmcnt(0) of the barrier below).  LDS-DMA pieces never land here (chunk buffers and tail slots only).
-            float vx = 0.f, vy = 0.f, vz = 0.f;          // no directions given: sigma does not depend on them
-            if (a.dirs) {
-                const float* d = a.dirs + (int64_t)(row / a.points_per_dir) * 3;
-                vx = d[0]; vy = d[1]; vz = d[2];
-            }
-            h8 GDhi[S::KD], GDlo[S::KD];
-            encode<2, S::KD, X3>(vx, vy, vz, half, GDhi, GDlo);
-#pragma unroll
-            for (int k = 0; k < S::KD; ++k) {
-                *reinterpret_cast<h8*>(gd_lds + (2 * k) * kTileBytes) = GDhi[k];
-                *reinterpret_cast<h8*>(gd_lds + (2 * k + 1) * kTileBytes) = GDlo[k];
-            }
-        }
-        float rr, rg, rb, rs;
-        {
-            h8 Ghi[S::KG], Glo[S::KG];
-            // handler.py:93: scalar_factor = 10, a true division (embedding.py:48)
-            encode<5, S::KG, X3>(__fdiv_rn(px, 10.f), __fdiv_rn(py, 10.f), __fdiv_rn(pz, 10.f), half, Ghi, Glo);
-            wk.template sync<false>();   // publishes chunk 0
-            Frags F;
-#pragma unroll
-            for (int k = 0; k < PD; ++k) {
-                F.hi[k] = *reinterpret_cast<const h8*>(wk.cur() + lane * 16 + (2 * k) * kTileBytes);
-                if (X3) F.lo[k] = *reinterpret_cast<const h8*>(wk.cur() + lane * 16 + (2 * k + 1) * kTileBytes);
-            }
-            mlp_eval<W, D, SKIP, X3, FORM>(wk, F, lane, net.inv_scale, Ghi, Glo, gd_lds, dot_tab, density_only, rr, rg, rb, rs);
-        }
-        if (live) {
-            if (a.raw && store_raw(a.raw + idx * 4, rr, rg, rb, rs)) flags |= NWE_FLAG_RAW;
-            if (a.sigma) {
-                a.sigma[idx] = rs;
-                if (bad(rs)) flags |= NWE_FLAG_RAW;
-            }
-        }
+#include "nwe_mfma_query_step.h"   // the step, shared as text with query_mfma_counted_kernel below
+    }
+    if (flags && a.flags) atomicOr(a.flags, flags);
+}
+
+// The counted form (nwe_render_sparse_async): the host knows only a CAPACITY, a.n_points, and sizes the grid for it
+// (query_counted_grid, nwe_plan.h); the point count is a device word an earlier kernel on the stream has written.  Every
+// workgroup reads n = min(*count, capacity) once and walks the packets item, item + grid, item + 2 grid, ... below n - a strided
+// walk: a contiguous run sized for the capacity would leave the whole of a thinly selected chunk to the first few workgroups.
+// a.steps is not read.  A workgroup with no packet below n (all of them when n == 0) returns before the bias table, before any
+// LDS-DMA piece and before any barrier; the others leave at the top of a step as the kernel above does.  Both tests depend on
+// item, the grid and n only, so the four waves leave together.  The step is the kernel's above, the same text: a row is the same
+// bits in either kernel, whatever packet of whichever workgroup it falls into.
+template <int W, int D, int SKIP, bool X3, int FORM>
+__global__ void __launch_bounds__(256) query_mfma_counted_kernel(QueryArgs a, NetMfma net, const uint32_t* __restrict__ count) {
+    using S = Shape<W, D>;
+    using SM = QuerySmem<W, D>;
+    __shared__ __attribute__((aligned(16))) char smem[SM::TOTAL];
+    const unsigned item = blockIdx.x;
+    const uint32_t counted = *count;
+    const int n = (int)(counted < (uint32_t)a.n_points ? counted : (uint32_t)a.n_points);
+    if ((int64_t)item * kQueryPacket >= n) return;   // workgroup-uniform; nothing has been touched
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int half = lane >> 5;
+
+    float* s_bias = reinterpret_cast<float*>(smem + SM::BOFF);
+    constexpr int NCH = S::n_chunks(FORM);
+    constexpr int NROWS = S::n_bias_rows(FORM);
+    static_assert(NROWS * 32 * 4 <= SM::BIAS_BYTES, "bias table too small for the dot rows");
+    for (int i = threadIdx.x; i < NROWS * 32; i += 256) s_bias[i] = net.bias[i];
+    const float* bias = s_bias;
+    const float* dot_tab = bias + NCH * 32;
+
+    Walker<S::CHUNK_BYTES, X3> wk;
+    wk.buf0 = smem; wk.lds_chunks = (uint32_t)(uintptr_t)(LDS_AS char*)smem;
+    wk.tail0 = smem + SM::LOFF; wk.lds_tail = wk.lds_chunks + SM::LOFF; wk.t3 = 0;
+    wk.b = 0; wk.wave = wave; wk.lane_off = lane * 16;
+
+    char* gd_lds = smem + SM::GOFF + wave * (2 * S::KD * kTileBytes) + lane * 16;
+    const bool density_only = a.density_only != 0;
+    __syncthreads();   // the bias table
+
+    uint32_t flags = 0;
+    for (int64_t packet = item;; packet += gridDim.x) {
+        const int64_t first = packet * kQueryPacket;
+        if (first >= n) break;   // workgroup-uniform
+#include "nwe_mfma_query_step.h"
     }
     if (flags && a.flags) atomicOr(a.flags, flags);
 }
@@ -136,6 +130,14 @@ void launch_one_query(QueryArgs a, const NetMfma& net, bool three_pass, unsigned
     if (blocks == 0) return;
     if (three_pass) hipLaunchKernelGGL((query_mfma_kernel<W, D, SKIP, true, FORM>), dim3(blocks), dim3(256), 0, stream, a, net);
     else hipLaunchKernelGGL((query_mfma_kernel<W, D, SKIP, false, FORM>), dim3(blocks), dim3(256), 0, stream, a, net);
+}
+
+// ... of a shape's counted kernel: `blocks` workgroups for the capacity a.n_points, the count at `count` on the device.
+template <int W, int D, int SKIP, int FORM>
+void launch_one_query_counted(QueryArgs a, const NetMfma& net, const uint32_t* count, bool three_pass, unsigned blocks, hipStream_t stream) {
+    if (blocks == 0) return;
+    if (three_pass) hipLaunchKernelGGL((query_mfma_counted_kernel<W, D, SKIP, true, FORM>), dim3(blocks), dim3(256), 0, stream, a, net, count);
+    else hipLaunchKernelGGL((query_mfma_counted_kernel<W, D, SKIP, false, FORM>), dim3(blocks), dim3(256), 0, stream, a, net, count);
 }
 
 }  // namespace nwe

@@ -30,3 +30,7 @@
 #define NWE_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_) \
     template void launch_one_query<W_, D_, SKIP_, FORM_>(QueryArgs, const NetMfma&, bool, unsigned, hipStream_t);
 #define NWE_EXTERN_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_)
+// ... and of their counted forms (nwe_render_sparse_async: the point count is read on the device), in units of their own
+#define NWE_SHAPE_QUERY_COUNTED_LAUNCHER(W_, D_, SKIP_, FORM_) \
+    template void launch_one_query_counted<W_, D_, SKIP_, FORM_>(QueryArgs, const NetMfma&, const uint32_t*, bool, unsigned, hipStream_t);
+#define NWE_EXTERN_SHAPE_QUERY_COUNTED_LAUNCHER(W_, D_, SKIP_, FORM_) extern NWE_SHAPE_QUERY_COUNTED_LAUNCHER(W_, D_, SKIP_, FORM_)

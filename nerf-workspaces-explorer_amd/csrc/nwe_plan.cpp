@@ -156,4 +156,21 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     return p;
 }
 
+int query_steps(int64_t packets, int forced, int cus) {
+    if (forced > 0) return forced < kQueryMaxSteps ? forced : kQueryMaxSteps;
+    const int64_t steps = packets / (8 * (int64_t)cus);   // the rule: nwe_plan.h
+    return (int)(steps < 1 ? 1 : (steps > kQueryMaxSteps ? kQueryMaxSteps : steps));
+}
+
+unsigned query_counted_grid(int64_t capacity, int packet, int forced, int cus) {
+    if (capacity <= 0 || packet <= 0) return 0;
+    const int64_t packets = (capacity + packet - 1) / packet;
+    if (forced > 0) {
+        const int64_t steps = forced < kQueryMaxSteps ? forced : kQueryMaxSteps;
+        return (unsigned)((packets + steps - 1) / steps);
+    }
+    const int64_t most = 8 * (int64_t)(cus > 0 ? cus : 1);
+    return (unsigned)(packets < most ? packets : most);
+}
+
 }  // namespace nwe

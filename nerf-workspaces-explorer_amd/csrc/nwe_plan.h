@@ -154,4 +154,22 @@ struct CallPlan {
 
 CallPlan plan_call(const CallDesc& c, int cus);
 
+// ---- point query (nwe_query_points) ----
+constexpr int kQueryPacket = 128;      // points per step of query_mfma_kernel (32 per wave)
+constexpr int kQueryPacketF32 = 16;    // ... of query_f32_kernel
+constexpr int kQueryMaxSteps = 256;    // steps per workgroup at the most: one packet workgroup's worth of evaluations of the bench frame (64 + 192 samples)
+
+// Steps per workgroup of a query of `packets` packets; forced (nwe_debug_set_query_steps) > 0 overrides the rule.
+// The rule: a workgroup holds a CU by itself, so a launch runs in rounds of one workgroup per CU.  A large query gets EIGHT
+// workgroups per CU - the last round, in which CUs idle once their workgroup is done, is then an eighth of the launch at the
+// most - and as many steps per workgroup as that leaves, up to kQueryMaxSteps: steps = clamp(packets / (8 CUs), 1, 256).
+// The prologue a workgroup amortises over its steps is small (one bias table, ~10 KB from L2, and a barrier: a few per cent
+// of ONE step), so a query of up to 8 CUs packets runs one step per workgroup and spreads as widely as it can.
+int query_steps(int64_t packets, int forced, int cus);
+// Workgroups of a COUNTED query launch (nwe_render_sparse_async: the point count is a device word, the host knows a capacity):
+// min(ceil(capacity / packet), 8 CUs) - the eight workgroups per CU of the rule above, which then walk the packets below the
+// count in strides of the grid; forced (nwe_debug_set_query_steps) > 0 makes it ceil(ceil(capacity / packet) / forced), so that
+// a small test walks more than one packet per workgroup.  0 for a capacity of 0.
+unsigned query_counted_grid(int64_t capacity, int packet, int forced, int cus);
+
 }  // namespace nwe

@@ -54,8 +54,11 @@ class NeRFReplicaInferenceHandler:
                  separate_passes: Optional[bool] = None, occupancy: Optional[Mapping[str, object]] = None,
                  baked_coarse: Optional[Mapping[str, object]] = None,
                  radiance_grid: Optional[Mapping[str, object]] = None,
-                 sparse_fine: Optional[Mapping[str, object]] = None) -> None:
-        """``sparse_fine``: a mapping with optional "min_weight" (1e-3), "dilate" (1) and "which" ("fine"): with it
+                 sparse_fine: Optional[Mapping[str, object]] = None, sparse_async: Optional[bool] = None) -> None:
+        """``sparse_async``: True, or NWE_SPARSE_ASYNC=1 in the environment, makes ``render_coordinates`` draw its sparse frame
+        through the asynchronous call (Renderer.render_sparse(asynchronous=True)): the same frame, queued instead of waited for
+        chunk by chunk.  It is an option of ``sparse_fine``: given without it, a ValueError.  Off by default.
+        ``sparse_fine``: a mapping with optional "min_weight" (1e-3), "dilate" (1) and "which" ("fine"): with it
         ``render_coordinates(preview=False)`` draws its frame through ``render_sparse_batch`` - the radiance grid as a proposal,
         the network only at the samples the grid gives weight (Renderer.render_sparse) - an approximation, off by default.  It
         needs ``radiance_grid`` too (a ValueError otherwise).  The environment variable NWE_SPARSE_FINE = "min_weight[,dilate]"
@@ -168,6 +171,12 @@ class NeRFReplicaInferenceHandler:
         self._sparse_fine = self.parse_sparse_fine(sparse_fine, os.environ.get("NWE_SPARSE_FINE", ""))
         if self._sparse_fine is not None and self._radiance_grid is None:
             raise ValueError("sparse_fine needs a radiance grid as its proposal: give radiance_grid={'lo': ..., 'hi': ...} too")
+        env_async = os.environ.get("NWE_SPARSE_ASYNC", "").strip()
+        if env_async not in ("", "0", "1"):
+            raise ValueError("NWE_SPARSE_ASYNC must be 0 or 1")
+        self._sparse_async = bool(sparse_async) if sparse_async is not None else env_async == "1"
+        if self._sparse_async and self._sparse_fine is None:
+            raise ValueError("sparse_async is an option of the sparse frame: give sparse_fine={...} (and a radiance grid) too")
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -364,7 +373,8 @@ class NeRFReplicaInferenceHandler:
             if from_grid:
                 res = self.render_grid_batch(camera_pose.numpy(), H, W, outputs=("rgb",))
             elif self._sparse_fine is not None and not preview:
-                res = self.render_sparse_batch(camera_pose.numpy(), H, W, outputs=("rgb",), **self._sparse_fine)
+                res = self.render_sparse_batch(camera_pose.numpy(), H, W, outputs=("rgb",), asynchronous=self._sparse_async,
+                                               **self._sparse_fine)
             else:
                 res = self.render_batch(camera_pose.numpy(), H, W, outputs=("rgb",))
         finally:
@@ -552,17 +562,19 @@ class NeRFReplicaInferenceHandler:
 
     def render_sparse(self, camera_pose, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
                       which="fine", precision: Optional[str] = None, min_weight: float = 1e-3, dilate: int = 1,
-                      outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+                      outputs: Sequence[str] = ("rgb", "depth", "acc"), asynchronous: bool = False) -> Dict[str, torch.Tensor]:
         """``render`` as a sparse frame (Renderer.render_sparse): the ``which`` network only where the radiance grid sees weight."""
         res = self.render_sparse_batch(np.asarray(camera_pose, dtype=np.float32).reshape(1, 4, 4), H, W, rows=rows, which=which,
-                                       precision=precision, min_weight=min_weight, dilate=dilate, outputs=outputs)
+                                       precision=precision, min_weight=min_weight, dilate=dilate, outputs=outputs,
+                                       asynchronous=asynchronous)
         return {k: v[0] for k, v in res.items()}
 
     def render_sparse_batch(self, poses, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
                             which="fine", precision: Optional[str] = None, min_weight: float = 1e-3, dilate: int = 1,
-                            outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+                            outputs: Sequence[str] = ("rgb", "depth", "acc"), asynchronous: bool = False) -> Dict[str, torch.Tensor]:
         """``render_batch`` as a sparse frame: [B,4,4] poses -> tensors with leading [B, h, W].  ``precision`` None: the
-        handler's own, "auto" resolved for the ``which`` network as run_network does."""
+        handler's own, "auto" resolved for the ``which`` network as run_network does.  ``asynchronous``: queued on the current
+        stream, not waited for (Renderer.render_sparse)."""
         r = self._sparse_renderer()
         w, auto = self._query_net(which)
         H = self._img_h if H is None else H
@@ -571,7 +583,8 @@ class NeRFReplicaInferenceHandler:
         poses = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4)
         r0, r1 = rows if rows is not None else (0, H)
         res = r.render_sparse(poses, H, W, fx=fx, fy=fy, cx=cx, cy=cy, near=self._depth_close_bound, far=self._depth_far_bound,
-                              rows=(r0, r1), which=w, precision=precision or auto, min_weight=min_weight, dilate=dilate, outputs=outputs)
+                              rows=(r0, r1), which=w, precision=precision or auto, min_weight=min_weight, dilate=dilate, outputs=outputs,
+                              asynchronous=asynchronous)
         return {k: v if k == "flags" else v.reshape((poses.shape[0], r1 - r0, W) + tuple(v.shape[1:])) for k, v in res.items()}
 
     def last_sparse_samples(self):

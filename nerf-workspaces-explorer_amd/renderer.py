@@ -661,10 +661,11 @@ class Renderer:
     def render_sparse(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
                       rows: Optional[Tuple[int, int]] = None, which: int = _lib.NET_FINE, precision: str = "f16x3",
                       min_weight: float = 1e-3, dilate: int = 1,
-                      outputs: Sequence[str] = ("rgb", "depth", "acc")) -> Dict[str, torch.Tensor]:
+                      outputs: Sequence[str] = ("rgb", "depth", "acc"), asynchronous: bool = False) -> Dict[str, torch.Tensor]:
         """A sparse frame (nwe_render_sparse): the radiance grid's frame as a proposal, network ``which`` at the samples of the
         output pass whose proposed weight is above ``min_weight`` (and ``dilate`` neighbours on either side), the grid's rows at
-        the others.  Synchronous.  ``outputs``: a choice of "rgb", "depth", "acc" and the diagnostics "weights_coarse"
+        the others.  Synchronous, unless ``asynchronous``: then the call is queued on the current stream and returns
+        (nwe_render_sparse_async), with the same bits; the tensors are valid for work queued on that stream behind it.  ``outputs``: a choice of "rgb", "depth", "acc" and the diagnostics "weights_coarse"
         [R, n_samples], "z_fine" [R, S], "weights_grid" [R, S], "selected" [R, S] (uint8) and "raw_fine" [R, S, 4] (S = n_samples +
         n_importance, the output pass); "flags" is always returned."""
         outputs = tuple(outputs)
@@ -675,12 +676,13 @@ class Renderer:
         r0, r1 = rows if rows is not None else (0, H)
         o = _lib.SparseOutputs()
         tail = (r0, r1, int(which), _lib.PRECISIONS[precision], float(min_weight), int(dilate))
+        entry = "nwe_render_sparse_async" if asynchronous else "nwe_render_sparse"
+        call = getattr(self._lib, entry)
         if self.device is None:   # a host-only context: the ABI's own refusals, nothing allocated
             for name in outputs:
                 setattr(o, name, 1)   # never written: every path of a host-only context refuses
-            self._check(self._lib.nwe_render_sparse(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail,
-                                                    C.byref(o), None), "nwe_render_sparse")
-            raise RuntimeError("nwe_render_sparse: a host-only context rendered")   # not reached
+            self._check(call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail, C.byref(o), None), entry)
+            raise RuntimeError(f"{entry}: a host-only context rendered")   # not reached
         n_rays = poses.shape[0] * max(r1 - r0, 0) * W
         S = self.n_samples + self.n_importance
         shapes = {"rgb": (n_rays, 3), "depth": (n_rays,), "acc": (n_rays,), "weights_coarse": (n_rays, self.n_samples),
@@ -694,22 +696,28 @@ class Renderer:
             for name in _lib.SPARSE_OUTPUT_FIELDS:
                 setattr(o, name, (bufs[name] if name in bufs else res[name]).data_ptr() if name in res else None)
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self._lib.nwe_render_sparse(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail,
-                                             C.byref(o), stream)
-        self._check(rc, "nwe_render_sparse")
+            rc = call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail, C.byref(o), stream)
+        self._check(rc, entry)
         return res
 
     def last_sparse_ms(self) -> Optional[float]:
-        """Device span of the last ``render_sparse`` call in ms, None if there was none."""
+        """Device span of the last ``render_sparse`` call in ms (blocks until it has finished), None if there was none."""
         ms = float(self._lib.nwe_last_sparse_ms(self._ctx))
         return ms if ms >= 0 else None
 
     def last_sparse_samples(self) -> Optional[Tuple[int, int]]:
-        """(selected, total) samples of the last ``render_sparse`` call, None if there was none."""
+        """(selected, total) samples of the last ``render_sparse`` call (blocks until an asynchronous one has finished), None if
+        there was none."""
         out = (C.c_int64 * 2)()
         if self._lib.nwe_last_sparse_samples(self._ctx, out) != _lib.NWE_OK:
             return None
         return int(out[0]), int(out[1])
+
+    def debug_last_sparse_host_waits(self) -> Optional[int]:
+        """Test hook (nwe_debug_last_sparse_host_waits): how often the last ``render_sparse`` call made the host wait for the
+        device - its chunks + 1 when synchronous, 0 for a warmed asynchronous call; None if there was none."""
+        n = int(self._lib.nwe_debug_last_sparse_host_waits(self._ctx))
+        return n if n >= 0 else None
 
     def debug_set_sparse_chunk(self, rays: int) -> None:
         """Test hook (nwe_debug_set_sparse_chunk): the rays of a chunk of ``render_sparse``; 0 restores the default."""

@@ -1,6 +1,6 @@
 """The MFMA render kernels keep the LDS-DMA destination in M0 across statements (one write per group of pieces), which is
 sound only while hipcc emits no M0 use of its own in those kernels: disassemble the built library and check, for every
-render_mfma_kernel, render_mfma_tail_kernel, render_mfma_occ_kernel and query_mfma_kernel, that
+render_mfma_kernel, render_mfma_tail_kernel, render_mfma_occ_kernel, query_mfma_kernel and query_mfma_counted_kernel, that
 
 * every instruction touching m0 is one of ours: `s_mov_b32 m0, <scalar register>` immediately followed by `s_nop 0` and the
   `global_load_lds_dwordx4` it addresses - the one asm statement of Walker::piece;
@@ -26,7 +26,7 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 IMPLICIT = re.compile(r"^(s_set_gpr_idx_\w+|s_movrel\w*|v_movrel\w*|ds_gws_\w+|ds_ordered_count|ds_\w+_gs\w*|s_sendmsg\w*|s_ttracedata\w*|"
                       r"v_interp_\w+|s_getreg_b32 \S+ hwreg\(HW_REG_M0|buffer_\w+ .*\blds\b|ds_\w+ .*\bgds\b)")
 PIECE = "global_load_lds_dwordx4"
-KERNEL = r"(?:render_mfma_(?:tail_|occ_)?|query_mfma_)kernel"   # the kernels that own M0
+KERNEL = r"(?:render_mfma_(?:tail_|occ_)?|query_mfma_(?:counted_)?)kernel"   # the kernels that own M0
 
 
 def analyse(body, addrs=None, x3=True):
