@@ -276,7 +276,10 @@ int64_t nwe_flops_per_eval(const nwe_ctx *ctx, int which);
  * refused, zero rays, or a launch refused after its argument checks ("coarse and fine networks must have the same
  * shape"): this call and nwe_last_launch_parts then still describe the last launch that was made.  Returns < 0 if nothing
  * was launched.  Like every entry point it leaves the calling
- * thread's current HIP device as it found it. */
+ * thread's current HIP device as it found it.
+ * A time is read from the launch's events once and kept: this call, nwe_last_launch_parts, nwe_last_coarse_launch,
+ * nwe_last_query_ms, nwe_last_grid_ms and nwe_last_sparse_ms return the same float, exactly, for as long as they describe
+ * the same launch, however often they are asked and whatever is launched in between. */
 float nwe_last_kernel_ms(nwe_ctx *ctx);
 
 /* The same launch taken apart: a frame whose last round of workgroups is ragged is rendered as TWO launches of the kernel

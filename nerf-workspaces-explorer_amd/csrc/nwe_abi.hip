@@ -59,6 +59,13 @@ struct Slot {
     DevBuf<float> poses;
     Event ev0, ev1;
     bool used = false;
+    // A time of the launch is read from its pair of events ONCE and kept (kept_time): the runtime converts the device's ticks anew
+    // at every hipEventElapsedTime, and two readings of one launch were seen to differ in the last digit - a report must not
+    // change while it describes the same launch.  kWhole: ev0 .. ev1; the others are the render ring's (nwe_last_launch_parts,
+    // nwe_last_coarse_launch).  Forgotten when the slot is prepared for a new launch.
+    enum { kWhole, kPart0, kPart1, kCoarse, kTimes };
+    mutable float time_ms[kTimes] = {};
+    mutable bool time_read[kTimes] = {};
 };
 
 // A slot of the sparse ring.  An asynchronous call (nwe_render_sparse_async) leaves its selected samples in `tally` on the device -
@@ -306,6 +313,7 @@ int prepare_slot(nwe_ctx* c, Slot& s) {
         for (Event* e : {&s.ev0, &s.ev1}) HIPCHK(c, hipEventCreate(&e->h));
     if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     s.used = false;
+    for (bool& read : s.time_read) read = false;
     return NWE_OK;
 }
 int prepare_slot(nwe_ctx* c, RenderSlot& s) {
@@ -851,13 +859,24 @@ int query_lattice(nwe_ctx* c, const NetState& n, const Lattice& l, int64_t cells
     return NWE_OK;
 }
 
+// The time between two events of the launch that slot `s` describes (both have passed): read once, then the same value.
+hipError_t kept_time(const Slot& s, int which, hipEvent_t from, hipEvent_t to, float* ms) {
+    if (!s.time_read[which]) {
+        const hipError_t e = hipEventElapsedTime(&s.time_ms[which], from, to);
+        if (e != hipSuccess) return e;
+        s.time_read[which] = true;
+    }
+    *ms = s.time_ms[which];
+    return hipSuccess;
+}
+
 // nwe_last_kernel_ms, nwe_last_query_ms: the time between the events of a recorded launch, or -1 and the context's error
 float elapsed_ms(nwe_ctx* c, const Slot& s, const char* who) {
     DeviceGuard guard;
     hipError_t e = hipSetDevice(c->device);
     if (e == hipSuccess) e = hipEventSynchronize(s.ev1);
     float ms = -1.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, s.ev0, s.ev1);
+    if (e == hipSuccess) e = kept_time(s, Slot::kWhole, s.ev0, s.ev1, &ms);
     if (e != hipSuccess) { c->err = std::string(who) + ": " + hipGetErrorString(e); (void)hipGetLastError(); return -1.f; }
     return ms;
 }
@@ -1072,14 +1091,14 @@ int nwe_last_launch_parts(nwe_ctx* c, float* ms2, int64_t* rays2) {
     rays2[0] = s->rays_first; rays2[1] = s->rays_total - s->rays_first;
     const hipEvent_t begin = s->has_share ? s->ev_share : s->ev0;   // behind the producer of a shared coarse pass
     if (s->has_mid) {
-        HIPCHK(c, hipEventElapsedTime(&ms2[0], begin, s->ev_mid));
-        HIPCHK(c, hipEventElapsedTime(&ms2[1], s->ev_mid, s->ev1));
+        HIPCHK(c, kept_time(*s, Slot::kPart0, begin, s->ev_mid, &ms2[0]));
+        HIPCHK(c, kept_time(*s, Slot::kPart1, s->ev_mid, s->ev1, &ms2[1]));
         // begin, ev_mid and ev1 lie on the caller's stream in this order, also when the second launch runs on the side stream
         // (ev1 behind the join), so no part is negative; one that is below the timer's step is reported as that step, never as 0
         // (the sum then exceeds nwe_last_kernel_ms by less than that step)
         for (int i = 0; i < 2; ++i) ms2[i] = std::max(ms2[i], kMinPartMs);
     } else {
-        HIPCHK(c, hipEventElapsedTime(&ms2[0], begin, s->ev1));
+        HIPCHK(c, kept_time(*s, Slot::kPart0, begin, s->ev1, &ms2[0]));
     }
     return NWE_OK;
 }
@@ -1092,7 +1111,7 @@ int nwe_last_coarse_launch(nwe_ctx* c, float* ms, int64_t* rays) {
     if (!s->has_share) return NWE_OK;
     ON_DEVICE(c);
     HIPCHK(c, hipEventSynchronize(s->ev1));
-    HIPCHK(c, hipEventElapsedTime(ms, s->ev0, s->ev_share));
+    HIPCHK(c, kept_time(*s, Slot::kCoarse, s->ev0, s->ev_share, ms));
     *rays = s->share_rays;
     return NWE_OK;
 }
