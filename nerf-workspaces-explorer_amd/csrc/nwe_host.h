@@ -113,7 +113,7 @@ constexpr int kGridThreads = 64;   // rays of a workgroup of radiance_grid_rende
 void launch_radiance_grid_render(const RenderArgs& a, const RadianceGrid& g, hipStream_t stream);
 
 // ---- sparse frame (nwe_render_sparse; nwe_sparse.hip) ----
-constexpr int64_t kSparseChunkSamples = (int64_t)1 << 22;   // samples of a chunk at the most: rays * S
+// kSparseChunkSamples, the samples of a chunk at the most, and the chunks and scratch of a call (plan_sparse): nwe_plan.h (HIP-free)
 // One chunk of a sparse call: rays [first, first + count) of the call `a` describes (camera, tables, counts, white_bkgd, a.n_rays =
 // the whole call's).  The [count, S] tables are stored SAMPLE-major, element (s, r) at s * count + r, so that the threads of a
 // wave, one per ray, read and write consecutive addresses as they walk their samples.  The compacted lists are ray-major: the

@@ -173,4 +173,18 @@ unsigned query_counted_grid(int64_t capacity, int packet, int forced, int cus) {
     return (unsigned)(packets < most ? packets : most);
 }
 
+SparsePlan plan_sparse(int64_t n_rays, int S, int chunk_hook) {
+    SparsePlan p;
+    p.cap = kSparseChunkSamples / S;
+    if (p.cap < 1) p.cap = 1;
+    if (chunk_hook > 0 && chunk_hook < p.cap) p.cap = chunk_hook;
+    if (n_rays < p.cap) p.cap = n_rays;
+    p.chunks = (n_rays + p.cap - 1) / p.cap;
+    p.M = p.cap * S;
+    const auto take = [&](int64_t n) { const int64_t at = p.bytes; p.bytes += (n + 255) / 256 * 256; return at; };
+    p.at_grid = take(p.M * 16); p.at_rows = take(p.M * 16); p.at_z = take(p.M * 4); p.at_points = take(p.M * 12); p.at_dirs = take(p.M * 12);
+    p.at_offsets = take(p.cap * 4); p.at_total = take(4); p.at_mask = take(p.M);
+    return p;
+}
+
 }  // namespace nwe

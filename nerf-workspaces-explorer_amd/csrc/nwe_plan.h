@@ -1,6 +1,7 @@
 // The plan of a render call: which launches it is, what each of them gets and what the slot must hold for them.  Plain C++
 // without HIP (nwe_plan.cpp), pure arithmetic on a handful of integers: nwe_abi.hip describes the call, plan_call() decides,
 // and the launchers carry the plan out (nwe_kernel_mfma.hip).  Nothing here asks a device: the CU count is an argument.
+// The chunks and the scratch of a sparse frame are planned here as well (plan_sparse; nwe_abi_sparse.hip carries them out).
 // The plain constants the decisions rest on live here too, and the device headers take them from here.
 #pragma once
 #include <stdint.h>
@@ -171,5 +172,19 @@ int query_steps(int64_t packets, int forced, int cus);
 // count in strides of the grid; forced (nwe_debug_set_query_steps) > 0 makes it ceil(ceil(capacity / packet) / forced), so that
 // a small test walks more than one packet per workgroup.  0 for a capacity of 0.
 unsigned query_counted_grid(int64_t capacity, int packet, int forced, int cus);
+
+// ---- sparse frame (nwe_render_sparse, nwe_render_sparse_async) ----
+constexpr int64_t kSparseChunkSamples = (int64_t)1 << 22;   // samples of a chunk at the most: rays * S
+
+// The chunks of a sparse call of either kind and the scratch they share, laid out for the rays of one chunk.  The regions, in the
+// order of their offsets, each rounded up to 256 bytes: the grid's and the query's rows (16 M each), z (4 M), points and directions
+// (12 M each), the rays' offsets (4 cap), the chunk's total (4), the mask (M).  n_rays >= 1, S >= 1: a call without rays plans nothing.
+struct SparsePlan {
+    int64_t cap = 0;       // rays of a chunk: 2^22 / S, at least 1, at most the hook (nwe_debug_set_sparse_chunk, 0 = none) and n_rays
+    int64_t chunks = 0, M = 0;   // ceil(n_rays / cap) chunks, of cap * S samples
+    int64_t at_grid = 0, at_rows = 0, at_z = 0, at_points = 0, at_dirs = 0, at_offsets = 0, at_total = 0, at_mask = 0;   // byte offsets
+    int64_t bytes = 0;     // of the whole scratch: the end of the last region
+};
+SparsePlan plan_sparse(int64_t n_rays, int S, int chunk_hook);
 
 }  // namespace nwe

@@ -1,5 +1,6 @@
 """What the size tests of the grid and sparse kernels share (tests/test_grid_sizes_host.py, tests/test_gpu_grid_sizes.py): the
-sizes at which the loops of csrc/nwe_sparse.hip and of the host code in csrc/nwe_abi.hip take a second turn, and the scenes there.
+sizes at which the loops of csrc/nwe_sparse.hip and of the host code in csrc/nwe_abi_grids.hip and csrc/nwe_abi_sparse.hip take a
+second turn, and the scenes there.
 
 A. `sparse_scan_kernel` scans a chunk's per-ray counts in tiles of SCAN_TILE: a 40 x 64 frame is tiles of 1024, 1024 and 512 rays.
    `tiled_scan` restates the kernel tile by tile in numpy; `scan_premises` says what the frame's selection must hold for the
@@ -25,8 +26,8 @@ from tests import radiance_grid as R
 from tests import sparse_fine as SF
 
 SCAN_TILE = 1024                     # kScanThreads (csrc/nwe_sparse.hip)
-SPARSE_CHUNK_SAMPLES = 1 << 22       # kSparseChunkSamples (csrc/nwe_host.h)
-BAKE_CHUNK_CELLS = 1 << 20           # probe_lattice at probes = 1 (csrc/nwe_abi.hip)
+SPARSE_CHUNK_SAMPLES = 1 << 22       # kSparseChunkSamples (csrc/nwe_plan.h)
+BAKE_CHUNK_CELLS = 1 << 20           # probe_lattice at probes = 1 (csrc/nwe_abi_grids.hip)
 
 
 def camera(H, W):

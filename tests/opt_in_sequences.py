@@ -227,7 +227,7 @@ def table_use(st, call, hook=None):
 
 
 def scratch_use(step):
-    """Floats of d_occ_scratch a build step reserves (csrc/nwe_abi.hip; grids this small are one chunk)."""
+    """Floats of d_occ_scratch a build step reserves (csrc/nwe_abi_grids.hip; grids this small are one chunk)."""
     cells = int(np.prod(step[2]))
     # one chunk: the builds walk at most 2^20 probe points at a time (tests/grid_sizes.py: BAKE_CHUNK_CELLS); beyond that the scratch
     # would hold a chunk, not the grid, and this model would not be the library's

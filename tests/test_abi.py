@@ -141,8 +141,8 @@ def test_header_is_usable_from_plain_c(tmp_path):
 
 
 def test_host_code_under_sanitizers():
-    """`make asan`: nwe_pack.cpp (the fp32 and MFMA packers with the fp64 fold) and the HOST half of nwe_abi.hip (validation, the
-    copies out) built with AddressSanitizer + UndefinedBehaviorSanitizer and driven by tests/c/abi_smoke.c on a host-only context.  GPU
+    """`make asan`: nwe_pack.cpp (the fp32 and MFMA packers with the fp64 fold) and the HOST half of the units of the C ABI - nwe_abi.hip, nwe_abi_grids.hip,
+    nwe_abi_sparse.hip - (validation, the copies out) built with AddressSanitizer + UndefinedBehaviorSanitizer and driven by tests/c/abi_smoke.c on a host-only context.  GPU
     sanitizers do not exist on this pool; the device code is covered by the parity tests."""
     import shutil
     import subprocess

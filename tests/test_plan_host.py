@@ -1,7 +1,8 @@
 """The launch planner without a GPU (csrc/nwe_plan.cpp through nwe_debug_plan, include/nwe.h): plain C++ that compiles without
 ROCm; its plans at every CU count against a recording of the arithmetic it replaced (tests/golden/plan_table.npz, whose header
 says which commit's code produced it and how - a recording of this project's own earlier code, never of the code under test);
-invariants of a plan over the same grid; the call-level decisions from context state; the refusals of the real calls."""
+invariants of a plan over the same grid; the call-level decisions from context state; the refusals of the real calls; the chunks
+and the scratch of a sparse frame (plan_sparse) against the arithmetic of the two calls that each formed them."""
 import ctypes as C
 import os
 import shutil
@@ -65,6 +66,67 @@ def test_the_planner_compiles_without_rocm(tmp_path):
     subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", "-c", os.path.join(CSRC, "nwe_plan.cpp"), "-o", str(tmp_path / "nwe_plan.o")], check=True)
     for name in ("nwe_plan.cpp", "nwe_plan.h"):
         assert "hip" not in open(os.path.join(CSRC, name)).read().replace("HIP", "").replace(".hip", ""), name
+    # the sparse frame's plan is declared there, constant included, and nowhere beside it: the HIP headers take it from the planner
+    header = open(os.path.join(CSRC, "nwe_plan.h")).read()
+    for declared in ("constexpr int64_t kSparseChunkSamples = (int64_t)1 << 22;", "struct SparsePlan {", "SparsePlan plan_sparse(int64_t n_rays, int S, int chunk_hook);"):
+        assert declared in header, declared
+    assert "kSparseChunkSamples =" not in open(os.path.join(CSRC, "nwe_host.h")).read()
+
+
+# plan_sparse's fields in the order tests/c/sparse_plan_smoke.cpp prints them
+KEYS = ("cap", "chunks", "M", "at_grid", "at_rows", "at_z", "at_points", "at_dirs", "at_offsets", "at_total", "at_mask", "bytes")
+REGIONS = KEYS[3:11]
+# (n_rays, S, hook): one ray; M = 432, whose 4 M = 1 728 bytes round up to 1 792; three chunks, the last of 5 rays; one chunk against two
+# at 2^22 // 192 = 21 845 rays; the largest legal S = 128 + 256; a hook above the cap; a hook of one ray
+SPARSE_CASES = ((1, 1, 0), (27, 16, 0), (133, 16, 64), (21845, 192, 0), (21846, 192, 0), (2560, 384, 0), (100, 16, 1000), (100, 16, 1))
+
+
+def _sparse_plan_of_the_parent(n_rays, S, hook):
+    """The chunk size and the scratch layout as nwe_render_sparse and nwe_render_sparse_async of commit 4becc22 formed them, each for
+    itself (csrc/nwe_abi.hip there: `cap`, the `take` lambda, at_grid .. at_mask, the loop `first += cap`), restated."""
+    cap = max(1, (1 << 22) // S)
+    if hook > 0:
+        cap = min(cap, hook)
+    cap = min(cap, n_rays)
+    M = cap * S
+    plan, size = {"cap": cap, "chunks": -(-n_rays // cap), "M": M}, 0
+    for name, n in zip(REGIONS, (M * 16, M * 16, M * 4, M * 12, M * 12, cap * 4, 4, M)):
+        plan[name] = size
+        size += (n + 255) // 256 * 256
+    plan["bytes"] = size
+    return plan, dict(zip(REGIONS, (M * 16, M * 16, M * 4, M * 12, M * 12, cap * 4, 4, M)))
+
+
+def test_the_sparse_plan_is_the_arithmetic_it_replaced(tmp_path):
+    """tests/c/sparse_plan_smoke.cpp - the host compiler, every warning an error, no ROCm include path, nwe_plan.cpp alone - prints
+    plan_sparse at the smallest inputs at which it can go wrong; every field against the restatement of the code it replaced."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "sparse_plan_smoke")
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "c", "sparse_plan_smoke.cpp"),
+                    os.path.join(CSRC, "nwe_plan.cpp"), "-o", exe], check=True)
+    words = [str(v) for case in SPARSE_CASES for v in case]
+    done = subprocess.run([exe] + words, capture_output=True, text=True)
+    assert done.returncode == 0, done.stderr
+    piped = subprocess.run([exe], input=" ".join(words), capture_output=True, text=True)
+    assert piped.returncode == 0 and piped.stdout == done.stdout
+    lines = done.stdout.splitlines()
+    assert len(lines) == len(SPARSE_CASES)
+    for case, line in zip(SPARSE_CASES, lines):
+        got = dict(zip(KEYS, (int(v) for v in line.split())))
+        want, sizes = _sparse_plan_of_the_parent(*case)
+        assert len(line.split()) == len(KEYS) and got == want, (case, got, want)
+        # ascending, 256-aligned, no region reaches into the next, bytes is the end of the last
+        ends = [got[name] + sizes[name] for name in REGIONS]
+        starts = [got[name] for name in REGIONS]
+        assert starts[0] == 0 and all(s % 256 == 0 for s in starts), (case, got)
+        assert all(end <= nxt and start < nxt for start, end, nxt in zip(starts, ends, starts[1:])), (case, got)
+        assert ends[-1] <= got["bytes"] < ends[-1] + 256 and got["bytes"] % 256 == 0, (case, got)
+    by_case = {case: dict(zip(KEYS, (int(v) for v in line.split()))) for case, line in zip(SPARSE_CASES, lines)}
+    assert by_case[27, 16, 0]["M"] == 432 and by_case[27, 16, 0]["at_points"] - by_case[27, 16, 0]["at_z"] == 1792
+    assert (by_case[133, 16, 64]["cap"], by_case[133, 16, 64]["chunks"], 133 - 2 * 64) == (64, 3, 5)
+    assert (by_case[21845, 192, 0]["chunks"], by_case[21846, 192, 0]["chunks"], by_case[21846, 192, 0]["cap"]) == (1, 2, 21845)
+    assert by_case[2560, 384, 0]["cap"] == 2560 and by_case[100, 16, 1000]["cap"] == 100 and by_case[100, 16, 1]["chunks"] == 100
 
 
 @pytest.fixture(scope="module")
