@@ -15,8 +15,8 @@ finite exactly where no evaluation that counts for it ran the colour layers.
 
 Which test takes the branch where (P = proved by a NaN-head test; elsewhere the [0.1, 0.9] hollow share of the reference's sigma
 stands for it).  Plain and tail kernels at 8x256 and 4x128: tests/test_gpu_colour_skip.py (P), tests/test_gpu_packet_blocks.py;
-plain at 4x256 and 8x128: test_plain_lean_equals_full_and_on_equals_off (the tail kernels of these two shapes are left to a
-later file).  Terminating, all four shapes: test_terminating_on_equals_off,
+plain at 4x256 and 8x128: test_plain_lean_equals_full_and_on_equals_off (the tail kernels of these two shapes:
+tests/test_gpu_lean_domain.py).  Terminating, all four shapes: test_terminating_on_equals_off,
 test_terminating_kernel_with_nothing_to_stop_gives_the_plain_full_bits, at 4x128 / 8x128 under the packets plan also
 test_terminating_packets_plan_leaves_its_loop_at_the_narrow_shapes; 4x128 and 8x256: test_terminating_parity_with_the_masked_reference,
 test_terminating_path_runs_exactly_where_predicted (P).  Occupancy, all four: test_occupancy_on_equals_off,
