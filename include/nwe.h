@@ -734,6 +734,67 @@ int nwe_render_sparse_async(nwe_ctx *ctx, const float *c2w, int n_poses, int H, 
 int nwe_debug_last_sparse_host_waits(nwe_ctx *ctx);
 unsigned nwe_debug_query_counted_grid(int64_t capacity, int packet, int forced_steps, int cus);
 
+/* Adaptive frame, opt-in: render a lattice of every k-th pixel with the networks, render the pixels of the lattice cells whose
+ * corners disagree as well, interpolate the rest bilinearly.  An entry point of its own, off unless called.  Every pixel that is
+ * rendered has the bits nwe_render gives it; the approximation is confined to pixels whose four surrounding samples agree within
+ * the caller's tolerances.  The camera arguments, R and the ray order are nwe_render's.
+ * The rule, for each pose of the call on its own:
+ *   Lattice.  It belongs to the rows of the CALL: lattice rows Lh = {row_begin + i k < row_end} and row_end - 1, lattice columns
+ *      Lw = {i k < W} and W - 1.  A pixel with h in Lh and w in Lw is a lattice pixel (kind 0); k = 1 makes every pixel one.
+ *      Consecutive lattice rows and columns bound the CELLS; with a single lattice row (or column) the cells are degenerate, h0 == h1.
+ *   Stage 1.  Every lattice pixel is rendered by the networks: its ray is the row nwe_create_rays writes for it, rendered through
+ *      the machinery of nwe_render_rays with rgb, depth, acc and flags requested - the bits of nwe_render for that pixel.
+ *   Flat cells.  A cell is FLAT iff for every pair (i, j) of its four corner pixels fabsf(v_i - v_j) <= tol_rgb for each of r, g, b
+ *      and acc, and fabsf(depth_i - depth_j) <= tol_depth: plain fp32 subtractions and comparisons, so a NaN or an inf - inf makes
+ *      the cell BUSY, a tolerance below 0 makes every cell busy and +inf every cell with finite corners flat.  The rgb compared
+ *      is the output rgb (behind nwe_set_white_background).
+ *   Kinds.  A non-lattice pixel is RENDERED (kind 1) iff it lies in the closed rectangle [h0 .. h1] x [w0 .. w1] of at least one
+ *      busy cell - a pixel on a lattice row or column between two cells is interpolated only if both are flat - and INTERPOLATED
+ *      (kind 2) otherwise.
+ *   Stage 2.  Every kind 1 pixel is rendered exactly as in stage 1.
+ *   Stage 3.  Every kind 2 pixel is interpolated in its cell: cell row i = min(largest i with Lh[i] <= h, cells - 1), likewise the
+ *      column; fy = (h1 == h0) ? 0 : (float)(h - h0) / (float)(h1 - h0), likewise fx, true fp32 divisions; each of r, g, b, depth
+ *      and acc along w on the top pair and on the bottom pair, then along h, each step a + (b - a) f in three separately rounded
+ *      fp32 operations (no FMA) - the arithmetic of the grids.
+ *   Flags.  The rgb / depth / acc bits of both render launches, and those of any non-finite value an interpolation yields.  The
+ *      coarse bits and the disparity bit are never reported.
+ * So a pixel's outputs depend on the call's camera, rows, k and tolerances and on the networks only, and a pose batch is
+ * bit-identical to single-pose calls.  A ROW TILE IS NOT bit-identical to the whole image near its borders: its lattice is its
+ * own.  nwe_render_tiled does not use the call.
+ * LIMITATION: a feature that lies wholly inside a flat cell and is narrower than k pixels is not seen (k = 2: single pixels).
+ * SYNCHRONOUS: queued on `stream` and waited for, as nwe_render_sparse.  The number of kind 1 pixels is known only on the device
+ * and is read back once (a pinned word) between the two render launches; a call with no busy cell makes one render launch.
+ * The two render launches are ordinary render launches of the context, as two nwe_render_rays calls with lean outputs would be:
+ * they take slots of the render ring, and nwe_last_kernel_ms, nwe_last_launch_parts, nwe_debug_last_plan and
+ * nwe_last_ray_evaluations afterwards describe the last launch made.  Any precision; nwe_set_white_background and
+ * nwe_set_separate_passes are honoured; early termination, the shared coarse pass, an occupancy grid and a baked coarse pass refuse
+ * the call with nwe_render_rays' codes and texts.  The one-shot hooks and the training tables are neither used nor cleared (unlike
+ * nwe_render_rays); the radiance grid is not read.
+ * COST: a launch of precomputed rays is not lean, so a rendered pixel costs what a ray of nwe_render_rays costs - it pays for the
+ * coarse colour and has no hollow path - not what a pixel of nwe_render costs (DESIGN.md 5.10 has the measurements).
+ * The scratch (pixel lists, rays, compact outputs, kinds, counts: about 70 bytes per pixel) is the context's own, grow-only.
+ * Refuses in this order, before anything is queued: a NULL context; NULL out, a wrong struct_bytes, none of rgb / depth / acc
+ * requested (NWE_ERR_INVALID); the camera and the ray count as nwe_render refuses them; more than 2^24 rays; k outside 1 .. 64, a NaN
+ * tolerance (NWE_ERR_INVALID); an unknown precision; everything nwe_render_rays refuses of the context for lean outputs (networks,
+ * sampling, modes, shapes); last, a host-only context (NWE_ERR_STATE).  Zero rays is NWE_OK and launches nothing.
+ *   nwe_last_adaptive           out4 = {pixels, lattice, rendered, interpolated} of the most recent call that ran, *ms (may be
+ *                               NULL) its device span, first launch to last, the read-back gap included; NWE_ERR_STATE if none.
+ *   nwe_debug_adaptive_lattice  the lattice of [first, last_excl) into out[0 .. cap): returns its size, or -1 (an empty range, k
+ *                               outside 1 .. 64, NULL, cap too small).  Needs no context. */
+typedef struct nwe_adaptive_outputs {
+    uint64_t struct_bytes;  /* = sizeof(nwe_adaptive_outputs) */
+    float *rgb;             /* [R,3] */
+    float *depth;           /* [R]   */
+    float *acc;             /* [R]   */
+    uint8_t *kind;          /* [R]    diagnostic, may be NULL: 0 lattice, 1 rendered, 2 interpolated */
+    uint32_t *flags;        /* [1]    NWE_FLAG_RGB / _DEPTH / _ACC, OR-ed (caller zeroes it) */
+} nwe_adaptive_outputs;
+int nwe_render_adaptive(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near,
+                        float far, int row_begin, int row_end, int precision, int k, float tol_rgb, float tol_depth,
+                        const nwe_adaptive_outputs *out, void *stream);
+int nwe_last_adaptive(nwe_ctx *ctx, int64_t *out4, float *ms);
+int nwe_debug_adaptive_lattice(int first, int last_excl, int k, int32_t *out, int cap);
+
 /* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
  * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1 without separate
  * passes, n_importance == 0, or a call armed with nwe_debug_set_coarse_weights).  Under separate passes with k = 1 it is the

@@ -36,7 +36,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_render_grid", "nwe_last_grid_ms",
            "nwe_render_sparse", "nwe_debug_set_sparse_chunk", "nwe_last_sparse_ms", "nwe_last_sparse_samples",
            "nwe_render_sparse_async", "nwe_debug_last_sparse_host_waits", "nwe_debug_query_counted_grid",
-           "nwe_debug_set_packet_blocks", "nwe_debug_last_packet_blocks", "nwe_debug_packet_pixels")
+           "nwe_debug_set_packet_blocks", "nwe_debug_last_packet_blocks", "nwe_debug_packet_pixels",
+           "nwe_render_adaptive", "nwe_last_adaptive", "nwe_debug_adaptive_lattice")
 
 
 class Outputs(C.Structure):
@@ -78,6 +79,18 @@ class SparseOutputs(C.Structure):
 
     def __init__(self, **kw):
         super().__init__(struct_bytes=C.sizeof(SparseOutputs), **kw)
+
+
+ADAPTIVE_OUTPUT_FIELDS = ("rgb", "depth", "acc", "kind", "flags")
+ADAPTIVE_MAX_K = 64
+
+
+class AdaptiveOutputs(C.Structure):
+    """nwe_adaptive_outputs of nwe_render_adaptive."""
+    _fields_ = [("struct_bytes", C.c_uint64)] + [(name, C.c_void_p) for name in ADAPTIVE_OUTPUT_FIELDS]
+
+    def __init__(self, **kw):
+        super().__init__(struct_bytes=C.sizeof(AdaptiveOutputs), **kw)
 
 
 PLAN_HOOK_COARSE_WEIGHTS, PLAN_HOOK_OTHER = 1, 2
@@ -200,6 +213,9 @@ def load() -> C.CDLL:
         "nwe_render_sparse_async": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, I, I, F, I, C.POINTER(SparseOutputs), P]),
         "nwe_debug_last_sparse_host_waits": (I, [P]),
         "nwe_debug_query_counted_grid": (C.c_uint, [I64, I, I, I]),
+        "nwe_render_adaptive": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, I, I, F, F, C.POINTER(AdaptiveOutputs), P]),
+        "nwe_last_adaptive": (I, [P, C.POINTER(I64), C.POINTER(F)]),
+        "nwe_debug_adaptive_lattice": (I, [I, I, I, C.POINTER(C.c_int32), I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -1,6 +1,6 @@
 // C ABI of libnwe_hip.so (include/nwe.h): the context and what the units of the ABI share (nwe_ctx.h), networks and sampling, the
 // render, tiled, ray and query calls, their reports, the debug switches.  The grids: nwe_abi_grids.hip; the sparse frames:
-// nwe_abi_sparse.hip.  Weight packing: nwe_pack.cpp; planning: nwe_plan.cpp; the refusals: nwe_check.cpp.
+// nwe_abi_sparse.hip; the adaptive frame: nwe_abi_adaptive.hip.  Weight packing: nwe_pack.cpp; planning: nwe_plan.cpp; the refusals: nwe_check.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -68,7 +68,8 @@ int wait_for_launches(nwe_ctx* c) {
     for (RenderSlot& s : c->render.slots)
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     if (c->rays_slot.used) HIPCHK(c, hipEventSynchronize(c->rays_slot.ev1));
-    for (Slot& s : c->query.slots)   // a query streams the weights of its network throughout
+    if (c->adaptive_slot.used) HIPCHK(c, hipEventSynchronize(c->adaptive_slot.ev1));   // synchronous: long passed
+    for (Slot& s : c->query.slots)  // a query streams the weights of its network throughout
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     for (Slot& s : c->grid.slots)    // a grid frame reads the sampling tables and the radiance grid
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
@@ -372,6 +373,29 @@ int render_rows(nwe_ctx* c, const Camera& m, int precision, const nwe_outputs* o
     a.out = *out;
     return launch(c, desc.d, slot, a, precision, stream);
 }
+
+}  // namespace
+
+namespace nwe {
+
+int render_ray_list(nwe_ctx* c, const ContextDesc& desc, const float* rays_dev, int64_t n_rays, int precision, const nwe_outputs& out, bool hooks,
+                    hipStream_t stream) {
+    RenderSlot& slot = c->render.next();
+    TRY(prepare_slot(c, slot));
+    RenderArgs a = {};
+    a.rays = rays_dev; a.n_rays = n_rays; a.W = 1; a.rows = 1;
+    a.ray_cols = c->net[0].in_dir == 0 ? 8 : 11;                       // rays.py:22-30: no view-direction columns without view dirs
+    if (hooks) {
+        a.z_fine_in = c->dbg_z_fine; a.raw_in_c = c->dbg_raw_c; a.raw_in_f = c->dbg_raw_f; a.w_in = c->dbg_w;
+        a.t_rand = c->trn_t; a.noise_c = c->trn_nc; a.noise_f = c->trn_nf; a.u_rand = c->trn_u;
+    }
+    a.out = out;
+    return launch(c, desc, slot, a, precision, stream);
+}
+
+}  // namespace nwe
+
+namespace {
 
 // 1 / 0: device `from` can / cannot read and write `to`'s memory directly; -1: the query failed (*err says how)
 int can_access_peer(int from, int to, hipError_t* err = nullptr) {
@@ -679,15 +703,7 @@ int nwe_render_rays(nwe_ctx* c, const float* rays_dev, int64_t n_rays, int preci
     CHECK(c, check_ray_count(n_rays, true, !rays_dev));
     if (n_rays == 0) return NWE_OK;
     ON_DEVICE(c);
-    RenderSlot& slot = c->render.next();
-    TRY(prepare_slot(c, slot));
-    RenderArgs a = {};
-    a.rays = rays_dev; a.n_rays = n_rays; a.W = 1; a.rows = 1;
-    a.ray_cols = c->net[0].in_dir == 0 ? 8 : 11;                       // rays.py:22-30: no view-direction columns without view dirs
-    a.z_fine_in = c->dbg_z_fine; a.raw_in_c = c->dbg_raw_c; a.raw_in_f = c->dbg_raw_f; a.w_in = c->dbg_w;
-    a.t_rand = c->trn_t; a.noise_c = c->trn_nc; a.noise_f = c->trn_nf; a.u_rand = c->trn_u;
-    a.out = *out;
-    return launch(c, desc.d, slot, a, precision, (hipStream_t)stream);
+    return render_ray_list(c, desc.d, rays_dev, n_rays, precision, *out, true, (hipStream_t)stream);
 }
 
 int nwe_to8b(nwe_ctx* c, const float* rgb_dev, uint8_t* out_dev, int64_t n, void* stream) {

@@ -359,4 +359,28 @@ Refusal check_render_sparse(const ContextDesc* d, const nwe_sparse_outputs* out,
     return {};
 }
 
+Refusal check_adaptive(const ContextDesc* d, const nwe_adaptive_outputs* out, const Camera& m, int precision, int k, float tol_rgb,
+                       float tol_depth) {
+    if (!d) return invalid("null context");
+    if (!out) return invalid("null outputs");
+    if (out->struct_bytes != sizeof(nwe_adaptive_outputs))
+        return invalid("nwe_adaptive_outputs.struct_bytes != sizeof(nwe_adaptive_outputs): the caller was built against another version of include/nwe.h");
+    if (!out->rgb && !out->depth && !out->acc) return invalid("none of rgb / depth / acc requested");
+    if (Refusal r = check_camera(m)) return r;
+    const int64_t n_rays = (int64_t)m.n_poses * (m.row_end - m.row_begin) * m.W;
+    if (Refusal r = check_ray_count(n_rays, false)) return r;
+    if (n_rays > kAdaptiveMaxRays) return invalid("adaptive frame: more than 2^24 rays in one call");
+    if (k < 1 || k > kAdaptiveMaxK) return invalid("adaptive frame: k must be in 1..64");
+    if (tol_rgb != tol_rgb || tol_depth != tol_depth) return invalid("adaptive frame: the tolerances must not be NaN");
+    if (Refusal r = check_precision(precision)) return r;
+    // the two render launches are nwe_render_rays launches with lean outputs: what that call refuses of the context, in its words
+    static float somewhere;
+    nwe_outputs lean = {};
+    lean.struct_bytes = sizeof(nwe_outputs);
+    lean.rgb = &somewhere;
+    if (Refusal r = check_ready(d, &lean, precision, false, true)) return r;
+    if (d->host_only) return state("host-only context cannot render");
+    return {};
+}
+
 }  // namespace nwe

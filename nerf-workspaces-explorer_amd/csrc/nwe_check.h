@@ -114,5 +114,10 @@ Refusal check_render_grid(const ContextDesc* d, const nwe_grid_outputs* out, con
 Refusal check_render_sparse(const ContextDesc* d, const nwe_sparse_outputs* out, const Camera& m, int which, int precision, float min_weight,
                             int dilate);
 constexpr int kSparseMaxDilate = 8;
+// nwe_render_adaptive, in the order it refuses in: the context, the outputs, the camera, the ray count (nwe_render's, then the
+// call's own 2^24), k and the tolerances, the precision, everything check_ready refuses for a lean-output nwe_render_rays, and last -
+// so that everything in front can be asked of a host-only context - the device.
+Refusal check_adaptive(const ContextDesc* d, const nwe_adaptive_outputs* out, const Camera& m, int precision, int k, float tol_rgb,
+                       float tol_depth);
 
 }  // namespace nwe

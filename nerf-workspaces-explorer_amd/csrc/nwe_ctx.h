@@ -1,5 +1,5 @@
 // Private to the units of the C ABI (nwe_abi.hip: context, networks, the render, tiled, ray and query calls; nwe_abi_grids.hip: the
-// three grids and the grid frame; nwe_abi_sparse.hip: the sparse frames): the context, what it owns on its device, and the
+// three grids and the grid frame; nwe_abi_sparse.hip: the sparse frames; nwe_abi_adaptive.hip: the adaptive frame): the context, what it owns on its device, and the
 // helpers that more than one of the units needs (defined in nwe_abi.hip unless said otherwise).
 #pragma once
 #include <cstring>
@@ -198,6 +198,14 @@ struct nwe_ctx {
     int sparse_chunk = 0;     // nwe_debug_set_sparse_chunk: 0 = the default
     DevBuf<uint8_t> d_sparse_scratch;
     Owned<void*, hipHostFree> sparse_word;
+    // nwe_render_adaptive: a slot of its own for its pose table and the span of the call (nwe_last_adaptive) - its two render launches
+    // take slots of the render ring -, the scratch, grow-only, the pinned word the kind 1 count is read back through, and the counts of
+    // the last call that ran {pixels, lattice, rendered, interpolated}
+    Slot adaptive_slot;
+    DevBuf<uint8_t> d_adaptive_scratch;
+    Owned<void*, hipHostFree> adaptive_word;
+    int64_t adaptive_counts[4] = {0, 0, 0, 0};
+    bool adaptive_ran = false;
     const float* dbg_z_fine = nullptr;
     const float *dbg_raw_c = nullptr, *dbg_raw_f = nullptr, *dbg_w = nullptr;   // nwe_debug_set_raw / _coarse_weights, one call
     int fold = 1;             // nwe_debug_set_fold: read by nwe_set_network
@@ -252,6 +260,10 @@ float elapsed_ms(nwe_ctx* c, const Slot* last, const char* who);   // the time o
 // One query launch: the fp32 or the MFMA kernel by the precision, in its counted form (q.n_points a capacity, *count the points, on
 // the device) where `count` is given.  Refuses where the build has no MFMA query kernel for the network's shape.
 int run_query(nwe_ctx* c, const NetState& net, const QueryArgs& q, int precision, hipStream_t stream, const uint32_t* count = nullptr);
+// One render launch of a ray list on the next slot of the render ring, planned and carried out as every render launch is:
+// nwe_render_rays with its one-shot hooks and training tables (hooks), nwe_render_adaptive without.  The checks are the caller's.
+int render_ray_list(nwe_ctx* c, const ContextDesc& desc, const float* rays_dev, int64_t n_rays, int precision, const nwe_outputs& out, bool hooks,
+                    hipStream_t stream);
 CoarseGrid coarse_grid_args(const nwe_ctx* ctx);          // the context's grids as their kernels take them (nwe_abi_grids.hip)
 RadianceGrid radiance_grid_args(const nwe_ctx* ctx);
 

@@ -146,6 +146,34 @@ void launch_sparse_composite(const RenderArgs& a, const SparseChunk& c, hipStrea
 // nwe_render_sparse_async (nwe_sparse_async.hip): *tally += *c.total, behind the chunk's scan on `stream`
 void launch_sparse_tally(const SparseChunk& c, unsigned long long* tally, hipStream_t stream);
 
+// ---- adaptive frame (nwe_render_adaptive; nwe_adaptive.hip) ----
+// The frame of an adaptive call as its kernels read it (by value): the lattice axes of the call's rows and columns (nwe_plan.h), the
+// regions of the scratch (AdaptivePlan) and the caller's outputs.  Pixel p of the call is ray p of nwe_render's order, below 2^24.
+struct AdaptiveFrame {
+    AdaptiveAxis h, w;
+    int n_poses;
+    int pixels, lattice;        // of the whole call
+    float tol_rgb, tol_depth;
+    int32_t* list;              // [n]  the pixels of a render launch: the lattice's, then the kind 1 pixels in pixel order
+    float *c_rgb, *c_depth, *c_acc;   // compact outputs of both launches: the lattice pixels, [pose][i][j], then the kind 1 pixels
+    uint8_t* kinds;             // [pixels]
+    uint32_t* counts;           // [pixels] 1 for a kind 1 pixel, then the exclusive scan
+    uint8_t* busy;              // [n_poses][h.cells][w.cells]
+    uint32_t* total;            // [1] the kind 1 pixels
+    const uint32_t* render_flags;   // [1] what the two render launches raised
+    float *rgb, *depth, *acc;   // the caller's; each may be null
+    uint8_t* kind;
+    uint32_t* flags;
+};
+// the lattice pixels into f.list, pose-major, lattice rows then columns
+void launch_adaptive_lattice(const AdaptiveFrame& f, hipStream_t stream);
+// rays[i] = the row create_rays_kernel writes for pixel f.list[i] of the camera `a` (a.rays null), `cols` = 11 or 8 columns, i < n
+void launch_adaptive_rays(const RenderArgs& a, const AdaptiveFrame& f, int n, int cols, float* rays, hipStream_t stream);
+// cells -> busy marks; pixels -> kinds and counts; counts -> their exclusive scan and *total; the kind 1 pixels into f.list
+void launch_adaptive_classify(const AdaptiveFrame& f, hipStream_t stream);
+// every pixel of the frame from the compact outputs: copied (kind 0, 1) or interpolated (kind 2); the kinds and the flags
+void launch_adaptive_compose(const AdaptiveFrame& f, hipStream_t stream);
+
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);
 

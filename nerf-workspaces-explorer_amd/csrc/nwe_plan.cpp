@@ -187,4 +187,28 @@ SparsePlan plan_sparse(int64_t n_rays, int S, int chunk_hook) {
     return p;
 }
 
+AdaptivePlan plan_adaptive(int n_poses, int rows, int width, int k, int ray_cols) {
+    AdaptivePlan p;
+    p.h = adaptive_axis(rows, k); p.w = adaptive_axis(width, k);
+    p.n_poses = n_poses; p.cols = ray_cols;
+    p.pixels = (int64_t)n_poses * rows * width;
+    p.lattice = (int64_t)n_poses * p.h.n * p.w.n;
+    p.cells = (int64_t)n_poses * p.h.cells * p.w.cells;
+    p.list = p.lattice > p.pixels - p.lattice ? p.lattice : p.pixels - p.lattice;
+    const auto take = [&](int64_t n) { const int64_t at = p.bytes; p.bytes += (n + 255) / 256 * 256; return at; };
+    p.at_list = take(p.list * 4); p.at_rays = take(p.list * ray_cols * 4);
+    p.at_rgb = take(p.pixels * 12); p.at_depth = take(p.pixels * 4); p.at_acc = take(p.pixels * 4);
+    p.at_kind = take(p.pixels); p.at_counts = take(p.pixels * 4); p.at_busy = take(p.cells);
+    p.at_total = take(4); p.at_flags = take(4);
+    return p;
+}
+
+int adaptive_lattice(int first, int last_excl, int k, int32_t* out, int cap) {
+    if (first >= last_excl || (int64_t)last_excl - first > INT32_MAX - kAdaptiveMaxK || k < 1 || k > kAdaptiveMaxK || !out) return -1;
+    const AdaptiveAxis x = adaptive_axis(last_excl - first, k);
+    if (x.n > cap) return -1;
+    for (int i = 0; i < x.n; ++i) out[i] = first + adaptive_entry(x, i);
+    return x.n;
+}
+
 }  // namespace nwe

@@ -187,4 +187,45 @@ struct SparsePlan {
 };
 SparsePlan plan_sparse(int64_t n_rays, int S, int chunk_hook);
 
+// ---- adaptive frame (nwe_render_adaptive) ----
+constexpr int kAdaptiveMaxK = 64;
+constexpr int64_t kAdaptiveMaxRays = (int64_t)1 << 24;   // rays of a call at the most: bounds the scratch
+
+// One axis of a call's lattice (include/nwe.h), in LOCAL coordinates 0 .. len - 1 (a row axis: h - row_begin): the entries
+// {i k < len} and len - 1, ascending.  The kernels of nwe_adaptive.hip and the planner compile these few functions.
+struct AdaptiveAxis {
+    int len, k;
+    int n;        // lattice entries: ceil(len / k), and one more where len - 1 is no multiple of k
+    int cells;    // max(n - 1, 1): a single entry bounds one degenerate cell
+};
+NWE_HOST_DEVICE inline AdaptiveAxis adaptive_axis(int len, int k) {
+    AdaptiveAxis x;
+    x.len = len; x.k = k;
+    x.n = (len + k - 1) / k + ((len - 1) % k != 0 ? 1 : 0);
+    x.cells = x.n > 1 ? x.n - 1 : 1;
+    return x;
+}
+NWE_HOST_DEVICE inline int adaptive_entry(const AdaptiveAxis& x, int i) { const int v = i * x.k; return v < x.len - 1 ? v : x.len - 1; }   // i < n
+NWE_HOST_DEVICE inline bool adaptive_on_lattice(const AdaptiveAxis& x, int v) { return v % x.k == 0 || v == x.len - 1; }
+NWE_HOST_DEVICE inline int adaptive_index(const AdaptiveAxis& x, int v) { return v % x.k == 0 ? v / x.k : x.n - 1; }   // of a lattice coordinate
+// min(largest i with entry(i) <= v, cells - 1)
+NWE_HOST_DEVICE inline int adaptive_cell(const AdaptiveAxis& x, int v) { const int i = v / x.k; return i < x.cells - 1 ? i : x.cells - 1; }
+
+// The lattice and the scratch of an adaptive call.  The regions, in the order of their offsets, each rounded up to 256 bytes: the
+// pixel list (4 per ray of the larger launch), its rays (4 cols each), the compact rgb / depth / acc of both launches (lattice
+// first; 12 + 4 + 4 per pixel), the kinds (1 per pixel), the counts and their scan (4 per pixel), the cells' busy marks (1 per
+// cell), the total and the render launches' flag word (4 each).  n_poses, rows, width >= 1: a call without rays plans nothing.
+struct AdaptivePlan {
+    AdaptiveAxis h, w;
+    int n_poses = 0, cols = 0;
+    int64_t pixels = 0, lattice = 0, cells = 0;   // of the whole call
+    int64_t list = 0;                              // rays of a render launch at the most: max(lattice, pixels - lattice)
+    int64_t at_list = 0, at_rays = 0, at_rgb = 0, at_depth = 0, at_acc = 0, at_kind = 0, at_counts = 0, at_busy = 0, at_total = 0, at_flags = 0;
+    int64_t bytes = 0;
+};
+AdaptivePlan plan_adaptive(int n_poses, int rows, int width, int k, int ray_cols);
+// The lattice of [first, last_excl) in image coordinates, ascending, into out[0 .. cap): returns its entries, or -1 for an empty
+// range, k outside 1 .. kAdaptiveMaxK, a null array or one that is too small.
+int adaptive_lattice(int first, int last_excl, int k, int32_t* out, int cap);
+
 }  // namespace nwe

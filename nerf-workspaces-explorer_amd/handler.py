@@ -54,8 +54,16 @@ class NeRFReplicaInferenceHandler:
                  separate_passes: Optional[bool] = None, occupancy: Optional[Mapping[str, object]] = None,
                  baked_coarse: Optional[Mapping[str, object]] = None,
                  radiance_grid: Optional[Mapping[str, object]] = None,
-                 sparse_fine: Optional[Mapping[str, object]] = None, sparse_async: Optional[bool] = None) -> None:
-        """``sparse_async``: True, or NWE_SPARSE_ASYNC=1 in the environment, makes ``render_coordinates`` draw its sparse frame
+                 sparse_fine: Optional[Mapping[str, object]] = None, sparse_async: Optional[bool] = None,
+                 adaptive: Optional[Mapping[str, object]] = None) -> None:
+        """``adaptive``: a mapping with optional "k" (2), "tol_rgb" (2/255) and "tol_depth" (0.05): with it
+        ``render_coordinates(preview=False)`` draws its frame through ``render_adaptive_batch`` - every k-th pixel and the
+        pixels of the lattice cells whose corners disagree rendered by the networks, the rest interpolated
+        (Renderer.render_adaptive) - an approximation, off by default.  The environment variable NWE_ADAPTIVE =
+        "k,tol_rgb[,tol_depth]" overrides the three, and switches the option on for two-argument callers.  It is refused
+        together with ``sparse_fine``, ``early_termination > 0``, ``shared_coarse > 1``, ``occupancy``, ``baked_coarse`` and
+        ``devices``; previews are unchanged.
+        ``sparse_async``: True, or NWE_SPARSE_ASYNC=1 in the environment, makes ``render_coordinates`` draw its sparse frame
         through the asynchronous call (Renderer.render_sparse(asynchronous=True)): the same frame, queued instead of waited for
         chunk by chunk.  It is an option of ``sparse_fine``: given without it, a ValueError.  Off by default.
         ``sparse_fine``: a mapping with optional "min_weight" (1e-3), "dilate" (1) and "which" ("fine"): with it
@@ -177,6 +185,13 @@ class NeRFReplicaInferenceHandler:
         self._sparse_async = bool(sparse_async) if sparse_async is not None else env_async == "1"
         if self._sparse_async and self._sparse_fine is None:
             raise ValueError("sparse_async is an option of the sparse frame: give sparse_fine={...} (and a radiance grid) too")
+        self._adaptive = self.parse_adaptive(adaptive, os.environ.get("NWE_ADAPTIVE", ""))
+        if self._adaptive is not None:
+            for on, other in ((self._sparse_fine is not None, "sparse_fine"), (self._early_termination > 0.0, "early_termination > 0"),
+                              (self._shared_coarse > 1, "shared_coarse > 1"), (self._occupancy is not None, "an occupancy grid (occupancy)"),
+                              (self._baked_coarse is not None, "a baked coarse pass (baked_coarse)"), (bool(self._devices), "devices")):
+                if on:
+                    raise ValueError(f"adaptive (the adaptive frame) is not supported together with {other}")
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -239,6 +254,36 @@ class NeRFReplicaInferenceHandler:
         if opt["which"] not in ("coarse", "fine"):
             raise ValueError("sparse_fine: which must be 'coarse' or 'fine'")
         opt["min_weight"] = float(opt["min_weight"])
+        return opt
+
+    @staticmethod
+    def parse_adaptive(adaptive: Optional[Mapping[str, object]], env: str = "") -> Optional[Dict[str, object]]:
+        """The ``adaptive`` option with its defaults, NWE_ADAPTIVE = "k,tol_rgb[,tol_depth]" (``env``) laid over it; None when
+        neither is given."""
+        env = [v.strip() for v in env.split(",") if v.strip() != ""]
+        if adaptive is None and not env:
+            return None
+        opt = {"k": 2, "tol_rgb": 2 / 255, "tol_depth": 0.05}
+        if adaptive is not None:
+            unknown = set(adaptive) - set(opt)
+            if unknown:
+                raise ValueError(f"adaptive may hold k, tol_rgb, tol_depth; got {sorted(adaptive)}")
+            opt.update(adaptive)
+        if env and not 2 <= len(env) <= 3:
+            raise ValueError("NWE_ADAPTIVE must be k,tol_rgb[,tol_depth]")
+        try:
+            if env:
+                opt["k"], opt["tol_rgb"] = int(env[0]), float(env[1])
+            if len(env) > 2:
+                opt["tol_depth"] = float(env[2])
+        except ValueError:
+            raise ValueError("NWE_ADAPTIVE must be k,tol_rgb[,tol_depth]") from None
+        if isinstance(opt["k"], bool) or not isinstance(opt["k"], int) or not 1 <= opt["k"] <= _lib.ADAPTIVE_MAX_K:
+            raise ValueError("adaptive: k must be an integer in 1..64")
+        for key in ("tol_rgb", "tol_depth"):
+            if isinstance(opt[key], bool) or not isinstance(opt[key], (int, float)) or opt[key] != opt[key]:
+                raise ValueError(f"adaptive: {key} must be a number, not NaN")
+            opt[key] = float(opt[key])
         return opt
 
     # ------------------------------------------------------------------------------------------------
@@ -375,6 +420,8 @@ class NeRFReplicaInferenceHandler:
             elif self._sparse_fine is not None and not preview:
                 res = self.render_sparse_batch(camera_pose.numpy(), H, W, outputs=("rgb",), asynchronous=self._sparse_async,
                                                **self._sparse_fine)
+            elif self._adaptive is not None and not preview:
+                res = self.render_adaptive_batch(camera_pose.numpy(), H, W, outputs=("rgb",), **self._adaptive)
             else:
                 res = self.render_batch(camera_pose.numpy(), H, W, outputs=("rgb",))
         finally:
@@ -590,6 +637,36 @@ class NeRFReplicaInferenceHandler:
     def last_sparse_samples(self):
         """(selected, total) samples of the last sparse frame (Renderer.last_sparse_samples), None if there was none."""
         return self._sparse_renderer().last_sparse_samples()
+
+    def render_adaptive(self, camera_pose, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
+                        precision: Optional[str] = None, k: int = 2, tol_rgb: float = 2 / 255, tol_depth: float = 0.05,
+                        outputs: Sequence[str] = ("rgb",)) -> Dict[str, torch.Tensor]:
+        """``render`` as an adaptive frame (Renderer.render_adaptive): a lattice of every k-th pixel, the cells that are not flat,
+        the rest interpolated."""
+        res = self.render_adaptive_batch(np.asarray(camera_pose, dtype=np.float32).reshape(1, 4, 4), H, W, rows=rows, precision=precision,
+                                         k=k, tol_rgb=tol_rgb, tol_depth=tol_depth, outputs=outputs)
+        return {name: v if name == "flags" else v[0] for name, v in res.items()}
+
+    def render_adaptive_batch(self, poses, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
+                              precision: Optional[str] = None, k: int = 2, tol_rgb: float = 2 / 255, tol_depth: float = 0.05,
+                              outputs: Sequence[str] = ("rgb",)) -> Dict[str, torch.Tensor]:
+        """``render_batch`` as an adaptive frame: [B,4,4] poses -> tensors with leading [B, h, W]; each pose has its own lattice."""
+        r = self._need_renderer()
+        if isinstance(r, TiledRenderer):
+            raise NotImplementedError("the adaptive frame is rendered by one device (its lattice belongs to the rows of a call): not with devices")
+        H = self._img_h if H is None else H
+        W = self._img_w if W is None else W
+        fx, fy, cx, cy = pinhole_intrinsics(H, W)
+        poses = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4)
+        r0, r1 = rows if rows is not None else (0, H)
+        res = r.render_adaptive(poses, H, W, fx=fx, fy=fy, cx=cx, cy=cy, near=self._depth_close_bound, far=self._depth_far_bound,
+                                rows=(r0, r1), precision=precision or self._precision, k=k, tol_rgb=tol_rgb, tol_depth=tol_depth,
+                                outputs=outputs)
+        return {name: v if name == "flags" else v.reshape((poses.shape[0], r1 - r0, W) + tuple(v.shape[1:])) for name, v in res.items()}
+
+    def last_adaptive(self):
+        """The counts and the device span of the last adaptive frame (Renderer.last_adaptive), None if there was none."""
+        return self._need_renderer().last_adaptive()
 
     @property
     def coarse_grid(self):

@@ -724,6 +724,64 @@ class Renderer:
         if self._lib.nwe_debug_set_sparse_chunk(self._ctx, int(rays)) != _lib.NWE_OK:
             raise ValueError("the sparse chunk must be 0 (the default) or a number of rays of at least 1")
 
+    # -- adaptive frame ---------------------------------------------------------------------------
+    def render_adaptive(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
+                        rows: Optional[Tuple[int, int]] = None, precision: str = "f16x3", k: int = 2, tol_rgb: float = 2 / 255,
+                        tol_depth: float = 0.05, outputs: Sequence[str] = ("rgb",)) -> Dict[str, torch.Tensor]:
+        """An adaptive frame (nwe_render_adaptive): the lattice of every ``k``-th pixel and the pixels of the lattice cells whose
+        corners differ by more than ``tol_rgb`` (r, g, b, acc) or ``tol_depth`` are rendered by the networks, bit for bit as
+        ``render`` renders them; the pixels of the other cells are interpolated bilinearly.  Synchronous.  ``outputs``: a choice
+        of "rgb", "depth", "acc" (at least one) and the diagnostic "kind" [R] (uint8: 0 lattice, 1 rendered, 2 interpolated);
+        "flags" is always returned."""
+        outputs = tuple(outputs)
+        unknown = set(outputs) - set(_lib.ADAPTIVE_OUTPUT_FIELDS[:-1])
+        if unknown:
+            raise ValueError(f"unknown adaptive outputs {sorted(unknown)}; have {_lib.ADAPTIVE_OUTPUT_FIELDS[:-1]}")
+        poses = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(-1, 4, 4))
+        r0, r1 = rows if rows is not None else (0, H)
+        o = _lib.AdaptiveOutputs()
+        tail = (r0, r1, _lib.PRECISIONS[precision], int(k), float(tol_rgb), float(tol_depth))
+        call = self._lib.nwe_render_adaptive
+        if self.device is None:   # a host-only context: the ABI's own refusals, nothing allocated
+            for name in outputs:
+                setattr(o, name, 1)   # never written: every path of a host-only context refuses
+            self._check(call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail, C.byref(o), None),
+                        "nwe_render_adaptive")
+            raise RuntimeError("nwe_render_adaptive: a host-only context rendered")   # not reached
+        n_rays = poses.shape[0] * max(r1 - r0, 0) * W
+        shapes = {"rgb": (n_rays, 3), "depth": (n_rays,), "acc": (n_rays,), "kind": (n_rays,)}
+        with torch.cuda.device(self.device):
+            # at least one element each: an empty tensor has no pointer, and a call of zero rays still says what it asks for
+            bufs = {name: torch.empty(max(int(np.prod(shapes[name])), 1), dtype=torch.uint8 if name == "kind" else torch.float32,
+                                      device=self.device) for name in outputs}
+            res = {name: bufs[name][:int(np.prod(shapes[name]))].view(shapes[name]) for name in outputs}
+            res["flags"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            for name in _lib.ADAPTIVE_OUTPUT_FIELDS:
+                setattr(o, name, (bufs[name] if name in bufs else res[name]).data_ptr() if name in res else None)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail, C.byref(o), stream)
+        self._check(rc, "nwe_render_adaptive")
+        return res
+
+    def last_adaptive(self) -> Optional[Dict[str, object]]:
+        """{"pixels", "lattice", "rendered", "interpolated", "ms"} of the last ``render_adaptive`` call that ran (ms: its device
+        span, the read-back between its two render launches included), None if there was none."""
+        out, ms = (C.c_int64 * 4)(), C.c_float(-1.0)
+        if self._lib.nwe_last_adaptive(self._ctx, out, C.byref(ms)) != _lib.NWE_OK:
+            return None
+        return {"pixels": int(out[0]), "lattice": int(out[1]), "rendered": int(out[2]), "interpolated": int(out[3]), "ms": float(ms.value)}
+
+    @staticmethod
+    def adaptive_lattice(first: int, last_excl: int, k: int) -> np.ndarray:
+        """The lattice rows (or columns) of [first, last_excl) at ``k`` (nwe_debug_adaptive_lattice; needs no context)."""
+        lib = _lib.load()
+        cap = max(int(last_excl) - int(first), 1)
+        out = (C.c_int32 * cap)()
+        n = lib.nwe_debug_adaptive_lattice(int(first), int(last_excl), int(k), out, cap)
+        if n < 0:
+            raise ValueError("adaptive lattice: an empty range, or k outside 1..64")
+        return np.array(out[:n], dtype=np.int32)
+
     def last_coarse_launch(self) -> Optional[Tuple[float, int]]:
         """(ms, rays) of the coarse (producer) launch of the last render, None if it had none (k = 1 without separate passes,
         n_importance == 0)."""
