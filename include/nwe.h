@@ -771,7 +771,11 @@ unsigned nwe_debug_query_counted_grid(int64_t capacity, int packet, int forced_s
  * the call with nwe_render_rays' codes and texts.  The one-shot hooks and the training tables are neither used nor cleared (unlike
  * nwe_render_rays); the radiance grid is not read.
  * COST: a launch of precomputed rays is not lean, so a rendered pixel costs what a ray of nwe_render_rays costs - it pays for the
- * coarse colour and has no hollow path - not what a pixel of nwe_render costs (DESIGN.md 5.10 has the measurements).
+ * coarse colour and has no hollow path - not what a pixel of nwe_render costs (DESIGN.md 5.10 has the measurements).  Under
+ * nwe_set_adaptive_pixel_lists (opt-in, off by default) each of the two render launches for which the list kernels of
+ * nwe_render_pixels can serve the call (an MFMA precision, networks packed in a product formulation, no separate passes) hands
+ * them the call's pixel list in place of a ray table: such a launch is lean, and outputs, kinds, counts and flags are the same
+ * bits with the switch on and off.  Where they cannot, the call runs as without the switch.
  * The scratch (pixel lists, rays, compact outputs, kinds, counts: about 70 bytes per pixel) is the context's own, grow-only.
  * Refuses in this order, before anything is queued: a NULL context; NULL out, a wrong struct_bytes, none of rgb / depth / acc
  * requested (NWE_ERR_INVALID); the camera and the ray count as nwe_render refuses them; more than 2^24 rays; k outside 1 .. 64, a NaN
@@ -794,6 +798,49 @@ int nwe_render_adaptive(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int 
                         const nwe_adaptive_outputs *out, void *stream);
 int nwe_last_adaptive(nwe_ctx *ctx, int64_t *out4, float *ms);
 int nwe_debug_adaptive_lattice(int first, int last_excl, int k, int32_t *out, int cap);
+/* The switch of the COST paragraph above.  Host-side like nwe_set_separate_passes: 0 or 1, anything else is NWE_ERR_INVALID, and it
+ * works on a host-only context; the getter returns -1 for a NULL context. */
+int nwe_set_adaptive_pixel_lists(nwe_ctx *ctx, int on);
+int nwe_get_adaptive_pixel_lists(const nwe_ctx *ctx);
+
+/* Pixel list: render any subset of the pixels of a pinhole view, in any order, on lean kernels.
+ * The camera arguments are nwe_render's.  pixels_dev[i] is an output ray index of nwe_render with the same camera arguments,
+ * (p * (row_end - row_begin) + (h - row_begin)) * W + w, and output row i holds, bit for bit, what nwe_render writes to that row.
+ * Any order; duplicates are allowed.  A value outside [0, n_poses * rows * W) renders the clamped pixel (below 0: pixel 0, else the
+ * last): defined, and never an out-of-range read.
+ * Flags.  Only the rgb / depth / acc bits are reported, whichever path ran (the adaptive frame's rule): the launch raises its bits
+ * into a word of its slot's and a one-thread kernel ORs the masked word into the caller's.
+ * ASYNCHRONOUS on `stream`, like nwe_render: poses are staged before the call returns; the list must stay valid until the stream
+ * has passed the call.  The call is an ordinary launch on the render ring: nwe_last_kernel_ms, nwe_last_launch_parts,
+ * nwe_debug_last_plan and nwe_last_ray_evaluations (executed == full) describe it.  nwe_set_white_background is honoured.
+ * PATH.  Under an MFMA precision, when the one shape both networks share has list kernels - both are packed in a product
+ * formulation - and separate passes are off, the call takes the LIST KERNELS: the lean kernels of nwe_render (density-only coarse
+ * pass, hollow colour path, both work decompositions, the work queue) that read each ray's pixel from the list.  The launch is
+ * planned as the same number of rays of nwe_render_rays is: no packet blocks, no tail path.  Every other legal call - NWE_PREC_F32,
+ * separate passes, a network packed unfolded (nwe_debug_set_fold(0)), a shape without list kernels - renders through a RAY TABLE:
+ * the rows nwe_create_rays writes for the clamped pixels, into a buffer the launch's slot owns, then nwe_render_rays' launch.  The
+ * bits are the same; the cost is that of nwe_render_rays.  nwe_last_pixels says which path the last launch took (path: 1 list
+ * kernels, 0 ray table; a render launch of nwe_render_adaptive under nwe_set_adaptive_pixel_lists counts as one); NWE_ERR_STATE if
+ * none ran.  nwe_debug_pixels_path answers for a call that is not made: 1 / 0, -1 for a NULL context or an unknown precision; a
+ * host-only context serves it.
+ * Refuses in this order, before anything is queued: a NULL context; NULL out, a wrong struct_bytes, none of rgb / depth / acc
+ * requested (NWE_ERR_INVALID); the camera and its ray count as nwe_render refuses them; n_pixels < 0 or >= 2^31, or NULL pixels_dev
+ * with n_pixels > 0 (NWE_ERR_INVALID); an unknown precision; everything nwe_render_rays refuses of the context for lean outputs, in
+ * its codes and texts (networks, sampling, shapes; early termination, the shared coarse pass, an occupancy grid and a baked coarse
+ * pass); last, a host-only context (NWE_ERR_STATE).  n_pixels == 0 is NWE_OK and launches nothing.  The one-shot hooks and the
+ * training tables are neither used nor cleared. */
+typedef struct nwe_pixel_outputs {
+    uint64_t struct_bytes;  /* = sizeof(nwe_pixel_outputs) */
+    float *rgb;             /* [n,3] */
+    float *depth;           /* [n]   */
+    float *acc;             /* [n]   */
+    uint32_t *flags;        /* [1]    NWE_FLAG_RGB / _DEPTH / _ACC, OR-ed (caller zeroes it) */
+} nwe_pixel_outputs;
+int nwe_render_pixels(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy, float near,
+                      float far, int row_begin, int row_end, const int32_t *pixels_dev, int64_t n_pixels, int precision,
+                      const nwe_pixel_outputs *out, void *stream);
+int nwe_last_pixels(nwe_ctx *ctx, int64_t *n_pixels, int *path);
+int nwe_debug_pixels_path(const nwe_ctx *ctx, int precision);
 
 /* The producer launch of the most recent render launch (the one nwe_last_kernel_ms describes, under the same rules; blocks like
  * it): *ms = its time, *rays = the representative rays it walked; -1 / 0 when that launch had none (k = 1 without separate
@@ -900,7 +947,7 @@ typedef struct nwe_plan_stage {
     int64_t n_rays;       /* the stage's rays: the producer's are the representatives */
     int32_t n_importance;
     int32_t net;          /* the network (0 coarse, 1 fine) in both descriptor slots, -1: (coarse, fine) */
-    int32_t variant;      /* the kernels: 0 plain, 1 terminating, 2 sharing, 3 occupancy grid; -1: the grid producer of a baked coarse pass */
+    int32_t variant;      /* the kernels: 0 plain, 1 terminating, 2 sharing, 3 occupancy grid, 5 pixel list (nwe_render_pixels); -1: the grid producer of a baked coarse pass */
     int32_t plan;         /* nwe_debug_last_plan: 0 packets, 1 sample split, 2 packets + split rest; -1: that producer, which has none */
     int32_t n_launches;   /* 1, or 2 under plan 2 */
     int32_t fork;         /* 0 the second launch follows the first on the caller's stream; it goes to the side stream, which forks

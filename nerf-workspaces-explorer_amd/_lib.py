@@ -37,7 +37,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_render_sparse", "nwe_debug_set_sparse_chunk", "nwe_last_sparse_ms", "nwe_last_sparse_samples",
            "nwe_render_sparse_async", "nwe_debug_last_sparse_host_waits", "nwe_debug_query_counted_grid",
            "nwe_debug_set_packet_blocks", "nwe_debug_last_packet_blocks", "nwe_debug_packet_pixels",
-           "nwe_render_adaptive", "nwe_last_adaptive", "nwe_debug_adaptive_lattice")
+           "nwe_render_adaptive", "nwe_last_adaptive", "nwe_debug_adaptive_lattice",
+           "nwe_set_adaptive_pixel_lists", "nwe_get_adaptive_pixel_lists", "nwe_render_pixels", "nwe_last_pixels", "nwe_debug_pixels_path")
 
 
 class Outputs(C.Structure):
@@ -91,6 +92,18 @@ class AdaptiveOutputs(C.Structure):
 
     def __init__(self, **kw):
         super().__init__(struct_bytes=C.sizeof(AdaptiveOutputs), **kw)
+
+
+PIXEL_OUTPUT_FIELDS = ("rgb", "depth", "acc", "flags")
+FLAG_RGB, FLAG_DEPTH, FLAG_ACC = 1, 2, 4
+
+
+class PixelOutputs(C.Structure):
+    """nwe_pixel_outputs of nwe_render_pixels."""
+    _fields_ = [("struct_bytes", C.c_uint64)] + [(name, C.c_void_p) for name in PIXEL_OUTPUT_FIELDS]
+
+    def __init__(self, **kw):
+        super().__init__(struct_bytes=C.sizeof(PixelOutputs), **kw)
 
 
 PLAN_HOOK_COARSE_WEIGHTS, PLAN_HOOK_OTHER = 1, 2
@@ -216,6 +229,11 @@ def load() -> C.CDLL:
         "nwe_render_adaptive": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, I, I, F, F, C.POINTER(AdaptiveOutputs), P]),
         "nwe_last_adaptive": (I, [P, C.POINTER(I64), C.POINTER(F)]),
         "nwe_debug_adaptive_lattice": (I, [I, I, I, C.POINTER(C.c_int32), I]),
+        "nwe_set_adaptive_pixel_lists": (I, [P, I]),
+        "nwe_get_adaptive_pixel_lists": (I, [P]),
+        "nwe_render_pixels": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, P, I64, I, C.POINTER(PixelOutputs), P]),
+        "nwe_last_pixels": (I, [P, C.POINTER(I64), C.POINTER(I)]),
+        "nwe_debug_pixels_path": (I, [P, I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

@@ -1,6 +1,6 @@
 // C ABI of libnwe_hip.so (include/nwe.h): the context and what the units of the ABI share (nwe_ctx.h), networks and sampling, the
 // render, tiled, ray and query calls, their reports, the debug switches.  The grids: nwe_abi_grids.hip; the sparse frames:
-// nwe_abi_sparse.hip; the adaptive frame: nwe_abi_adaptive.hip.  Weight packing: nwe_pack.cpp; planning: nwe_plan.cpp; the refusals: nwe_check.cpp.
+// nwe_abi_sparse.hip; the adaptive frame: nwe_abi_adaptive.hip; the pixel list: nwe_abi_pixels.hip.  Weight packing: nwe_pack.cpp; planning: nwe_plan.cpp; the refusals: nwe_check.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -202,7 +202,7 @@ constexpr bool kStampedBuild = false;
 #endif
 
 // The call as the planner sees it (nwe_plan.h): `a` as the entry point and context_args() filled it, the context's modes.
-CallDesc describe_call(const ContextDesc& ctx, const RenderArgs& a, int precision) {
+CallDesc describe_call(const ContextDesc& ctx, const RenderArgs& a, int precision, bool list = false) {
     CallDesc d;
     d.n_rays = a.n_rays;
     RenderArgs consumer = a;
@@ -216,6 +216,8 @@ CallDesc describe_call(const ContextDesc& ctx, const RenderArgs& a, int precisio
     d.baked = ctx.cgrid.set;   // check_ready has let nothing but lean pinhole calls through
     RenderArgs unstamped = a;
     unstamped.stamps = nullptr;
+    d.list = list;
+    if (list) unstamped.rays = nullptr;   // the pixel list, no ray table: the list kernels make the rays themselves
     d.lean = mfma_is_lean(unstamped); d.stamps = a.stamps != nullptr; d.stamped_build = kStampedBuild;
     d.w_in = a.w_in != nullptr;
     d.want_weights_coarse = a.out.weights_coarse != nullptr; d.want_flags = a.out.flags != nullptr;
@@ -287,10 +289,18 @@ RenderArgs stage_args(const CallPlan& p, const RenderSlot& slot, RenderArgs& a) 
 
 // A render launch on the ring slot prepare_slot() made ready (ctx->render.next()): describe the call, plan it, carry
 // the plan out.  The ring moves on here, once the launch has been recorded.
-int launch(nwe_ctx* ctx, const ContextDesc& desc, RenderSlot& slot, RenderArgs& a, int precision, hipStream_t stream) {
+int launch(nwe_ctx* ctx, const ContextDesc& desc, RenderSlot& slot, RenderArgs& a, int precision, hipStream_t stream, bool list = false,
+           uint32_t flags_mask = 0) {
     context_args(ctx, a);
     if (a.n_rays <= 0) return NWE_OK;
-    const CallPlan p = plan_call(describe_call(desc, a, precision), ctx->cus);
+    const CallPlan p = plan_call(describe_call(desc, a, precision, list), ctx->cus);
+    // a pixel-list call: the launch's flag bits go through a word of the slot's, the masked bits from there to the caller's
+    uint32_t* const masked_flags = flags_mask ? a.out.flags : nullptr;
+    if (masked_flags) {
+        HIPCHK(ctx, slot.pixel_flags.reserve(1));
+        HIPCHK(ctx, hipMemsetAsync(slot.pixel_flags.get(), 0, sizeof(uint32_t), stream));
+        a.out.flags = slot.pixel_flags.get();
+    }
     const bool mfma = precision != NWE_PREC_F32, three_pass = precision == NWE_PREC_F16X3;
     TRY(provide(ctx, slot, p, stream));
     const RenderArgs prod = stage_args(p, slot, a);
@@ -350,6 +360,7 @@ int launch(nwe_ctx* ctx, const ContextDesc& desc, RenderSlot& slot, RenderArgs& 
             (void)hipStreamSynchronize(slot.side);
             return fail(ctx, NWE_ERR_HIP, std::string("work queue: joining the side stream: ") + hipGetErrorString(hipGetLastError()));
         }
+        if (masked_flags) hipLaunchKernelGGL(or_masked_flags_kernel, dim3(1), dim3(1), 0, stream, a.out.flags, flags_mask, masked_flags);
         if (mfma) ctx->last_plan = pass.plan;
         slot.side_used = report.side_used; slot.has_mid = report.mid_recorded;
         return NWE_OK;
@@ -379,7 +390,7 @@ int render_rows(nwe_ctx* c, const Camera& m, int precision, const nwe_outputs* o
 namespace nwe {
 
 int render_ray_list(nwe_ctx* c, const ContextDesc& desc, const float* rays_dev, int64_t n_rays, int precision, const nwe_outputs& out, bool hooks,
-                    hipStream_t stream) {
+                    hipStream_t stream, uint32_t flags_mask) {
     RenderSlot& slot = c->render.next();
     TRY(prepare_slot(c, slot));
     RenderArgs a = {};
@@ -390,7 +401,19 @@ int render_ray_list(nwe_ctx* c, const ContextDesc& desc, const float* rays_dev, 
         a.t_rand = c->trn_t; a.noise_c = c->trn_nc; a.noise_f = c->trn_nf; a.u_rand = c->trn_u;
     }
     a.out = out;
-    return launch(c, desc, slot, a, precision, stream);
+    return launch(c, desc, slot, a, precision, stream, false, flags_mask);
+}
+
+int render_pixel_list(nwe_ctx* c, const ContextDesc& desc, const RenderArgs& cam, int n_poses, const int32_t* list_dev, int64_t n, int precision,
+                      const nwe_outputs& out, hipStream_t stream, uint32_t flags_mask) {
+    RenderSlot& slot = c->render.next();
+    TRY(prepare_slot(c, slot));
+    RenderArgs a = cam;
+    a.rays = reinterpret_cast<const float*>(list_dev);   // the list kernels read the slot as int32 (render_mfma_list_kernel)
+    a.ray_cols = n_poses;                                // ... and clamp a listed pixel to the rays of the camera's own frame
+    a.n_rays = n;
+    a.out = out;
+    return launch(c, desc, slot, a, precision, stream, true, flags_mask);
 }
 
 }  // namespace nwe

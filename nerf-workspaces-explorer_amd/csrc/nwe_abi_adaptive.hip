@@ -6,14 +6,21 @@ namespace {
 
 // One render launch of the call: the rays of the first n pixels of the list, rendered into the compact outputs from `first` on, the
 // flags into the scratch's word.  rgb, depth and acc are always rendered: the cells are judged on all of them.
+// Under nwe_set_adaptive_pixel_lists, where the list kernels can serve the call (pixel_list_path), the list itself is the launch's
+// input - it is in nwe_render's ray order, which is what the list kernels read - and no ray table is written: the same bits.
 int render_list(nwe_ctx* c, const ContextDesc& desc, const RenderArgs& cam, const AdaptiveFrame& f, const AdaptivePlan& p, float* rays, uint32_t* flags,
                 int64_t first, int n, int precision, hipStream_t stream) {
-    launch_adaptive_rays(cam, f, n, p.cols, rays, stream);
-    HIPCHK(c, hipGetLastError());
     nwe_outputs o = {};
     o.struct_bytes = sizeof(nwe_outputs);
     o.rgb = f.c_rgb + first * 3; o.depth = f.c_depth + first; o.acc = f.c_acc + first;
     o.flags = flags;
+    if (c->adaptive_lists && pixel_list_path(desc, precision)) {
+        TRY(render_pixel_list(c, desc, cam, p.n_poses, f.list, n, precision, o, stream));
+        c->pixels_n = n; c->pixels_path = 1;
+        return NWE_OK;
+    }
+    launch_adaptive_rays(cam, f, n, p.cols, rays, stream);
+    HIPCHK(c, hipGetLastError());
     return render_ray_list(c, desc, rays, n, precision, o, false, stream);
 }
 

@@ -383,4 +383,38 @@ Refusal check_adaptive(const ContextDesc* d, const nwe_adaptive_outputs* out, co
     return {};
 }
 
+Refusal check_adaptive_pixel_lists(int on) {
+    if (on != 0 && on != 1) return invalid("adaptive_pixel_lists must be 0 or 1 (0 = off)");
+    return {};
+}
+
+Refusal check_pixels(const ContextDesc* d, const nwe_pixel_outputs* out, const Camera& m, int64_t n_pixels, bool null_pixels, int precision) {
+    if (!d) return invalid("null context");
+    if (!out) return invalid("null outputs");
+    if (out->struct_bytes != sizeof(nwe_pixel_outputs))
+        return invalid("nwe_pixel_outputs.struct_bytes != sizeof(nwe_pixel_outputs): the caller was built against another version of include/nwe.h");
+    if (!out->rgb && !out->depth && !out->acc) return invalid("none of rgb / depth / acc requested");
+    if (Refusal r = check_camera(m)) return r;
+    if (Refusal r = check_ray_count((int64_t)m.n_poses * (m.row_end - m.row_begin) * m.W, false)) return r;
+    if (n_pixels < 0 || n_pixels > INT32_MAX || (null_pixels && n_pixels > 0)) return invalid("bad pixels (null, a negative count, or more than 2^31 - 1)");
+    if (Refusal r = check_precision(precision)) return r;
+    // the launch is an nwe_render_rays launch with lean outputs, or stands in for one: what that call refuses of the context, in its words
+    static float somewhere;
+    nwe_outputs lean = {};
+    lean.struct_bytes = sizeof(nwe_outputs);
+    lean.rgb = &somewhere;
+    if (Refusal r = check_ready(d, &lean, precision, false, true)) return r;
+    if (d->host_only) return state("host-only context cannot render");
+    return {};
+}
+
+bool pixel_list_path(const ContextDesc& d, int precision) {
+    if (precision == NWE_PREC_F32 || d.separate || d.stamps) return false;
+    const NetDesc &nc = d.net[0], &nf = d.net[1];
+    if (!nc.set || !nc.mfma_ok || !nc.built[kVariantList]) return false;
+    if (d.ni > 0 && (!nf.set || !nf.mfma_ok || !nf.built[kVariantList] || nf.D != nc.D || nf.W != nc.W || nf.skip != nc.skip || nf.form != nc.form))
+        return false;
+    return true;
+}
+
 }  // namespace nwe

@@ -119,5 +119,15 @@ constexpr int kSparseMaxDilate = 8;
 // so that everything in front can be asked of a host-only context - the device.
 Refusal check_adaptive(const ContextDesc* d, const nwe_adaptive_outputs* out, const Camera& m, int precision, int k, float tol_rgb,
                        float tol_depth);
+Refusal check_adaptive_pixel_lists(int on);
+// nwe_render_pixels, in the order it refuses in: the context, the outputs, the camera and its ray count as nwe_render refuses them,
+// the list (null_pixels: no list was given), the precision, everything check_ready refuses for a lean-output nwe_render_rays, and
+// last - so that everything in front can be asked of a host-only context - the device.
+Refusal check_pixels(const ContextDesc* d, const nwe_pixel_outputs* out, const Camera& m, int64_t n_pixels, bool null_pixels, int precision);
+// Which way a pixel list that check_pixels (or check_adaptive) has let through is rendered: true = the list kernels (kVariantList),
+// false = a ray table through nwe_render_rays' launch.  The list kernels are taken under an MFMA precision when both networks that
+// run have one shape whose list kernels are built - which says that they are packed in a product formulation - and neither
+// separate passes nor a stamp buffer ask for other kernels.
+bool pixel_list_path(const ContextDesc& d, int precision);
 
 }  // namespace nwe

@@ -1,5 +1,5 @@
 // Private to the units of the C ABI (nwe_abi.hip: context, networks, the render, tiled, ray and query calls; nwe_abi_grids.hip: the
-// three grids and the grid frame; nwe_abi_sparse.hip: the sparse frames; nwe_abi_adaptive.hip: the adaptive frame): the context, what it owns on its device, and the
+// three grids and the grid frame; nwe_abi_sparse.hip: the sparse frames; nwe_abi_adaptive.hip: the adaptive frame; nwe_abi_pixels.hip: the pixel list): the context, what it owns on its device, and the
 // helpers that more than one of the units needs (defined in nwe_abi.hip unless said otherwise).
 #pragma once
 #include <cstring>
@@ -101,6 +101,11 @@ struct RenderSlot : Slot {
     bool side_used = false;
     // the tail path (nwe_debug_last_tail): the split items of a launch that took it, whose third counter lies behind the two
     unsigned tail_items = 0;
+    // pixel list (nwe_render_pixels): the word the launch's flags go through (or_masked_flags_kernel: only the rgb / depth / acc bits
+    // reach the caller's) and, where the call renders through a ray table, the clamped list and the table (last reader: prepare_slot)
+    DevBuf<uint32_t> pixel_flags;
+    DevBuf<int32_t> pixel_list;
+    DevBuf<float> pixel_rays;
 };
 
 // The box of either grid of a context, as its checks let it through (check_grid_box).
@@ -206,6 +211,11 @@ struct nwe_ctx {
     Owned<void*, hipHostFree> adaptive_word;
     int64_t adaptive_counts[4] = {0, 0, 0, 0};
     bool adaptive_ran = false;
+    int adaptive_lists = 0;   // nwe_set_adaptive_pixel_lists: 0 = off
+    // nwe_last_pixels: the last pixel-list launch that was recorded - nwe_render_pixels, or a render launch of the adaptive frame
+    // under nwe_set_adaptive_pixel_lists - its pixels and its path (1 list kernels, 0 ray table); -1: none yet
+    int64_t pixels_n = 0;
+    int pixels_path = -1;
     const float* dbg_z_fine = nullptr;
     const float *dbg_raw_c = nullptr, *dbg_raw_f = nullptr, *dbg_w = nullptr;   // nwe_debug_set_raw / _coarse_weights, one call
     int fold = 1;             // nwe_debug_set_fold: read by nwe_set_network
@@ -262,8 +272,15 @@ float elapsed_ms(nwe_ctx* c, const Slot* last, const char* who);   // the time o
 int run_query(nwe_ctx* c, const NetState& net, const QueryArgs& q, int precision, hipStream_t stream, const uint32_t* count = nullptr);
 // One render launch of a ray list on the next slot of the render ring, planned and carried out as every render launch is:
 // nwe_render_rays with its one-shot hooks and training tables (hooks), nwe_render_adaptive without.  The checks are the caller's.
+// flags_mask != 0: the launch raises its flag bits into a word of its slot's, and only the bits of the mask reach out.flags.
 int render_ray_list(nwe_ctx* c, const ContextDesc& desc, const float* rays_dev, int64_t n_rays, int precision, const nwe_outputs& out, bool hooks,
-                    hipStream_t stream);
+                    hipStream_t stream, uint32_t flags_mask = 0);
+// One render launch of a pixel list on the list kernels (render_mfma_list_kernel), on the next slot of the render ring: ray i is
+// the ray of pixel list_dev[i], clamped, of the pinhole view `cam` (camera_args over a pose table on the device that stays valid
+// until the launch has run) with n_poses poses.  The caller has checked pixel_list_path (nwe_check.h); lean outputs only.
+int render_pixel_list(nwe_ctx* c, const ContextDesc& desc, const RenderArgs& cam, int n_poses, const int32_t* list_dev, int64_t n, int precision,
+                      const nwe_outputs& out, hipStream_t stream, uint32_t flags_mask = 0);
+int prepare_slot(nwe_ctx* c, RenderSlot& s);              // ... and forgets the render slot's parts
 CoarseGrid coarse_grid_args(const nwe_ctx* ctx);          // the context's grids as their kernels take them (nwe_abi_grids.hip)
 RadianceGrid radiance_grid_args(const nwe_ctx* ctx);
 

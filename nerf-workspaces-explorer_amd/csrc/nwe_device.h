@@ -30,6 +30,8 @@ struct RenderArgs {
     // ray source: either precomputed rays [n_rays,11] or pinhole poses
     const float* rays;       // device, may be null -> generate from poses
     int ray_cols;            // columns of `rays`: 11, or 8 for networks without view directions (rays.py:22-30)
+                             // The list kernels only (render_mfma_list_kernel): `rays` holds the call's pixel list, int32 [n_rays],
+                             // and ray_cols the poses of the camera - a listed pixel is clamped to ray_cols * rows * W - 1
     unsigned queue_items;    // a queued launch (`queue` below): its work items; in the padding in front of the pointer
     const float* poses;      // device, n_poses x 16 (row-major c2w)
     int64_t n_rays;          // total rays of the call

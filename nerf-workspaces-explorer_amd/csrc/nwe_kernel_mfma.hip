@@ -9,7 +9,7 @@ namespace nwe {
 #define NWE_DECLARE_SHAPE(W_, D_, SKIP_, FORM_)                                                                                   \
     NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantPlain) NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantTerm)   \
     NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantShare) NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantOcc)    \
-    NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantTail)                                                                \
+    NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantTail) NWE_EXTERN_SHAPE_LAUNCHER(W_, D_, SKIP_, FORM_, kVariantList)    \
     NWE_EXTERN_SHAPE_QUERY_LAUNCHER(W_, D_, SKIP_, FORM_) NWE_EXTERN_SHAPE_QUERY_COUNTED_LAUNCHER(W_, D_, SKIP_, FORM_)
 NWE_SHAPES(NWE_DECLARE_SHAPE)
 #undef NWE_DECLARE_SHAPE
@@ -63,9 +63,10 @@ struct ShapeRow {
     {W_, D_, SKIP_, FORM_, Shape<W_, D_>::n_chunks(FORM_),                                                                   \
      {render_launcher<W_, D_, SKIP_, FORM_, kVariantPlain>(), render_launcher<W_, D_, SKIP_, FORM_, kVariantTerm>(),         \
       render_launcher<W_, D_, SKIP_, FORM_, kVariantShare>(), render_launcher<W_, D_, SKIP_, FORM_, kVariantOcc>(),          \
-      render_launcher<W_, D_, SKIP_, FORM_, kVariantTail>()},                                                               \
+      render_launcher<W_, D_, SKIP_, FORM_, kVariantTail>(), render_launcher<W_, D_, SKIP_, FORM_, kVariantList>()},         \
      query_launcher<W_, D_, SKIP_, FORM_>(), query_counted_launcher<W_, D_, SKIP_, FORM_>()},
-static_assert(kVariantPlain == 0 && kVariantTerm == 1 && kVariantShare == 2 && kVariantOcc == 3 && kVariantTail == 4 && kVariants == 5,
+static_assert(kVariantPlain == 0 && kVariantTerm == 1 && kVariantShare == 2 && kVariantOcc == 3 && kVariantTail == 4 && kVariantList == 5 &&
+              kVariants == 6,
               "a row lists its launchers in the order of Variant");
 static const ShapeRow kShapes[] = {NWE_SHAPES(NWE_SHAPE_ROW)};
 #undef NWE_SHAPE_ROW

@@ -1,6 +1,6 @@
 // The explicit instantiations of the MFMA kernels: ONE unit of them per compilation, chosen on the command line (Makefile).
 //   -DNWE_INST_GROUP=NWE_SHAPES_A ... _F   the group of shapes (nwe_mfma_shapes.h)
-//   -DNWE_INST_VARIANT=kVariantPlain | kVariantTerm | kVariantShare | kVariantOcc | kVariantTail   the render kernels of that variant, or
+//   -DNWE_INST_VARIANT=kVariantPlain | kVariantTerm | kVariantShare | kVariantOcc | kVariantTail | kVariantList   the render kernels of that variant, or
 //   -DNWE_INST_QUERY                       the query kernels, or
 //   -DNWE_INST_QUERY_COUNTED               their counted forms (units of their own: the query units hold what they held)
 //   -DNWE_ONE_KERNEL=true|false            instead of all three: the headline kernel alone, folded or not (`make one`)

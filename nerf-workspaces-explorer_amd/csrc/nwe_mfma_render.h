@@ -285,6 +285,45 @@ __global__ void __launch_bounds__(256) render_mfma_occ_kernel(RenderArgs a_in, N
 #include "nwe_mfma_render_item.h"
 #undef NWE_ITEM_OCC
 }
+// LIST: a pixel list (include/nwe.h, nwe_render_pixels), for the LEAN kernels of the folded and the no-view-dirs formulations, in a
+// kernel of its own name: the other kernels keep their symbols and see no new token (NWE_ITEM_LIST).  The launch is a ray list's -
+// n_rays work rows, no packet blocks, no tail path - but ray `row` of it is the ray of pixel list[row] of the pinhole view the
+// camera fields describe, which seed_ray makes from three registers: no ray table, so the kernel is lean, with the density-only
+// coarse pass and the hollow colour path of the plain lean kernel.  The list comes in the slot of `rays`, which every lean kernel
+// nulls: read first, as int32, then nulled like the rest.  ray_cols, the columns of a ray table, is the poses of the camera here:
+// the listed value is clamped to 0 .. ray_cols * rows * W - 1, the rays of an nwe_render call with that camera, so that no value
+// makes make_ray read outside the pose table.  `row`, the index within the list, stays what every table row, every store and
+// live / gone use.  The queue's slot is free: the ticket prologue is render_mfma_kernel's.
+template <int W, int D, int SKIP, bool X3, bool SPLIT, int FORM>
+__global__ void __launch_bounds__(256) render_mfma_list_kernel(RenderArgs a_in, NetMfma nc, NetMfma nf) {
+    static_assert(FORM != kFormReference, "pixel list: lean kernels of the product formulations only");
+    constexpr bool LEAN = true, TERM = false, SHARE = false;
+    RenderArgs a = a_in;
+    const int32_t* const list = reinterpret_cast<const int32_t*>(a_in.rays);
+    a.out.raw_coarse = a.out.raw_fine = a.out.z_fine = a.out.weights_coarse = nullptr;
+    a.out.disp = a.out.z_std = a.out.rgb_coarse = a.out.depth_coarse = a.out.acc_coarse = a.out.disp_coarse = nullptr;
+    a.out.sample_cond = a.out.sample_amp = a.out.sample_switch = a.out.feat_map = nullptr;
+    a.z_fine_in = a.raw_in_c = a.raw_in_f = a.w_in = a.t_rand = a.noise_c = a.noise_f = a.u_rand = nullptr;
+    a.stamps = nullptr; a.rays = nullptr;
+    using S = Shape<W, D>;
+    using SM = Smem<W, D, SPLIT>;
+    __shared__ __attribute__((aligned(16))) char smem[SM::TOTAL];
+    static_assert(SM::CHUNKS >= 4 && SM::BOFF >= SM::CHUNKS && SM::WOFF > SM::BOFF && SM::TOFF > SM::BOFF && SM::GOFF > SM::BOFF,
+                  "the ticket's word lies in the chunk buffers, below every region the prologue writes in front of its barrier");
+    unsigned item = blockIdx.x;
+    if (a.queue) {
+        unsigned* s_item = reinterpret_cast<unsigned*>(smem);
+        if (threadIdx.x == 0) *s_item = atomicAdd(a.queue, 1u);
+        __syncthreads();
+        const unsigned ticket = *s_item;            // tested as the vector value it is read as (render_mfma_kernel)
+        if (ticket >= a.queue_items) return;
+        item = __builtin_amdgcn_readfirstlane(ticket);
+    }
+    NWE_STAMP(const unsigned stamp_item = item;)
+#define NWE_ITEM_LIST
+#include "nwe_mfma_render_item.h"
+#undef NWE_ITEM_LIST
+}
 #undef NWE_PRIME_STREAM
 #undef NWE_EVAL_POINT
 
@@ -311,7 +350,7 @@ void launch_one(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_p
         const unsigned items = mfma_workgroups(rays, split);
         // a queued launch (a.queue: a zeroed counter of this launch's own) deals its work items to a larger grid; the
         // terminating and the sharing kernels take no tickets, so their launches are never queued
-        const bool queued = (VARIANT == kVariantPlain || VARIANT == kVariantTail) && a.queue;
+        const bool queued = (VARIANT == kVariantPlain || VARIANT == kVariantTail || VARIANT == kVariantList) && a.queue;
         if (queued) a.queue_items = items;
         const unsigned grid = queued ? queue_grid(items) : items;
         RenderKernel kernel;
@@ -328,6 +367,11 @@ void launch_one(RenderArgs a, const NetMfma& nc, const NetMfma& nf, bool three_p
             kernel = kernels[three_pass ? 0 : 1];
         } else if constexpr (VARIANT == kVariantOcc) {   // lean only: the caller has checked
 #define NWE_KERNEL(X3_, SPLIT_) render_mfma_occ_kernel<W, D, SKIP, X3_, SPLIT_, FORM>
+            const RenderKernel kernels[4] = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true), NWE_KERNEL(false, false)};
+#undef NWE_KERNEL
+            kernel = kernels[(three_pass ? 0 : 2) + (split ? 0 : 1)];
+        } else if constexpr (VARIANT == kVariantList) {   // lean only, a.rays = the pixel list: the caller has checked
+#define NWE_KERNEL(X3_, SPLIT_) render_mfma_list_kernel<W, D, SKIP, X3_, SPLIT_, FORM>
             const RenderKernel kernels[4] = {NWE_KERNEL(true, true), NWE_KERNEL(true, false), NWE_KERNEL(false, true), NWE_KERNEL(false, false)};
 #undef NWE_KERNEL
             kernel = kernels[(three_pass ? 0 : 2) + (split ? 0 : 1)];

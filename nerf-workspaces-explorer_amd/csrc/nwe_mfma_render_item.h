@@ -9,6 +9,8 @@
 //   NWE_ITEM_OCC, defined by render_mfma_occ_kernel alone, with occ (const OccGrid*: the occupancy grid; that kernel's comment
 //   holds the argument).  The occupancy code is under the preprocessor, not under `if constexpr`, so that every other kernel
 //   compiles the very tokens it compiled before: their device code is the same to the byte (tools/device_code_digest.py).
+//   NWE_ITEM_LIST, defined by render_mfma_list_kernel alone, with list (const int32_t*: the call's pixel list), under the
+//   preprocessor for the same reason: the seed comes from the listed pixel, and there are no packet blocks.
 //   stamp_item (diagnostic builds only): the item's row group in the stamp buffer
 // and NWE_PRIME_STREAM / NWE_EVAL_POINT.  The first word of smem may hold a queued launch's ticket up to the barrier behind the
 // table copies.
@@ -39,7 +41,7 @@
     // One 32-bit row index per lane (the ABI keeps n_rays below 2^31): the ray's own index, or the call's last ray for the
     // lanes of a ragged last packet, which compute along and store nothing.  64-bit only where an offset is formed.
     int row_of = (int)(ridx64 < a.n_rays ? ridx64 : a.n_rays - 1);
-#ifndef NWE_ITEM_OCC
+#if !defined(NWE_ITEM_OCC) && !defined(NWE_ITEM_LIST)
     // A blocked call (nwe_packet_blocks.h; the lean plain and tail kernels, by plan_call's decision): the index names pixel pi(j),
     // so that the packet is an 8x4 block.  Everything from here on - the seed, the tables' rows, every store - sees the pixel; gone,
     // lane_live and live above are the index's, and such a call has no ragged packet.
@@ -53,7 +55,14 @@
     // construction): nothing of it but |d| stays in registers across an MLP evaluation.  The empty asm hides the seed from
     // loop-invariant code motion, which would otherwise hoist the expansion and spill its results.
     const bool producer = SHARE && share_role(a) == kShareProducer, consumer = SHARE && share_role(a) == kShareConsumer;
+#ifdef NWE_ITEM_LIST
+    // The seed of the listed pixel: one 4-byte load per lane, here and nowhere else, so the pointer and the pixel are dead before
+    // the sample loop.  Clamped into the rays of the camera's own nwe_render call (a.ray_cols poses): whatever the list holds, the
+    // pose index make_ray reads with lies in the pose table.  `row` stays the index within the list.
+    const RaySeed seed = seed_ray(a, min(max(list[row], 0), a.ray_cols * a.rows * a.W - 1));
+#else
     const RaySeed seed = seed_of<SHARE>(a, rclamp);
+#endif
     auto fresh_ray = [&]() __attribute__((always_inline)) {
         RaySeed sd = seed;
         asm volatile("" : "+v"(sd.pose), "+v"(sd.x), "+v"(sd.y));

@@ -71,7 +71,8 @@ PassPlan plan_pass(const PassDesc& d, int cus) {
 static int stage_variant(const CallDesc& c, int role, bool lean, int n_importance, bool w_in, int net) {
     const bool share = role != kShareOff && lean;
     int v = kVariantPlain;
-    if (c.occ) v = lean && role == kShareOff && !c.term ? kVariantOcc : -1;
+    if (c.list) v = lean && role == kShareOff && !c.term && !c.occ ? kVariantList : -1;
+    else if (c.occ) v = lean && role == kShareOff && !c.term ? kVariantOcc : -1;
     else if (c.term) v = lean && !share ? kVariantTerm : -1;
     else if (share) v = n_importance > 0 ? kVariantShare : -1;
     else if (role != kShareOff && (role == kShareProducer ? n_importance != 0 : !w_in)) v = -1;
@@ -125,7 +126,8 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     p.share_rays = p.coarse_launch ? k.n_rays : 0;
     if (!c.mfma) return p;
 
-    // Work queue: a call that is one fused plain MFMA kernel - plain kernels only: early termination, the occupancy grid, the
+    // Work queue: a call that is one fused plain MFMA kernel - plain kernels (and the list kernels, which take the plain kernel's
+    // tickets) only: early termination, the occupancy grid, the
     // shared coarse pass and separate passes keep their launches as they are - may deal its workgroups from the slot's counters,
     // and its hybrid plan's second launch may backfill the first from the slot's own stream.
     const bool plain_only = !p.separate && !p.share && !c.term && !c.occ;
@@ -143,7 +145,7 @@ CallPlan plan_call(const CallDesc& c, int cus) {
     if (k.active && !p.baked) k.pass = plan_pass(describe(k, !p.full, false), cus);
     PassDesc d = describe(m, !p.full, p.full || c.w_in);
     d.may_queue = plain_only && c.queue_mode != 0;
-    d.side = c.backfill; d.tail = c.tail;
+    d.side = c.backfill; d.tail = c.tail && !c.list;   // a pixel list has no tail path: it is planned as the ray list it replaces
     m.pass = plan_pass(d, cus);
     p.may_queue = m.pass.queued();   // a call that queues nothing pays nothing
     p.need_side = p.may_queue && c.backfill;

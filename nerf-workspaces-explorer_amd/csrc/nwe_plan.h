@@ -33,14 +33,15 @@ constexpr int kShareOff = 0, kShareProducer = 1, kShareConsumer = 2;
 //   term:  four, early termination (TERM; lean)        share: four, shared coarse pass (SHARE; lean)
 //   occ:   four, occupancy grid (render_mfma_occ_kernel; lean)
 //   tail:  two, render_mfma_tail_kernel (three-pass / single-pass, each holding both decompositions; lean)
-// The first four are what a plan's `variant` may say (nwe_debug_plan reports the number); the tail kernel is taken through
-// PassPlan::tail.
-enum Variant { kVariantPlain, kVariantTerm, kVariantShare, kVariantOcc, kVariantTail, kVariants };
+//   list:  four, pixel list (render_mfma_list_kernel; lean): the rays of listed pixels of a pinhole view (nwe_render_pixels)
+// The first four and the last are what a plan's `variant` may say (nwe_debug_plan reports the number); the tail kernel is taken
+// through PassPlan::tail.
+enum Variant { kVariantPlain, kVariantTerm, kVariantShare, kVariantOcc, kVariantTail, kVariantList, kVariants };
 
-// Whether a shape has a variant's kernels: the terminating, the sharing and the occupancy kernels exist for the product
+// Whether a shape has a variant's kernels: the terminating, the sharing, the occupancy and the list kernels exist for the product
 // formulations, kFormReference is a comparison path; every form has the plain kernels and, with them, the queue and the tail kernel.
 constexpr bool variant_built(int variant, int form) {
-    return variant == kVariantTerm || variant == kVariantShare || variant == kVariantOcc ? form != kFormReference : true;
+    return variant == kVariantTerm || variant == kVariantShare || variant == kVariantOcc || variant == kVariantList ? form != kFormReference : true;
 }
 
 // The grid of a queued MFMA launch of n work items (nwe_debug_set_work_queue): n plus a quarter, rounded up to a multiple of 8.
@@ -60,14 +61,14 @@ struct PassDesc {
     int64_t n_rays = 0;
     int n_samples = 0, n_importance = 0;
     int role = kShareOff;          // costs the launch: a producer runs the coarse pass alone, a consumer the fine pass alone
-    int variant = kVariantPlain;   // the kernels the stage takes: plain, term, share or occ; -1 = none can serve it (the plan is not ok)
+    int variant = kVariantPlain;   // the kernels the stage takes: plain, term, share, occ or list; -1 = none can serve it (the plan is not ok)
     bool lean = false;             // only rgb / depth / acc / flags of pinhole views, no hook, no table (is_lean without the stamps)
     bool stamps = false;           // a stamp buffer is set (nwe_debug_set_stamps): such a launch is not lean ...
     bool stamped_build = false;    // ... except, in a -DNWE_STAMPS build, for the tail path, whose kernel stamps all the same
     bool tail_built = false;       // the shape has the tail kernel
     int decomposition = -1;        // nwe_debug_set_decomposition: -1 = by cost, 0 / 1 / 2 forces a plan
     int queue_mode = -1;           // nwe_debug_set_work_queue: -1 = a launch with more work items than CUs, 1 = every launch
-    bool may_queue = false;        // the queue may be used at all: plain kernels only, and not under queue mode 0
+    bool may_queue = false;        // the queue may be used at all: plain and list kernels only, and not under queue mode 0
     bool side = false;             // a side stream is on offer for the second launch (NWE_WORK_QUEUE_BACKFILL)
     bool tail = false;             // the tail path is allowed (NWE_WORK_QUEUE_TAIL)
 };
@@ -121,6 +122,10 @@ struct CallDesc {
     bool backfill = true, tail = true;
     int rows = 0, width = 0;       // a pinhole call: the rows rendered per pose and the image width; 0 for a ray list
     bool packet_blocks = false;    // nwe_debug_set_packet_blocks
+    // A pixel-list call (nwe_render_pixels on the list kernels): planned as a ray list of n_rays rays (rows = width = 0: no packet
+    // blocks, no tail path), but lean - its kernels make the rays themselves - and on the shape's list kernels.  The caller has
+    // checked pixel_list_path (nwe_check.h): no mode is on.
+    bool list = false;
 };
 
 // One stage = one launch group with its own RenderArgs: the coarse stage (the producer of a shared coarse pass, the coarse

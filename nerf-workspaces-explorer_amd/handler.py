@@ -55,8 +55,11 @@ class NeRFReplicaInferenceHandler:
                  baked_coarse: Optional[Mapping[str, object]] = None,
                  radiance_grid: Optional[Mapping[str, object]] = None,
                  sparse_fine: Optional[Mapping[str, object]] = None, sparse_async: Optional[bool] = None,
-                 adaptive: Optional[Mapping[str, object]] = None) -> None:
-        """``adaptive``: a mapping with optional "k" (2), "tol_rgb" (2/255) and "tol_depth" (0.05): with it
+                 adaptive: Optional[Mapping[str, object]] = None, adaptive_lists: Optional[bool] = None) -> None:
+        """``adaptive_lists``: True, or NWE_ADAPTIVE_LISTS=1 in the environment, lets the adaptive frame hand its pixel lists to
+        the list kernels of ``render_pixels`` (Renderer.set_adaptive_pixel_lists): the same frame, its rendered pixels on lean
+        kernels.  It is an option of ``adaptive``: given without it, a ValueError.  Off by default.
+        ``adaptive``: a mapping with optional "k" (2), "tol_rgb" (2/255) and "tol_depth" (0.05): with it
         ``render_coordinates(preview=False)`` draws its frame through ``render_adaptive_batch`` - every k-th pixel and the
         pixels of the lattice cells whose corners disagree rendered by the networks, the rest interpolated
         (Renderer.render_adaptive) - an approximation, off by default.  The environment variable NWE_ADAPTIVE =
@@ -192,6 +195,12 @@ class NeRFReplicaInferenceHandler:
                               (self._baked_coarse is not None, "a baked coarse pass (baked_coarse)"), (bool(self._devices), "devices")):
                 if on:
                     raise ValueError(f"adaptive (the adaptive frame) is not supported together with {other}")
+        env_lists = os.environ.get("NWE_ADAPTIVE_LISTS", "").strip()
+        if env_lists not in ("", "0", "1"):
+            raise ValueError("NWE_ADAPTIVE_LISTS must be 0 or 1")
+        self._adaptive_lists = bool(adaptive_lists) if adaptive_lists is not None else env_lists == "1"
+        if self._adaptive_lists and self._adaptive is None:
+            raise ValueError("adaptive_lists is an option of the adaptive frame: give adaptive={...} too")
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -324,6 +333,8 @@ class NeRFReplicaInferenceHandler:
         self._renderer.set_early_termination(self._early_termination)
         self._renderer.set_shared_coarse(self._shared_coarse)
         self._renderer.set_separate_passes(self._separate_passes)
+        if self._adaptive_lists:
+            self._renderer.set_adaptive_pixel_lists(True)
         if self._auto_precision:
             nets = (_lib.NET_COARSE,) + ((_lib.NET_FINE,) if fine is not None else ())
             each = all(self._renderer.mfma_supported(w) for w in nets)
@@ -663,6 +674,49 @@ class NeRFReplicaInferenceHandler:
                                 rows=(r0, r1), precision=precision or self._precision, k=k, tol_rgb=tol_rgb, tol_depth=tol_depth,
                                 outputs=outputs)
         return {name: v if name == "flags" else v.reshape((poses.shape[0], r1 - r0, W) + tuple(v.shape[1:])) for name, v in res.items()}
+
+    def _single_renderer(self, what: str) -> Renderer:
+        r = self._need_renderer()
+        if isinstance(r, TiledRenderer):
+            raise NotImplementedError(f"{what} is rendered by one device: not with devices")
+        return r
+
+    def render_pixels(self, init_coordinates: COORD, coordinates: COORD, pixels) -> torch.Tensor:
+        """The listed pixels of the view ``render_coordinates`` draws: ``pixels`` holds indices h * W + w into its image (an int32
+        device tensor, or anything ``torch.as_tensor`` takes), in any order; returns their float rgb [n, 3] on the device, bit
+        for bit the float frame gathered at the list (Renderer.render_pixels)."""
+        r = self._single_renderer("a pixel list")
+        camera_pose = get_camera_poses_from_list_of_coordinates(init_coordinates, [coordinates])
+        H, W = self._img_h, self._img_w
+        pixels = torch.as_tensor(pixels, dtype=torch.int32).reshape(-1).to(r.device)
+        res = r.render_pixels(camera_pose.numpy(), H, W, pixels, fx=self._fx, fy=self._fy, cx=self._cx, cy=self._cy,
+                              near=self._depth_close_bound, far=self._depth_far_bound, precision=self._precision, outputs=("rgb",))
+        self._report_flags(res["flags"])
+        return res["rgb"]
+
+    def render_region(self, init_coordinates: COORD, coordinates: COORD, top: int, left: int, height: int, width: int) -> np.ndarray:
+        """The rectangle [top, top + height) x [left, left + width) of the view ``render_coordinates`` draws: uint8
+        [height, width, 3], equal to that crop of its image, with only those pixels rendered (Renderer.render_pixels; ``to8b`` on
+        the device and the pinned staging of ``render_coordinates``)."""
+        r = self._single_renderer("a region")
+        H, W = self._img_h, self._img_w
+        top, left, height, width = int(top), int(left), int(height), int(width)
+        if height < 1 or width < 1 or top < 0 or left < 0 or top + height > H or left + width > W:
+            raise ValueError(f"the region must be a non-empty rectangle inside the {H} x {W} image")
+        camera_pose = get_camera_poses_from_list_of_coordinates(init_coordinates, [coordinates])
+        rows_ = torch.arange(top, top + height, dtype=torch.int32, device=r.device)
+        cols_ = torch.arange(left, left + width, dtype=torch.int32, device=r.device)
+        pixels = (rows_[:, None] * W + cols_[None, :]).reshape(-1)
+        res = r.render_pixels(camera_pose.numpy(), H, W, pixels, fx=self._fx, fy=self._fy, cx=self._cx, cy=self._cy,
+                              near=self._depth_close_bound, far=self._depth_far_bound, precision=self._precision, outputs=("rgb",))
+        img = r.to8b(res["rgb"])
+        if self._stage is None or tuple(self._stage.shape) != (H, W, 3):
+            self._stage = torch.empty((H, W, 3), dtype=torch.uint8, pin_memory=True)
+        stage = self._stage.view(-1)[:height * width * 3].view(height, width, 3)   # the head of the frame's staging buffer
+        stage.copy_(img.reshape(height, width, 3), non_blocking=True)
+        torch.cuda.current_stream(img.device).synchronize()
+        self._report_flags(res["flags"])
+        return stage.numpy().copy()
 
     def last_adaptive(self):
         """The counts and the device span of the last adaptive frame (Renderer.last_adaptive), None if there was none."""

@@ -782,6 +782,73 @@ class Renderer:
             raise ValueError("adaptive lattice: an empty range, or k outside 1..64")
         return np.array(out[:n], dtype=np.int32)
 
+    def set_adaptive_pixel_lists(self, on: bool) -> None:
+        """Opt-in (nwe_set_adaptive_pixel_lists): ``render_adaptive`` hands its pixel lists to the list kernels of
+        ``render_pixels`` where they can serve the call, in place of ray tables.  The same bits; off by default."""
+        self._check(self._lib.nwe_set_adaptive_pixel_lists(self._ctx, 1 if on else 0), "nwe_set_adaptive_pixel_lists")
+
+    @property
+    def adaptive_pixel_lists(self) -> bool:
+        return int(self._lib.nwe_get_adaptive_pixel_lists(self._ctx)) == 1
+
+    # -- pixel list -------------------------------------------------------------------------------
+    def render_pixels(self, c2w, H: int, W: int, pixels: torch.Tensor, *, fx: float, fy: float, cx: float, cy: float, near: float,
+                      far: float, rows: Optional[Tuple[int, int]] = None, precision: str = "f16x3",
+                      outputs: Sequence[str] = ("rgb",)) -> Dict[str, torch.Tensor]:
+        """The listed pixels of a pinhole view (nwe_render_pixels): ``pixels`` is an int32 tensor [n] on this renderer's device
+        of ray indices of ``render`` with the same camera arguments, (p * rows + (h - rows[0])) * W + w, in any order, duplicates
+        allowed; a value outside the frame renders the clamped pixel.  Row i of every output holds, bit for bit, what ``render``
+        writes to row ``pixels[i]``.  Asynchronous on the current stream.  ``outputs``: a choice of "rgb", "depth", "acc" (at
+        least one); "flags" (the rgb / depth / acc bits only) is always returned."""
+        outputs = tuple(outputs)
+        unknown = set(outputs) - set(_lib.PIXEL_OUTPUT_FIELDS[:-1])
+        if unknown:
+            raise ValueError(f"unknown pixel outputs {sorted(unknown)}; have {_lib.PIXEL_OUTPUT_FIELDS[:-1]}")
+        if not isinstance(pixels, torch.Tensor) or pixels.dtype != torch.int32 or pixels.dim() != 1:
+            raise ValueError("pixels must be an int32 tensor [n]")
+        poses = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(-1, 4, 4))
+        r0, r1 = rows if rows is not None else (0, H)
+        o = _lib.PixelOutputs()
+        n = int(pixels.shape[0])
+        call = self._lib.nwe_render_pixels
+        if self.device is None:   # a host-only context: the ABI's own refusals, nothing allocated
+            for name in outputs:
+                setattr(o, name, 1)   # never written: every path of a host-only context refuses, or launches nothing
+            self._check(call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, r0, r1, 1 if n else None, n,
+                             _lib.PRECISIONS[precision], C.byref(o), None), "nwe_render_pixels")
+            return {}
+        if pixels.device != self.device:
+            raise ValueError(f"pixels must be on {self.device}")
+        pixels = pixels.contiguous()
+        shapes = {"rgb": (n, 3), "depth": (n,), "acc": (n,)}
+        with torch.cuda.device(self.device):
+            # at least one element each: an empty tensor has no pointer, and a call of no pixels still says what it asks for
+            bufs = {name: torch.empty(max(int(np.prod(shapes[name])), 1), dtype=torch.float32, device=self.device) for name in outputs}
+            res = {name: bufs[name][:int(np.prod(shapes[name]))].view(shapes[name]) for name in outputs}
+            res["flags"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            for name in _lib.PIXEL_OUTPUT_FIELDS:
+                setattr(o, name, (bufs[name] if name in bufs else res[name]).data_ptr() if name in res else None)
+            stream = torch.cuda.current_stream(self.device)
+            rc = call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, r0, r1, pixels.data_ptr() if n else None, n,
+                      _lib.PRECISIONS[precision], C.byref(o), stream.cuda_stream)
+            pixels.record_stream(stream)   # the launch reads the list after this call has returned
+        self._check(rc, "nwe_render_pixels")
+        return res
+
+    def last_pixels(self) -> Optional[Dict[str, object]]:
+        """{"n", "path"} of the last pixel-list launch that was recorded - ``render_pixels``, or a render launch of
+        ``render_adaptive`` under ``set_adaptive_pixel_lists`` - path "list" (the list kernels) or "rays" (a ray table); None if
+        there was none."""
+        n, path = C.c_int64(), C.c_int()
+        if self._lib.nwe_last_pixels(self._ctx, C.byref(n), C.byref(path)) != _lib.NWE_OK:
+            return None
+        return {"n": int(n.value), "path": "list" if path.value == 1 else "rays"}
+
+    def pixels_path(self, precision: str = "f16x3") -> str:
+        """The path ``render_pixels`` would take under ``precision`` as the context stands (nwe_debug_pixels_path; a host-only
+        context serves it): "list" or "rays"."""
+        return "list" if int(self._lib.nwe_debug_pixels_path(self._ctx, _lib.PRECISIONS[precision])) == 1 else "rays"
+
     def last_coarse_launch(self) -> Optional[Tuple[float, int]]:
         """(ms, rays) of the coarse (producer) launch of the last render, None if it had none (k = 1 without separate passes,
         n_importance == 0)."""
