@@ -803,6 +803,71 @@ int nwe_debug_adaptive_lattice(int first, int last_excl, int k, int32_t *out, in
 int nwe_set_adaptive_pixel_lists(nwe_ctx *ctx, int on);
 int nwe_get_adaptive_pixel_lists(const nwe_ctx *ctx);
 
+/* Multi-level adaptive frame, opt-in: the adaptive frame above on a hierarchy of nested lattices - start on a coarse lattice,
+ * subdivide only the cells whose corners disagree, render whole pixels only at the finest level.  An entry point of its own beside
+ * nwe_render_adaptive, which it leaves as it is.  Every pixel that is rendered has the bits nwe_render gives it.  The arguments are
+ * nwe_render_adaptive's, and `levels` in 1 .. 4.
+ * The rule, for each pose of the call on its own:
+ *   Levels.  k is the FINEST spacing.  Level l = 0 .. levels - 1 has the spacing s_l = k 2^(levels - 1 - l); s_0 must be at most 64.
+ *   Lattices.  Per axis of the CALL, in local coordinates 0 .. len - 1 (rows: h - row_begin), L_l = {i s_l < len} and len - 1:
+ *      nwe_render_adaptive's lattice at the spacing s_l.  The lattices are nested, L_l is a subset of L_(l+1), so every cell of
+ *      level l + 1 lies inside exactly one cell of level l, its PARENT.  levels = 1 is nwe_render_adaptive's lattice.
+ *   Pass 0.  Every pixel of L_0 x L_0 is rendered by the networks (kind 0).  Every level 0 cell is ACTIVE.
+ *   Level l = 0 .. levels - 1.  Behind render pass l every active cell of level l is FLAT or BUSY by nwe_render_adaptive's rule on its
+ *      four corners, unchanged: all pairs; r, g, b and acc within tol_rgb, depth within tol_depth; plain fp32; a NaN makes the cell
+ *      busy.  Its corners are rendered by then.
+ *        l < levels - 1:  the pixels of L_(l+1) x L_(l+1) that are not rendered yet and lie in the closed rectangle of at least
+ *           one busy cell of level l form render pass l + 1; the children of the busy cells become active.
+ *        l = levels - 1:  every pixel that is not rendered yet and lies in the closed rectangle of at least one busy cell forms
+ *           render pass `levels`.
+ *      The pixels of the passes 1 .. levels have kind 1.
+ *   Interpolation.  Every pixel that no pass rendered has kind 2.  Its OWN cell at level l is, on both axes, cell index
+ *      min(largest i with L_l[i] <= v, cells - 1) of that level's lattice.  The smallest l whose own cell is flat is taken - one
+ *      exists: own cells nest, and a pixel whose own cell of the finest level is busy is rendered - and the pixel is interpolated
+ *      in that cell with nwe_render_adaptive's arithmetic: fx, fy true fp32 divisions; along w on the top and on the bottom pair,
+ *      then along h; each step a + (b - a) f in three separately rounded fp32 operations.
+ *   Flags, modes, precisions, white background, separate passes, the hooks: as nwe_render_adaptive.
+ * LIMITATION: a feature that lies wholly inside a cell that is flat at level l and is narrower than s_l pixels is not seen.  More
+ * levels trade that for time: with levels = 3 and k = 2 the blind spot of a flat level 0 cell is 8 pixels wide.
+ * SYNCHRONOUS, as nwe_render_adaptive.  Between two passes ONE pinned read-back of two words - the pixels of the next pass and the
+ * busy cells of the level - tells the host what to launch.  A level without a busy cell ends the passes: nothing further is
+ * launched, classified or read back, so a frame that is flat at level 0 costs one render launch and one read-back; a call makes at
+ * the most levels + 1 render launches and `levels` read-backs.  (The interpolated counts of the report reach the host with the
+ * wait that ends the call.)  A count outside its range is NWE_ERR_HIP.
+ * The render launches are nwe_render_adaptive's - under nwe_set_adaptive_pixel_lists the list kernels where they can serve the
+ * call, the ray table otherwise, the same bits either way; the lists are in ascending pixel order - and the render reports
+ * afterwards describe the last launch made.  A ROW TILE has its own lattices: the call is not for nwe_render_tiled.
+ * The scratch is the adaptive frame's own (the two calls share it, each is synchronous).
+ * Refuses as nwe_render_adaptive, in its order and words, with one refusal more directly behind k: levels outside 1 .. 4, or
+ * k 2^(levels - 1) > 64 (NWE_ERR_INVALID).
+ *   nwe_last_adaptive_levels    out[0 .. 4 + 2 levels) = {pixels, lattice, levels, render_launches, rendered[levels] - the pixels of
+ *                               the passes 1 .. levels -, interpolated[levels] - the kind 2 pixels by the level of their cell} of
+ *                               the most recent call that ran, *ms (may be NULL) its device span, the read-back gaps included.
+ *                               Returns NWE_ERR_INVALID where cap < 4 + 2 levels, NWE_ERR_STATE if none ran.  nwe_last_adaptive is
+ *                               not moved by the call, nor this report by nwe_render_adaptive.
+ *   nwe_debug_adaptive_levels_lattice   the lattice of level `level` (0 .. levels - 1) of [first, last_excl): as
+ *                               nwe_debug_adaptive_lattice; -1 also for levels the call refuses.
+ *   nwe_debug_adaptive_levels_plan      what a call of n_poses poses, `rows` rows and `width` columns is planned as, for a call that
+ *                               is not made: out[0 .. 5 + 2 levels) = {pixels, lattice, list - the most pixels a render pass can
+ *                               hold -, scratch bytes, cells[levels], pass_max[levels + 1] - the most pixels of each pass}.  Returns
+ *                               the entries written, or -1 (a size below 1, more than 2^24 pixels, levels the call refuses, ray_cols
+ *                               other than 8 or 11, NULL, cap too small).  Needs no context. */
+typedef struct nwe_adaptive_levels_outputs {
+    uint64_t struct_bytes;  /* = sizeof(nwe_adaptive_levels_outputs) */
+    float *rgb;             /* [R,3] */
+    float *depth;           /* [R]   */
+    float *acc;             /* [R]   */
+    uint8_t *kind;          /* [R]    diagnostic, may be NULL: 0 level 0 lattice, 1 rendered, 2 interpolated */
+    uint32_t *flags;        /* [1]    NWE_FLAG_RGB / _DEPTH / _ACC, OR-ed (caller zeroes it) */
+    uint8_t *level;         /* [R]    diagnostic, may be NULL: kind 0: 0; kind 1: its pass, 1 .. levels; kind 2: the level of its cell */
+} nwe_adaptive_levels_outputs;
+int nwe_render_adaptive_levels(nwe_ctx *ctx, const float *c2w, int n_poses, int H, int W, float fx, float fy, float cx, float cy,
+                               float near, float far, int row_begin, int row_end, int precision, int k, int levels, float tol_rgb,
+                               float tol_depth, const nwe_adaptive_levels_outputs *out, void *stream);
+int nwe_last_adaptive_levels(nwe_ctx *ctx, int64_t *out, int cap, float *ms);
+int nwe_debug_adaptive_levels_lattice(int first, int last_excl, int k, int levels, int level, int32_t *out, int cap);
+int nwe_debug_adaptive_levels_plan(int n_poses, int rows, int width, int k, int levels, int ray_cols, int64_t *out, int cap);
+
 /* Pixel list: render any subset of the pixels of a pinhole view, in any order, on lean kernels.
  * The camera arguments are nwe_render's.  pixels_dev[i] is an output ray index of nwe_render with the same camera arguments,
  * (p * (row_end - row_begin) + (h - row_begin)) * W + w, and output row i holds, bit for bit, what nwe_render writes to that row.

@@ -38,7 +38,8 @@ SYMBOLS = ("nwe_create", "nwe_destroy", "nwe_last_error", "nwe_set_network", "nw
            "nwe_render_sparse_async", "nwe_debug_last_sparse_host_waits", "nwe_debug_query_counted_grid",
            "nwe_debug_set_packet_blocks", "nwe_debug_last_packet_blocks", "nwe_debug_packet_pixels",
            "nwe_render_adaptive", "nwe_last_adaptive", "nwe_debug_adaptive_lattice",
-           "nwe_set_adaptive_pixel_lists", "nwe_get_adaptive_pixel_lists", "nwe_render_pixels", "nwe_last_pixels", "nwe_debug_pixels_path")
+           "nwe_set_adaptive_pixel_lists", "nwe_get_adaptive_pixel_lists", "nwe_render_pixels", "nwe_last_pixels", "nwe_debug_pixels_path",
+           "nwe_render_adaptive_levels", "nwe_last_adaptive_levels", "nwe_debug_adaptive_levels_lattice", "nwe_debug_adaptive_levels_plan")
 
 
 class Outputs(C.Structure):
@@ -92,6 +93,18 @@ class AdaptiveOutputs(C.Structure):
 
     def __init__(self, **kw):
         super().__init__(struct_bytes=C.sizeof(AdaptiveOutputs), **kw)
+
+
+ADAPTIVE_LEVELS_OUTPUT_FIELDS = ADAPTIVE_OUTPUT_FIELDS + ("level",)
+ADAPTIVE_MAX_LEVELS = 4
+
+
+class AdaptiveLevelsOutputs(C.Structure):
+    """nwe_adaptive_levels_outputs of nwe_render_adaptive_levels."""
+    _fields_ = [("struct_bytes", C.c_uint64)] + [(name, C.c_void_p) for name in ADAPTIVE_LEVELS_OUTPUT_FIELDS]
+
+    def __init__(self, **kw):
+        super().__init__(struct_bytes=C.sizeof(AdaptiveLevelsOutputs), **kw)
 
 
 PIXEL_OUTPUT_FIELDS = ("rgb", "depth", "acc", "flags")
@@ -234,6 +247,10 @@ def load() -> C.CDLL:
         "nwe_render_pixels": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, P, I64, I, C.POINTER(PixelOutputs), P]),
         "nwe_last_pixels": (I, [P, C.POINTER(I64), C.POINTER(I)]),
         "nwe_debug_pixels_path": (I, [P, I]),
+        "nwe_render_adaptive_levels": (I, [P, P, I, I, I, F, F, F, F, F, F, I, I, I, I, I, F, F, C.POINTER(AdaptiveLevelsOutputs), P]),
+        "nwe_last_adaptive_levels": (I, [P, C.POINTER(I64), I, C.POINTER(F)]),
+        "nwe_debug_adaptive_levels_lattice": (I, [I, I, I, I, I, C.POINTER(C.c_int32), I]),
+        "nwe_debug_adaptive_levels_plan": (I, [I, I, I, I, I, I, C.POINTER(I64), I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the symbol is missing: loud by design

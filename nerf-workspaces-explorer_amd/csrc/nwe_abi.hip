@@ -69,6 +69,7 @@ int wait_for_launches(nwe_ctx* c) {
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     if (c->rays_slot.used) HIPCHK(c, hipEventSynchronize(c->rays_slot.ev1));
     if (c->adaptive_slot.used) HIPCHK(c, hipEventSynchronize(c->adaptive_slot.ev1));   // synchronous: long passed
+    if (c->adaptive_levels_slot.used) HIPCHK(c, hipEventSynchronize(c->adaptive_levels_slot.ev1));
     for (Slot& s : c->query.slots)  // a query streams the weights of its network throughout
         if (s.used) HIPCHK(c, hipEventSynchronize(s.ev1));
     for (Slot& s : c->grid.slots)    // a grid frame reads the sampling tables and the radiance grid

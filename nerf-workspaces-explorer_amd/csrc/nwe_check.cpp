@@ -359,21 +359,17 @@ Refusal check_render_sparse(const ContextDesc* d, const nwe_sparse_outputs* out,
     return {};
 }
 
-Refusal check_adaptive(const ContextDesc* d, const nwe_adaptive_outputs* out, const Camera& m, int precision, int k, float tol_rgb,
-                       float tol_depth) {
-    if (!d) return invalid("null context");
-    if (!out) return invalid("null outputs");
-    if (out->struct_bytes != sizeof(nwe_adaptive_outputs))
-        return invalid("nwe_adaptive_outputs.struct_bytes != sizeof(nwe_adaptive_outputs): the caller was built against another version of include/nwe.h");
-    if (!out->rgb && !out->depth && !out->acc) return invalid("none of rgb / depth / acc requested");
+// Everything both adaptive calls refuse behind their outputs; levels: null for nwe_render_adaptive, which has none.
+static Refusal check_adaptive_call(const ContextDesc* d, const Camera& m, int precision, int k, const int* levels, float tol_rgb, float tol_depth) {
     if (Refusal r = check_camera(m)) return r;
     const int64_t n_rays = (int64_t)m.n_poses * (m.row_end - m.row_begin) * m.W;
     if (Refusal r = check_ray_count(n_rays, false)) return r;
     if (n_rays > kAdaptiveMaxRays) return invalid("adaptive frame: more than 2^24 rays in one call");
     if (k < 1 || k > kAdaptiveMaxK) return invalid("adaptive frame: k must be in 1..64");
+    if (levels && !adaptive_levels_ok(k, *levels)) return invalid("adaptive frame: levels must be in 1..4 and k * 2^(levels - 1) at most 64");
     if (tol_rgb != tol_rgb || tol_depth != tol_depth) return invalid("adaptive frame: the tolerances must not be NaN");
     if (Refusal r = check_precision(precision)) return r;
-    // the two render launches are nwe_render_rays launches with lean outputs: what that call refuses of the context, in its words
+    // the render launches are nwe_render_rays launches with lean outputs: what that call refuses of the context, in its words
     static float somewhere;
     nwe_outputs lean = {};
     lean.struct_bytes = sizeof(nwe_outputs);
@@ -381,6 +377,26 @@ Refusal check_adaptive(const ContextDesc* d, const nwe_adaptive_outputs* out, co
     if (Refusal r = check_ready(d, &lean, precision, false, true)) return r;
     if (d->host_only) return state("host-only context cannot render");
     return {};
+}
+
+Refusal check_adaptive(const ContextDesc* d, const nwe_adaptive_outputs* out, const Camera& m, int precision, int k, float tol_rgb,
+                       float tol_depth) {
+    if (!d) return invalid("null context");
+    if (!out) return invalid("null outputs");
+    if (out->struct_bytes != sizeof(nwe_adaptive_outputs))
+        return invalid("nwe_adaptive_outputs.struct_bytes != sizeof(nwe_adaptive_outputs): the caller was built against another version of include/nwe.h");
+    if (!out->rgb && !out->depth && !out->acc) return invalid("none of rgb / depth / acc requested");
+    return check_adaptive_call(d, m, precision, k, nullptr, tol_rgb, tol_depth);
+}
+
+Refusal check_adaptive_levels(const ContextDesc* d, const nwe_adaptive_levels_outputs* out, const Camera& m, int precision, int k, int levels,
+                              float tol_rgb, float tol_depth) {
+    if (!d) return invalid("null context");
+    if (!out) return invalid("null outputs");
+    if (out->struct_bytes != sizeof(nwe_adaptive_levels_outputs))
+        return invalid("nwe_adaptive_levels_outputs.struct_bytes != sizeof(nwe_adaptive_levels_outputs): the caller was built against another version of include/nwe.h");
+    if (!out->rgb && !out->depth && !out->acc) return invalid("none of rgb / depth / acc requested");
+    return check_adaptive_call(d, m, precision, k, &levels, tol_rgb, tol_depth);
 }
 
 Refusal check_adaptive_pixel_lists(int on) {

@@ -119,6 +119,10 @@ constexpr int kSparseMaxDilate = 8;
 // so that everything in front can be asked of a host-only context - the device.
 Refusal check_adaptive(const ContextDesc* d, const nwe_adaptive_outputs* out, const Camera& m, int precision, int k, float tol_rgb,
                        float tol_depth);
+// nwe_render_adaptive_levels: check_adaptive in its order and words, with one refusal more directly behind k: levels outside 1 .. 4 or
+// a coarsest spacing k 2^(levels - 1) above 64.
+Refusal check_adaptive_levels(const ContextDesc* d, const nwe_adaptive_levels_outputs* out, const Camera& m, int precision, int k, int levels,
+                              float tol_rgb, float tol_depth);
 Refusal check_adaptive_pixel_lists(int on);
 // nwe_render_pixels, in the order it refuses in: the context, the outputs, the camera and its ray count as nwe_render refuses them,
 // the list (null_pixels: no list was given), the precision, everything check_ready refuses for a lean-output nwe_render_rays, and

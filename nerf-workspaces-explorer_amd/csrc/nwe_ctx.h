@@ -212,6 +212,12 @@ struct nwe_ctx {
     int64_t adaptive_counts[4] = {0, 0, 0, 0};
     bool adaptive_ran = false;
     int adaptive_lists = 0;   // nwe_set_adaptive_pixel_lists: 0 = off
+    // nwe_render_adaptive_levels: its own slot, its pinned words - {next pass, busy cells} of a read-back, then the interpolated
+    // counts - and its report {pixels, lattice, levels, render_launches, rendered[4], interpolated[4]}; the scratch is d_adaptive_scratch
+    Slot adaptive_levels_slot;
+    Owned<void*, hipHostFree> adaptive_levels_words;
+    int64_t adaptive_levels_counts[4 + 2 * kAdaptiveMaxLevels] = {};
+    bool adaptive_levels_ran = false;
     // nwe_last_pixels: the last pixel-list launch that was recorded - nwe_render_pixels, or a render launch of the adaptive frame
     // under nwe_set_adaptive_pixel_lists - its pixels and its path (1 list kernels, 0 ray table); -1: none yet
     int64_t pixels_n = 0;

@@ -174,6 +174,38 @@ void launch_adaptive_classify(const AdaptiveFrame& f, hipStream_t stream);
 // every pixel of the frame from the compact outputs: copied (kind 0, 1) or interpolated (kind 2); the kinds and the flags
 void launch_adaptive_compose(const AdaptiveFrame& f, hipStream_t stream);
 
+// ---- multi-level adaptive frame (nwe_render_adaptive_levels; nwe_adaptive_levels.hip) ----
+// The frame of a multi-level call as its kernels read it (by value): the axes of every level, the regions of the scratch
+// (AdaptiveLevelsPlan) and the caller's outputs.  The compact outputs hold the render passes one behind the other in the order
+// they ran; slot[p] is pixel p's index in them, -1 while no pass has rendered it.
+struct AdaptiveLevelsFrame {
+    AdaptiveAxis h[kAdaptiveMaxLevels], w[kAdaptiveMaxLevels];
+    int levels, n_poses, pixels;
+    float tol_rgb, tol_depth;
+    int32_t* list;                    // [n] the pixels of a render pass, ascending
+    float *c_rgb, *c_depth, *c_acc;   // compact outputs of all passes
+    int32_t* slot;                    // [pixels]
+    uint32_t* counts;                 // [pixels] 1 for a pixel of the next pass, then the exclusive scan
+    uint8_t* state[kAdaptiveMaxLevels];   // per level [n_poses][h.cells][w.cells]: kAdaptiveInactive / Flat / Busy
+    uint32_t* words;                  // [levels][2] {the pixels of pass l + 1, the busy cells of level l}
+    uint32_t* interp;                 // [levels] the kind 2 pixels by the level of their cell
+    const uint32_t* render_flags;     // [1] what the render launches raised
+    // compose alone: the first slot of pass i = 0 .. levels (INT32_MAX for a pass that never ran) and the levels that were classified
+    int base[kAdaptiveMaxLevels + 1];
+    int classified;
+    float *rgb, *depth, *acc;         // the caller's; each may be null
+    uint8_t *kind, *level;
+    uint32_t* flags;
+};
+constexpr uint8_t kAdaptiveInactive = 0, kAdaptiveFlat = 1, kAdaptiveBusy = 2;
+// pass 0: the level 0 lattice pixels into f.list, pose-major, lattice rows then columns, and their slots
+void launch_adaptive_levels_lattice(const AdaptiveLevelsFrame& f, int lattice, hipStream_t stream);
+// level l: cells -> states and the busy count; pixels -> the members of pass l + 1; their scan and total; the members into f.list and
+// their slots from `first` on
+void launch_adaptive_levels_classify(const AdaptiveLevelsFrame& f, int l, int first, hipStream_t stream);
+// every pixel of the frame from the compact outputs: copied or interpolated; kinds, levels, flags and the interpolated counts
+void launch_adaptive_levels_compose(const AdaptiveLevelsFrame& f, hipStream_t stream);
+
 // Self-test kernels (nwe_selftest.hip)
 int run_selftest(int32_t* report8, hipStream_t stream);
 

@@ -213,4 +213,33 @@ int adaptive_lattice(int first, int last_excl, int k, int32_t* out, int cap) {
     return x.n;
 }
 
+AdaptiveLevelsPlan plan_adaptive_levels(int n_poses, int rows, int width, int k, int levels, int ray_cols) {
+    AdaptiveLevelsPlan p;
+    p.levels = levels; p.n_poses = n_poses; p.cols = ray_cols;
+    p.pixels = (int64_t)n_poses * rows * width;
+    int64_t on_lattice = 0;   // the pixels of the level before
+    for (int l = 0; l < levels; ++l) {
+        p.h[l] = adaptive_axis(rows, adaptive_level_spacing(k, levels, l)); p.w[l] = adaptive_axis(width, adaptive_level_spacing(k, levels, l));
+        p.cells[l] = (int64_t)n_poses * p.h[l].cells * p.w[l].cells;
+        const int64_t now = (int64_t)n_poses * p.h[l].n * p.w[l].n;
+        p.pass_max[l] = now - on_lattice;   // the lattices are nested
+        on_lattice = now;
+    }
+    p.pass_max[levels] = p.pixels - on_lattice;
+    p.lattice = p.pass_max[0];
+    for (int i = 0; i <= levels; ++i) p.list = p.pass_max[i] > p.list ? p.pass_max[i] : p.list;
+    const auto take = [&](int64_t n) { const int64_t at = p.bytes; p.bytes += (n + 255) / 256 * 256; return at; };
+    p.at_list = take(p.list * 4); p.at_rays = take(p.list * ray_cols * 4);
+    p.at_rgb = take(p.pixels * 12); p.at_depth = take(p.pixels * 4); p.at_acc = take(p.pixels * 4);
+    p.at_slot = take(p.pixels * 4); p.at_counts = take(p.pixels * 4);
+    for (int l = 0; l < levels; ++l) p.at_state[l] = take(p.cells[l]);
+    p.at_words = take(2 * kAdaptiveMaxLevels * 4); p.at_interp = take(kAdaptiveMaxLevels * 4); p.at_flags = take(4);
+    return p;
+}
+
+int adaptive_levels_lattice(int first, int last_excl, int k, int levels, int level, int32_t* out, int cap) {
+    if (!adaptive_levels_ok(k, levels) || level < 0 || level >= levels) return -1;
+    return adaptive_lattice(first, last_excl, adaptive_level_spacing(k, levels, level), out, cap);
+}
+
 }  // namespace nwe

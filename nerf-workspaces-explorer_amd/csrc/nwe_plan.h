@@ -233,4 +233,36 @@ AdaptivePlan plan_adaptive(int n_poses, int rows, int width, int k, int ray_cols
 // range, k outside 1 .. kAdaptiveMaxK, a null array or one that is too small.
 int adaptive_lattice(int first, int last_excl, int k, int32_t* out, int cap);
 
+// ---- multi-level adaptive frame (nwe_render_adaptive_levels) ----
+constexpr int kAdaptiveMaxLevels = 4;
+// The spacing of level l of `levels` over the finest spacing k: k 2^(levels - 1 - l)
+NWE_HOST_DEVICE inline int adaptive_level_spacing(int k, int levels, int l) { return k << (levels - 1 - l); }
+// levels in 1 .. kAdaptiveMaxLevels and the coarsest spacing within kAdaptiveMaxK
+inline bool adaptive_levels_ok(int k, int levels) {
+    return k >= 1 && k <= kAdaptiveMaxK && levels >= 1 && levels <= kAdaptiveMaxLevels && ((int64_t)k << (levels - 1)) <= kAdaptiveMaxK;
+}
+
+// The lattices and the scratch of a multi-level call.  Level l has the axes h[l], w[l] (adaptive_axis at its spacing); render pass 0
+// holds the level 0 lattice, pass l = 1 .. levels - 1 at the most the pixels of the level l lattice that are not on level l - 1's,
+// pass `levels` at the most the pixels off the finest lattice.  The regions, in the order of their offsets, each rounded up to 256
+// bytes: the pixel list (4 per pixel of the largest pass), its rays (4 cols each), the compact rgb / depth / acc of all passes in
+// the order they run (12 + 4 + 4 per pixel), the slots (4 per pixel), the counts and their scan (4 per pixel), the cells' states
+// (1 per cell, level by level), the words ({next pass, busy cells} per level, 4 each), the interpolated pixels per level (4 each)
+// and the render launches' flag word (4).  n_poses, rows, width >= 1 and adaptive_levels_ok(k, levels).
+struct AdaptiveLevelsPlan {
+    int levels = 0, n_poses = 0, cols = 0;
+    AdaptiveAxis h[kAdaptiveMaxLevels], w[kAdaptiveMaxLevels];
+    int64_t pixels = 0, lattice = 0;                      // of the whole call; lattice = pass 0
+    int64_t cells[kAdaptiveMaxLevels] = {};               // of the whole call, per level
+    int64_t pass_max[kAdaptiveMaxLevels + 1] = {};        // the most pixels each render pass can hold
+    int64_t list = 0;                                     // max over pass_max
+    int64_t at_list = 0, at_rays = 0, at_rgb = 0, at_depth = 0, at_acc = 0, at_slot = 0, at_counts = 0, at_state[kAdaptiveMaxLevels] = {},
+            at_words = 0, at_interp = 0, at_flags = 0;
+    int64_t bytes = 0;
+};
+AdaptiveLevelsPlan plan_adaptive_levels(int n_poses, int rows, int width, int k, int levels, int ray_cols);
+// The lattice of level `level` of `levels` over [first, last_excl), as adaptive_lattice; -1 also where adaptive_levels_ok fails or
+// the level is outside 0 .. levels - 1.
+int adaptive_levels_lattice(int first, int last_excl, int k, int levels, int level, int32_t* out, int cap);
+
 }  // namespace nwe

@@ -55,8 +55,12 @@ class NeRFReplicaInferenceHandler:
                  baked_coarse: Optional[Mapping[str, object]] = None,
                  radiance_grid: Optional[Mapping[str, object]] = None,
                  sparse_fine: Optional[Mapping[str, object]] = None, sparse_async: Optional[bool] = None,
-                 adaptive: Optional[Mapping[str, object]] = None, adaptive_lists: Optional[bool] = None) -> None:
-        """``adaptive_lists``: True, or NWE_ADAPTIVE_LISTS=1 in the environment, lets the adaptive frame hand its pixel lists to
+                 adaptive: Optional[Mapping[str, object]] = None, adaptive_lists: Optional[bool] = None,
+                 adaptive_levels: Optional[int] = None) -> None:
+        """``adaptive_levels``: an integer 1 .. 4, or NWE_ADAPTIVE_LEVELS=n in the environment, draws the adaptive frame on that many
+        nested lattices (Renderer.render_adaptive, ``levels``): ``adaptive``'s k is the finest spacing, k 2^(levels - 1) <= 64 the
+        coarsest.  It is an option of ``adaptive``: given without it, a ValueError.  Off (None) by default: the one-level call.
+        ``adaptive_lists``: True, or NWE_ADAPTIVE_LISTS=1 in the environment, lets the adaptive frame hand its pixel lists to
         the list kernels of ``render_pixels`` (Renderer.set_adaptive_pixel_lists): the same frame, its rendered pixels on lean
         kernels.  It is an option of ``adaptive``: given without it, a ValueError.  Off by default.
         ``adaptive``: a mapping with optional "k" (2), "tol_rgb" (2/255) and "tol_depth" (0.05): with it
@@ -201,6 +205,8 @@ class NeRFReplicaInferenceHandler:
         self._adaptive_lists = bool(adaptive_lists) if adaptive_lists is not None else env_lists == "1"
         if self._adaptive_lists and self._adaptive is None:
             raise ValueError("adaptive_lists is an option of the adaptive frame: give adaptive={...} too")
+        self._adaptive_levels = self.parse_adaptive_levels(adaptive_levels, os.environ.get("NWE_ADAPTIVE_LEVELS", ""),
+                                                           None if self._adaptive is None else self._adaptive["k"])
         # "auto": the fp32-grade MFMA mode (f16x3) where the network shape has an MFMA instantiation (every shape the
         # reference's configs use), else the fp32 vector-ALU HIP kernel, with a notice - a legal YAML (say net_width 64) must
         # render, slowly, rather than raise.  Decided in initialize_models(), when the shapes are known.
@@ -294,6 +300,26 @@ class NeRFReplicaInferenceHandler:
                 raise ValueError(f"adaptive: {key} must be a number, not NaN")
             opt[key] = float(opt[key])
         return opt
+
+    @staticmethod
+    def parse_adaptive_levels(levels: Optional[int], env: str = "", k: Optional[int] = None) -> Optional[int]:
+        """The ``adaptive_levels`` option, NWE_ADAPTIVE_LEVELS (``env``) where it is not given; ``k``: the adaptive frame's k, None
+        without an adaptive frame.  None when neither is given."""
+        env = env.strip()
+        if levels is None and env == "":
+            return None
+        if levels is None:
+            try:
+                levels = int(env)
+            except ValueError:
+                raise ValueError("NWE_ADAPTIVE_LEVELS must be an integer in 1..4") from None
+        if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= _lib.ADAPTIVE_MAX_LEVELS:
+            raise ValueError("adaptive_levels must be an integer in 1..4")
+        if k is None:
+            raise ValueError("adaptive_levels is an option of the adaptive frame: give adaptive={...} too")
+        if k << (levels - 1) > _lib.ADAPTIVE_MAX_K:
+            raise ValueError("adaptive_levels: k * 2^(levels - 1) must be at most 64")
+        return levels
 
     # ------------------------------------------------------------------------------------------------
     def set_sampling(self, n_samples: int, n_importance: int) -> None:
@@ -432,7 +458,7 @@ class NeRFReplicaInferenceHandler:
                 res = self.render_sparse_batch(camera_pose.numpy(), H, W, outputs=("rgb",), asynchronous=self._sparse_async,
                                                **self._sparse_fine)
             elif self._adaptive is not None and not preview:
-                res = self.render_adaptive_batch(camera_pose.numpy(), H, W, outputs=("rgb",), **self._adaptive)
+                res = self.render_adaptive_batch(camera_pose.numpy(), H, W, outputs=("rgb",), levels=self._adaptive_levels, **self._adaptive)
             else:
                 res = self.render_batch(camera_pose.numpy(), H, W, outputs=("rgb",))
         finally:
@@ -651,16 +677,16 @@ class NeRFReplicaInferenceHandler:
 
     def render_adaptive(self, camera_pose, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
                         precision: Optional[str] = None, k: int = 2, tol_rgb: float = 2 / 255, tol_depth: float = 0.05,
-                        outputs: Sequence[str] = ("rgb",)) -> Dict[str, torch.Tensor]:
+                        outputs: Sequence[str] = ("rgb",), levels: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """``render`` as an adaptive frame (Renderer.render_adaptive): a lattice of every k-th pixel, the cells that are not flat,
-        the rest interpolated."""
+        the rest interpolated; ``levels``: None, or the nested lattices of the multi-level frame."""
         res = self.render_adaptive_batch(np.asarray(camera_pose, dtype=np.float32).reshape(1, 4, 4), H, W, rows=rows, precision=precision,
-                                         k=k, tol_rgb=tol_rgb, tol_depth=tol_depth, outputs=outputs)
+                                         k=k, tol_rgb=tol_rgb, tol_depth=tol_depth, outputs=outputs, levels=levels)
         return {name: v if name == "flags" else v[0] for name, v in res.items()}
 
     def render_adaptive_batch(self, poses, H: Optional[int] = None, W: Optional[int] = None, *, rows: Optional[Tuple[int, int]] = None,
                               precision: Optional[str] = None, k: int = 2, tol_rgb: float = 2 / 255, tol_depth: float = 0.05,
-                              outputs: Sequence[str] = ("rgb",)) -> Dict[str, torch.Tensor]:
+                              outputs: Sequence[str] = ("rgb",), levels: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """``render_batch`` as an adaptive frame: [B,4,4] poses -> tensors with leading [B, h, W]; each pose has its own lattice."""
         r = self._need_renderer()
         if isinstance(r, TiledRenderer):
@@ -672,7 +698,7 @@ class NeRFReplicaInferenceHandler:
         r0, r1 = rows if rows is not None else (0, H)
         res = r.render_adaptive(poses, H, W, fx=fx, fy=fy, cx=cx, cy=cy, near=self._depth_close_bound, far=self._depth_far_bound,
                                 rows=(r0, r1), precision=precision or self._precision, k=k, tol_rgb=tol_rgb, tol_depth=tol_depth,
-                                outputs=outputs)
+                                outputs=outputs, levels=levels)
         return {name: v if name == "flags" else v.reshape((poses.shape[0], r1 - r0, W) + tuple(v.shape[1:])) for name, v in res.items()}
 
     def _single_renderer(self, what: str) -> Renderer:
@@ -721,6 +747,10 @@ class NeRFReplicaInferenceHandler:
     def last_adaptive(self):
         """The counts and the device span of the last adaptive frame (Renderer.last_adaptive), None if there was none."""
         return self._need_renderer().last_adaptive()
+
+    def last_adaptive_levels(self):
+        """The report of the last multi-level adaptive frame (Renderer.last_adaptive_levels), None if there was none."""
+        return self._need_renderer().last_adaptive_levels()
 
     @property
     def coarse_grid(self):

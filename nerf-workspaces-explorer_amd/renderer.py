@@ -727,41 +727,73 @@ class Renderer:
     # -- adaptive frame ---------------------------------------------------------------------------
     def render_adaptive(self, c2w, H: int, W: int, *, fx: float, fy: float, cx: float, cy: float, near: float, far: float,
                         rows: Optional[Tuple[int, int]] = None, precision: str = "f16x3", k: int = 2, tol_rgb: float = 2 / 255,
-                        tol_depth: float = 0.05, outputs: Sequence[str] = ("rgb",)) -> Dict[str, torch.Tensor]:
+                        tol_depth: float = 0.05, outputs: Sequence[str] = ("rgb",), levels: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """An adaptive frame (nwe_render_adaptive): the lattice of every ``k``-th pixel and the pixels of the lattice cells whose
         corners differ by more than ``tol_rgb`` (r, g, b, acc) or ``tol_depth`` are rendered by the networks, bit for bit as
         ``render`` renders them; the pixels of the other cells are interpolated bilinearly.  Synchronous.  ``outputs``: a choice
         of "rgb", "depth", "acc" (at least one) and the diagnostic "kind" [R] (uint8: 0 lattice, 1 rendered, 2 interpolated);
-        "flags" is always returned."""
+        "flags" is always returned.
+        ``levels``: None is that call.  An integer 1 .. 4 takes the multi-level frame (nwe_render_adaptive_levels): ``k`` is then
+        the finest of ``levels`` nested lattices, the coarsest has the spacing k 2^(levels - 1) <= 64, and only the cells whose
+        corners disagree are subdivided; ``outputs`` may then hold the diagnostic "level" [R] (uint8: the pass that rendered a
+        pixel, or the level of the cell it was interpolated in)."""
         outputs = tuple(outputs)
-        unknown = set(outputs) - set(_lib.ADAPTIVE_OUTPUT_FIELDS[:-1])
+        fields = _lib.ADAPTIVE_OUTPUT_FIELDS if levels is None else _lib.ADAPTIVE_LEVELS_OUTPUT_FIELDS
+        have = tuple(name for name in fields if name != "flags")
+        unknown = set(outputs) - set(have)
         if unknown:
-            raise ValueError(f"unknown adaptive outputs {sorted(unknown)}; have {_lib.ADAPTIVE_OUTPUT_FIELDS[:-1]}")
+            raise ValueError(f"unknown adaptive outputs {sorted(unknown)}; have {have}")
         poses = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32).reshape(-1, 4, 4))
         r0, r1 = rows if rows is not None else (0, H)
-        o = _lib.AdaptiveOutputs()
-        tail = (r0, r1, _lib.PRECISIONS[precision], int(k), float(tol_rgb), float(tol_depth))
-        call = self._lib.nwe_render_adaptive
+        if levels is None:
+            o, who, call = _lib.AdaptiveOutputs(), "nwe_render_adaptive", self._lib.nwe_render_adaptive
+            tail = (r0, r1, _lib.PRECISIONS[precision], int(k), float(tol_rgb), float(tol_depth))
+        else:
+            o, who, call = _lib.AdaptiveLevelsOutputs(), "nwe_render_adaptive_levels", self._lib.nwe_render_adaptive_levels
+            tail = (r0, r1, _lib.PRECISIONS[precision], int(k), int(levels), float(tol_rgb), float(tol_depth))
         if self.device is None:   # a host-only context: the ABI's own refusals, nothing allocated
             for name in outputs:
                 setattr(o, name, 1)   # never written: every path of a host-only context refuses
-            self._check(call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail, C.byref(o), None),
-                        "nwe_render_adaptive")
-            raise RuntimeError("nwe_render_adaptive: a host-only context rendered")   # not reached
+            self._check(call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail, C.byref(o), None), who)
+            raise RuntimeError(f"{who}: a host-only context rendered")   # not reached
         n_rays = poses.shape[0] * max(r1 - r0, 0) * W
-        shapes = {"rgb": (n_rays, 3), "depth": (n_rays,), "acc": (n_rays,), "kind": (n_rays,)}
+        shapes = {"rgb": (n_rays, 3), "depth": (n_rays,), "acc": (n_rays,), "kind": (n_rays,), "level": (n_rays,)}
         with torch.cuda.device(self.device):
             # at least one element each: an empty tensor has no pointer, and a call of zero rays still says what it asks for
-            bufs = {name: torch.empty(max(int(np.prod(shapes[name])), 1), dtype=torch.uint8 if name == "kind" else torch.float32,
+            bufs = {name: torch.empty(max(int(np.prod(shapes[name])), 1), dtype=torch.uint8 if name in ("kind", "level") else torch.float32,
                                       device=self.device) for name in outputs}
             res = {name: bufs[name][:int(np.prod(shapes[name]))].view(shapes[name]) for name in outputs}
             res["flags"] = torch.zeros(1, dtype=torch.int32, device=self.device)
-            for name in _lib.ADAPTIVE_OUTPUT_FIELDS:
+            for name in fields:
                 setattr(o, name, (bufs[name] if name in bufs else res[name]).data_ptr() if name in res else None)
             stream = torch.cuda.current_stream(self.device).cuda_stream
             rc = call(self._ctx, poses.ctypes.data, poses.shape[0], H, W, fx, fy, cx, cy, near, far, *tail, C.byref(o), stream)
-        self._check(rc, "nwe_render_adaptive")
+        self._check(rc, who)
         return res
+
+    def last_adaptive_levels(self) -> Optional[Dict[str, object]]:
+        """{"pixels", "lattice", "levels", "render_launches", "rendered", "interpolated", "ms"} of the last multi-level
+        ``render_adaptive`` call that ran: ``rendered[i]`` the pixels of render pass i + 1, ``interpolated[l]`` the pixels
+        interpolated in a cell of level l (lists of ``levels`` entries); None if there was none."""
+        cap = 4 + 2 * _lib.ADAPTIVE_MAX_LEVELS
+        out, ms = (C.c_int64 * cap)(), C.c_float(-1.0)
+        if self._lib.nwe_last_adaptive_levels(self._ctx, out, cap, C.byref(ms)) != _lib.NWE_OK:
+            return None
+        n = int(out[2])
+        return {"pixels": int(out[0]), "lattice": int(out[1]), "levels": n, "render_launches": int(out[3]),
+                "rendered": [int(v) for v in out[4:4 + n]], "interpolated": [int(v) for v in out[4 + n:4 + 2 * n]], "ms": float(ms.value)}
+
+    @staticmethod
+    def adaptive_levels_lattice(first: int, last_excl: int, k: int, levels: int, level: int) -> np.ndarray:
+        """The lattice rows (or columns) of [first, last_excl) at level ``level`` of ``levels`` over the finest spacing ``k``
+        (nwe_debug_adaptive_levels_lattice; needs no context)."""
+        lib = _lib.load()
+        cap = max(int(last_excl) - int(first), 1)
+        out = (C.c_int32 * cap)()
+        n = lib.nwe_debug_adaptive_levels_lattice(int(first), int(last_excl), int(k), int(levels), int(level), out, cap)
+        if n < 0:
+            raise ValueError("adaptive lattice: an empty range, k outside 1..64, levels outside 1..4, k * 2^(levels - 1) > 64 or a level outside 0..levels - 1")
+        return np.array(out[:n], dtype=np.int32)
 
     def last_adaptive(self) -> Optional[Dict[str, object]]:
         """{"pixels", "lattice", "rendered", "interpolated", "ms"} of the last ``render_adaptive`` call that ran (ms: its device
